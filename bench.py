@@ -4,11 +4,14 @@
 A "step" is one pass of the batched decode over one synthetic batch whose compressed payload is already resident in
 HBM; output stays in HBM.  Headline workload = the batch the metric is quoted on: 10 000 Yaz0 streams x 256 KiB per GPU
 (`--stream-kib 64` gives BASELINE.json configs[1] exactly).  `value` is measured with ONE batch in flight -- K steps back to
-back on one HIP stream, the execution the `roofline` object and the rocprofv3 summaries under profiles/ describe; the
-figure with two batches in flight (the tail of one launch overlapping the head of the next) is reported next to it as
-`config.pipelined`.
+back on one HIP stream, the execution the `roofline` object and the rocprofv3 summaries under profiles/ describe.
 
-On one GPU the same JSON line also carries (rank 0, skipped with --configs none):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what that figure needs: it generates and uploads the batch, runs
+W untimed and K timed steps, checks every stream's status and length, writes the last step's outputs when --dump-outputs DIR
+is given (per-stream results, a CRC-32 of every stream's bytes and the bytes of a fixed, seeded sample of streams, as .npy) and
+prints the line.  Everything else runs with --full only: the byte check of the first 1 024 streams against the CPU restatement
+(`config.verified_vs_oracle`), the figure with two batches in flight (the tail of one launch overlapping the head of the next,
+`config.pipelined`), and on one GPU (rank 0; --configs / --no-* select among them):
   configs       BASELINE.json configs[1..4] at their stated sizes (cfg2 Yaz0 10 000 x 64 KiB, cfg3 LZ4 100 000 x 256 KiB, one
                 GPU's shard of cfg4 = 5 000 mixed LZ10/LZ11/Yaz0/PRS streams, cfg5 compression as LZSS at Q0 / Q8 / Q15 and as
                 Yaz0 / LZ4 at Q0 / Q8), every other decode body of north_star on the headline's shape (body_<format>), ONE 1 000 KiB
@@ -23,7 +26,7 @@ Multi-GPU: one process per GPU (`python -m torch.distributed.run ... bench.py --
 starts exactly that as a child process).  --scaling weak (default): every rank decodes its own batch of --streams streams.
 --scaling strong: ONE batch of --streams streams is partitioned over the ranks by alz_partition_batch (greedy LPT, the
 library's host-side partitioner) -- `--scaling strong --format mixed --streams 40000` is BASELINE.json configs[3].  Either
-way there is no data-path collective; value = bytes decoded by all ranks / max time, and every rank checks its first
+way there is no data-path collective; value = bytes decoded by all ranks / max time, and with --full every rank checks its first
 1 024 streams byte for byte against the CPU restatement.
 
 Rank 0 prints the full record as a `BENCH_DETAIL {...}` line (also written to bench_detail.json) and then, LAST, the small contract
@@ -68,15 +71,32 @@ def parse_args():
     ap.add_argument("--streams", type=int, default=10000, help="streams per GPU (weak scaling) or in the whole batch (strong scaling)")
     ap.add_argument("--stream-kib", type=int, default=256)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--configs", default="all", help="all | none | comma list of cfg2,cfg3,cfg4,cfg5,realistic (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the pipelined figure, the byte check against the CPU "
+                         "restatement, the CPU baseline, copy bandwidth and end-to-end, the named configurations (the --no-* options and "
+                         "--configs / --inflight select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, <= 64 MB; rank 0's streams)")
+    ap.add_argument("--configs", default=None, help="--full: all (default) | none | comma list of cfg2,cfg3,cfg4,cfg5,bodies,realistic,single (N = 1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the byte comparison with the CPU restatement")
     ap.add_argument("--no-extras", action="store_true", help="skip copy bandwidth and the end-to-end (host buffer) run")
-    ap.add_argument("--inflight", type=int, default=2, help="batches in flight of the secondary, pipelined figure (1 = do not measure it)")
+    ap.add_argument("--inflight", type=int, default=None, help="--full: batches in flight of the secondary, pipelined figure (default 2; 1 = do not measure it)")
     ap.add_argument("--kernel-variant", type=int, default=0, help="alz_ctx_set_kernel_variant: 0 the library chooses, 1 / 2 one / two wavefronts per stream where both shapes exist (tuning)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU smoke tests of the N>1 path)")
     ap.add_argument("--all-ranks-on-device", type=int, default=-1, help="smoke test: every rank uses this GPU (needs --dist-backend gloo)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and ((args.configs or "none") != "none" or (args.inflight or 1) > 1):
+        ap.error("--configs and --inflight > 1 measure beyond the headline figure: add --full")
+    if args.configs is None:
+        args.configs = "all" if args.full else "none"
+    if args.inflight is None:
+        args.inflight = 2 if args.full else 1
+    if not args.full:                  # a plain run: set up, warm up, time the K steps, dump, print the line -- nothing else
+        args.no_cpu_baseline = args.no_verify = args.no_extras = True
+    return args
 
 
 def spawn_ranks(args):
@@ -316,6 +336,54 @@ def run_steps(db, steps, warmup, sync):
     return time.perf_counter() - t0, kernel_ms
 
 
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_VALUES = 12 << 20      # bytes of the sampled streams (float32: 48 MB)
+DUMP_SEED = 0x5EED
+
+
+def stream_outputs(ctx, np, d_buf, offs, lens, cap, n_arrays):
+    """What a caller of the timed path receives, stream by stream, as arrays for --dump-outputs: the CRC-32 of every stream's bytes
+    d_buf[offs[i] : offs[i] + lens[i]] (all of them, copied back in chunks of ~64 MB), the indices of a fixed, seeded sample of the
+    streams and those streams' bytes, zero beyond each one's length.  `n_arrays`: how many per-stream float64 arrays the caller
+    writes beside these (the sample gets what the 64 MB leave)."""
+    import zlib
+    n = len(offs)
+    per_stream = (n_arrays + 2) * 8 * n
+    if per_stream > DUMP_MAX_BYTES // 2:
+        raise ValueError("--dump-outputs: %d streams need %d bytes of per-stream arrays, more than %d" % (n, per_stream, DUMP_MAX_BYTES // 2))
+    crc = np.zeros(n, dtype=np.float64)
+    chunk = max(1, (64 << 20) // cap)
+    for i in range(0, n, chunk):
+        j = min(n, i + chunk)
+        base = int(offs[i])
+        span = int(offs[j - 1]) + int(lens[j - 1]) - base
+        h = ctx.d2h(d_buf, span, offset=base) if span > 0 else np.zeros(0, dtype=np.uint8)
+        for k in range(i, j):
+            a = int(offs[k]) - base
+            crc[k] = zlib.crc32(h[a:a + int(lens[k])])
+    values = min(DUMP_SAMPLE_VALUES, (DUMP_MAX_BYTES - per_stream) // 4)
+    width = min(cap, values)
+    k = min(n, values // width)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    sample = np.zeros((k, width), dtype=np.float32)
+    for r, i in enumerate(pick):
+        m = min(int(lens[i]), width)
+        if m:
+            sample[r, :m] = ctx.d2h(d_buf, m, offset=int(offs[i]))
+    return crc, pick.astype(np.float64), sample
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 or float64, at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def best_of_two(db, steps, sync):
     """The secondary configurations (not the headline, whose K steps are timed exactly once): two passes of K steps, the better wall
     clock reported with its own device time -- one pass in eight showed a host-side stall of tens of milliseconds between two launches
@@ -418,6 +486,14 @@ def main():
     # ---- the timed region: EXACTLY K steps between barriers, one batch in flight
     dt_local, kernel_ms = run_steps(main_db, args.steps, args.warmup, barrier)
     dt = reduce_step_time(dt_local, dist, device=red_dev)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after the last step: the per-stream results and the decoded bytes (left in HBM)
+        r0 = synth.result_records(main_db.plan.results())
+        lens = np.minimum(r0["dst_len"], recs["dst_cap"])
+        crc, pick, sample = stream_outputs(ctx, np, main_db.d_dst, recs["dst_off"], lens, target, 3)
+        dump_outputs(args.dump_outputs, {"status": r0["status"].astype(np.float64), "dst_len": r0["dst_len"].astype(np.float64),
+                                         "src_used": r0["src_used"].astype(np.float64), "decoded_crc32": crc, "sample_streams": pick,
+                                         "decoded_sample": sample})
 
     # ---- secondary: the same steps with two batches in flight (two HIP streams, two plans, two output buffers)
     pipelined = None
@@ -567,6 +643,13 @@ def run_encode_mode(args, np, A, synth, Context, Plan, shard_seed, reduce_step_t
     dt = reduce_step_time(time.perf_counter() - t0, dist, device=red_dev)
     kernel_ms = ctx.last_kernel_ms()
     er = synth.result_records(eres)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after the last step: per-stream results + aux and the compressed streams (left in HBM)
+        lens = np.minimum(er["dst_len"], r2["dst_cap"])
+        crc, pick, sample = stream_outputs(ctx, np, d_out, r2["dst_off"], lens, cap, 4)
+        dump_outputs(args.dump_outputs, {"status": er["status"].astype(np.float64), "dst_len": er["dst_len"].astype(np.float64),
+                                         "aux": np.frombuffer(aux, dtype=np.uint32).reshape(n, 2).astype(np.float64), "compressed_crc32": crc,
+                                         "sample_streams": pick, "compressed_sample": sample})
     comp = int(er["dst_len"].astype(np.int64).sum())
     ok = bool((rres["status"] == 0).all() and (er["status"] == 0).all())
     # what was written decodes back to the raw buffers (on the device), and the first buffers are the managed encoder's bytes

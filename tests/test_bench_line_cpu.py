@@ -5,6 +5,8 @@ import os
 import sys
 from contextlib import redirect_stdout
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (importing bench.py touches neither HIP nor torch)
@@ -133,3 +135,60 @@ def test_committed_counters_belong_to_the_kernels_at_head():
     assert r["counters_stale"] is False and r["traffic"] is not None and "issue" in r
     line = json.loads(bench.contract_line({"metric": "m", "value": 1.0, "unit": "u", "roofline": r, "config": {"workload": "w"}}))
     assert line["roofline"]["counters_stale"] is False
+
+
+def _args(monkeypatch, *argv):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+    return bench.parse_args()
+
+
+def test_a_plain_run_measures_the_headline_only_and_full_measures_the_rest(monkeypatch):
+    a = _args(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.configs == "none" and a.inflight == 1 and a.no_cpu_baseline and a.no_verify and a.no_extras
+    a = _args(monkeypatch, "--full")
+    assert a.full and a.configs == "all" and a.inflight == 2 and not (a.no_cpu_baseline or a.no_verify or a.no_extras)
+    a = _args(monkeypatch, "--full", "--configs", "cfg5", "--no-cpu-baseline", "--inflight", "1")
+    assert a.configs == "cfg5" and a.inflight == 1 and a.no_cpu_baseline and not a.no_verify
+    a = _args(monkeypatch, "--configs", "none", "--inflight", "1", "--no-verify")        # (what the profiling scripts pass: already the plain run)
+    assert a.configs == "none" and a.inflight == 1 and not a.full
+    for bad in (["--configs", "cfg2"], ["--inflight", "2"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            _args(monkeypatch, *bad)
+
+
+class _FakeCtx:
+    """d2h over a host array standing in for a device buffer."""
+
+    def __init__(self, mem):
+        self.mem = mem
+
+    def d2h(self, d, nbytes, offset=0):
+        assert d == "buf" and 0 <= offset and offset + nbytes <= len(self.mem)
+        return self.mem[offset:offset + nbytes].copy()
+
+
+def test_dumped_outputs_cover_every_stream_and_stay_within_64_mb(tmp_path):
+    import zlib
+    import numpy as np
+    n, cap, stride = 300, 65536, 65536 + 256
+    rng = np.random.default_rng(1)
+    mem = rng.integers(0, 256, n * stride + 64, dtype=np.uint8)
+    offs = np.arange(n, dtype=np.uint64) * np.uint64(stride)
+    lens = rng.integers(0, cap + 1, n).astype(np.uint32)
+    crc, pick, sample = bench.stream_outputs(_FakeCtx(mem), np, "buf", offs, lens, cap, 3)
+    for i in range(n):
+        assert crc[i] == zlib.crc32(mem[int(offs[i]):int(offs[i]) + int(lens[i])].tobytes())
+    assert sample.dtype == np.float32 and sample.shape == (len(pick), cap) and len(pick) == min(n, bench.DUMP_SAMPLE_VALUES // cap)
+    for r, i in enumerate(pick.astype(int)):
+        m = int(lens[i])
+        assert np.array_equal(sample[r, :m], mem[int(offs[i]):int(offs[i]) + m]) and not sample[r, m:].any()
+    assert np.array_equal(pick, bench.stream_outputs(_FakeCtx(mem), np, "buf", offs, lens, cap, 3)[1])        # a fixed sample
+    arrays = {"status": np.zeros(n), "dst_len": lens.astype(np.float64), "src_used": np.zeros(n), "decoded_crc32": crc, "sample_streams": pick,
+              "decoded_sample": sample}
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    assert sum(os.path.getsize(tmp_path / "out" / (k + ".npy")) for k in arrays) <= bench.DUMP_MAX_BYTES + 4096
+    assert np.array_equal(np.load(tmp_path / "out" / "decoded_sample.npy"), sample)
+    # a stream capacity wider than the whole sample budget: one row of the budget's width
+    crc1, pick1, sample1 = bench.stream_outputs(_FakeCtx(mem), np, "buf", offs[:1], np.array([cap], dtype=np.uint32), 64 << 20, 3)
+    assert sample1.shape == (1, bench.DUMP_SAMPLE_VALUES) and crc1[0] == zlib.crc32(mem[:cap].tobytes())

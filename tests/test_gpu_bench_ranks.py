@@ -31,7 +31,7 @@ def _bench(clean_launcher):
 def _bench_via(launch, *extra, gpus=2):
     shared = ["--dist-backend", "gloo", "--all-ranks-on-device", "0"] if _ndev() < gpus else []       # enough GPUs: one device per rank, RCCL
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus)] + shared + ["--steps", "2",
-           "--warmup", "1", "--configs", "none", "--no-extras", "--no-cpu-baseline", "--inflight", "1"] + list(extra)
+           "--warmup", "1", "--full", "--configs", "none", "--no-extras", "--no-cpu-baseline", "--inflight", "1"] + list(extra)   # (--full: every rank's byte check)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     rc, out, err = launch(cmd, env=env, cwd=ROOT, timeout=900)
     lines = [l for l in out.splitlines() if l.startswith("{")]

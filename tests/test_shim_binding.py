@@ -100,12 +100,14 @@ def test_every_format_class_implements_the_reference_surface():
 
 # ------------------------------------------------------------------------------------------------------------------
 # Behaviour the compiler would not catch either: property defaults, static signatures with their default arguments and the
-# interface lists of every shim class against the reference class it names (needs /root/reference: skipped on the GPU box),
-# and the parameter TYPES of every [DllImport] against the header.
+# interface lists of every shim class against the reference class it names (tests/golden/ref_surfaces.json: the reference classes'
+# surfaces, extracted by tests/golden/make_ref_surfaces.py), and the parameter TYPES of every [DllImport] against the header.
+import json
+
 import pytest
 
-REF = "/root/reference/src"
-REF_CLASSES = {   # shim file -> (shim class, reference files that hold the class)
+REF_SURFACES = os.path.join(ROOT, "tests", "golden", "ref_surfaces.json")
+REF_CLASSES = {   # shim file -> (shim class, reference files that hold the class, under the reference's source directory)
     "LZ10.cs": ("LZ10", ["AuroraLib.Compression.Nintendo/Nintendo/LZ10.cs"]),
     "LZ11.cs": ("LZ11", ["AuroraLib.Compression.Nintendo/Nintendo/LZ11.cs"]),
     "Yaz0.cs": ("Yaz0", ["AuroraLib.Compression.Nintendo/Nintendo/Yaz0.cs"]),
@@ -158,20 +160,16 @@ def _surface(text, cls):
 ZERO_DEFAULTS = {"", "0", "default", "false", "null"}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree only exists in the build container")
 @pytest.mark.parametrize("key", sorted(REF_CLASSES))
 def test_shim_class_mirrors_the_reference_class(key):
     cls, ref_files = REF_CLASSES[key]
     shim_text = open(os.path.join(SHIM, key.split(":")[0])).read()
-    ref_text = "\n".join(open(os.path.join(REF, f), encoding="utf-8-sig").read() for f in ref_files)
     s_if, s_props, s_stat = _surface(shim_text, cls)
-    r_if, r_props, r_stat = set(), {}, {}
-    for f in ref_files:
-        i, p, st = _surface(open(os.path.join(REF, f), encoding="utf-8-sig").read(), cls)
-        r_if |= i; r_props.update(p)
-        for k, v in st.items():
-            r_stat.setdefault(k, set()).update(v)
-    assert ref_text
+    ref = json.load(open(REF_SURFACES))[key]
+    assert ref["class"] == cls and ref["files"] == ref_files and ref["interfaces"] and ref["statics"]
+    r_if = set(ref["interfaces"])
+    r_props = {k: tuple(v) for k, v in ref["properties"].items()}
+    r_stat = {k: {(ret, tuple(params)) for ret, params in v} for k, v in ref["statics"].items()}
     # interfaces: the shim class implements exactly what the class it replaces implements
     assert s_if == r_if, (cls, s_if, r_if)
     # every public settable property of the reference class exists with the same type and the same default

@@ -9,7 +9,7 @@ run() {
   ALZ_EXTRA_FLAGS="$1" bash auroralib/compression_amd/csrc/build.sh > /dev/null 2>&1
   echo "== flags: $1"
   for f in lz4_block snappy_raw; do
-    python bench.py --mode encode --format $f --quality 8 --steps 3 --warmup 1 --no-cpu-baseline --configs none --no-extras 2>/dev/null | python -c "
+    python bench.py --full --mode encode --format $f --quality 8 --steps 3 --warmup 1 --no-cpu-baseline --configs none --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg5 $f q8', d['ms_per_step'], 'ms', d['config']['parity_ok'])"
   done

@@ -7,7 +7,7 @@ run() {
   ALZ_EXTRA_FLAGS="$1" bash auroralib/compression_amd/csrc/build.sh > /dev/null 2>&1
   echo "== flags: $1"
   for f in lzss yaz0; do
-  python bench.py --mode encode --format $f --quality 0 --steps 5 --warmup 1 --no-cpu-baseline --configs none --no-extras 2>/dev/null | python -c "
+  python bench.py --full --mode encode --format $f --quality 0 --steps 5 --warmup 1 --no-cpu-baseline --configs none --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg5 $f q0', d['ms_per_step'], 'ms')"
   done

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 export TMPDIR=/tmp
 TAG=$1; CTRS=$2; shift; shift
 D=gpurun_out/pmc_$TAG; rm -rf $D; mkdir -p $D
-rocprofv3 --pmc $CTRS --output-format csv -d $D -- python3 bench.py --no-cpu-baseline --no-verify --no-extras --inflight 1 "$@" > $D/log.txt 2>&1
+rocprofv3 --pmc $CTRS --output-format csv -d $D -- python3 bench.py --full --no-cpu-baseline --no-verify --no-extras --inflight 1 "$@" > $D/log.txt 2>&1
 python3 - $TAG <<'PY'
 import csv,glob,sys,collections
 tag=sys.argv[1]

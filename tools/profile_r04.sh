@@ -36,7 +36,7 @@ cfg3_100000 lz4_block 100000 256
 LIST
 # the Test.bmp windows (bench.py --configs realistic: five formats), a 64-stream headline batch beside them
 D=gpurun_out/prof_r04_realistic; rm -rf $D; mkdir -p $D
-B="python3 bench.py --streams 64 --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-extras --configs realistic --inflight 1"
+B="python3 bench.py --full --streams 64 --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-extras --configs realistic --inflight 1"
 rocprofv3 --kernel-trace --output-format csv -d $D/stats -- $B > $D/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/fetch -- $B > $D/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/write -- $B > $D/write.log 2>&1

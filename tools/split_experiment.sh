@@ -10,7 +10,7 @@ trap 'patch -R -p1 < tools/variants/r06_split.patch > /dev/null; cp /tmp/libauro
 bash auroralib/compression_amd/csrc/build.sh > /dev/null 2>&1 || exit 1
 for v in 0 4 5; do
   echo "== kernel variant $v"
-  B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --configs none --inflight 1 --format lz4_block --kernel-variant $v"
+  B="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras --configs none --inflight 1 --format lz4_block --kernel-variant $v"
   timeout 300 $B 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('bench: value', d['value'], 'GiB/s  ms_per_step', d['ms_per_step'], ' parity', d['config'].get('parity_ok'), d['config'].get('verified_vs_oracle'))"
   D=gpurun_out/split_v$v; rm -rf $D; mkdir -p $D
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -- $B --no-verify > $D/stats.log 2>&1

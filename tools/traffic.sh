@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 TAG=$1; shift
 for c in FETCH_SIZE WRITE_SIZE; do
   D=gpurun_out/traffic_${TAG}_$c; rm -rf $D; mkdir -p $D
-  rocprofv3 --pmc $c --output-format csv -d $D -- python3 bench.py --no-cpu-baseline --no-verify --no-extras --inflight 1 "$@" > $D/log.txt 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $D -- python3 bench.py --full --no-cpu-baseline --no-verify --no-extras --inflight 1 "$@" > $D/log.txt 2>&1
 done
 python3 - $TAG <<'PY'
 import csv,glob,sys,collections
