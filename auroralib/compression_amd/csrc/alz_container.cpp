@@ -7,6 +7,7 @@
 // /root/reference/src).  A C# shim would keep (1) in managed code and P/Invoke only alz_decode/alz_encode_batch
 // (INTEGRATION.md); hosts without the managed library use these entry points instead.
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -158,13 +159,19 @@ const uint8_t kSnappyId[10] = { 0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 
 
 inline bool lz4_magic_defined(uint32_t v) { return v == 0x184C2102u || v == 0x184D2204u || (v >= 0x184D2A50u && v <= 0x184D2A5Fu); }   // LZ4.Frame.cs:50-70
 
+// Which branches of the LZ4 file decode ran, process-wide (alz_debug_container_counters): what a test asserts to show that its cases reached each of them.
+enum { CNT_BATCH_BLOCKS, CNT_SPLIT_PLANS, CNT_TIGHT_RETRIES, CNT_FALLBACK_BLOCKS, CNT_LINKED_BLOCKS, CNT_STORED_BLOCKS, CNT_COUNT };
+std::atomic<uint64_t> g_counters[CNT_COUNT];
+inline void count(int which, uint64_t n = 1) { g_counters[which].fetch_add(n, std::memory_order_relaxed); }
+
 struct DevBuf {   // device allocation released on every exit path
     alz_ctx* c; void* p;
     explicit DevBuf(alz_ctx* ctx) : c(ctx), p(nullptr) {}
     ~DevBuf() { if (p) alz_device_free(c, p); }
 };
 
-// Does any match of this LZ4 block point in front of the block's own output?  (A walk over the sequences: input only.)
+// Does any match of this LZ4 block point in front of the block's own output?  (A walk over the sequences: input only.)  Offset 0 is a
+// distance of 65 536 (E1): it reaches back while the block has produced less than that.
 static bool lz4_block_reaches_back(const uint8_t* b, uint32_t n) {
     uint64_t produced = 0; uint32_t p = 0;
     while (p < n) {
@@ -178,7 +185,7 @@ static bool lz4_block_reaches_back(const uint8_t* b, uint32_t n) {
         const uint32_t dist = b[p] | (b[p + 1] << 8); p += 2;
         uint64_t ml = tok & 15;
         if (ml == 15) { uint32_t x; do { if (p >= n) return false; x = b[p++]; ml += x; } while (x == 255); }
-        if (dist > produced) return true;
+        if ((dist == 0 ? 65536u : dist) > produced) return true;
         produced += ml + 4;
     }
     return false;
@@ -219,14 +226,19 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
         alz_plan_destroy(ctx, pl);
         return e;
     };
-    // blocks in order, each seeing `out - origin` bytes of history when `linked`
-    auto run_sequential = [&](const std::vector<Lz4Block>& bl, size_t first, size_t origin, bool linked) -> int {
+    // blocks in order, each seeing `out - origin` bytes of history when `linked`; `fallback`: the rest of a batch that did not hold
+    auto run_sequential = [&](const std::vector<Lz4Block>& bl, size_t first, size_t origin, bool linked, bool fallback) -> int {
         for (size_t i = first; i < bl.size() && st == ALZ_ST_OK; i++) {
-            if (bl[i].raw) {
-                if (out + bl[i].len > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
-                int e = alz_memcpy_h2d(ctx, (uint8_t*)d_dst.p + out, src + bl[i].off, bl[i].len); if (e != ALZ_OK) return e;
-                out += bl[i].len; continue;
+            if (fallback) count(CNT_FALLBACK_BLOCKS);
+            if (bl[i].raw) {                                                             // what fits, as the window writes it (win_clip)
+                const size_t n = out + bl[i].len > cap ? cap - out : bl[i].len;
+                if (n) { int e = alz_memcpy_h2d(ctx, (uint8_t*)d_dst.p + out, src + bl[i].off, n); if (e != ALZ_OK) return e; }
+                count(CNT_STORED_BLOCKS);
+                out += n;
+                if (n < bl[i].len) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
+                continue;
             }
+            if (linked) count(CNT_LINKED_BLOCKS);
             std::vector<alz_stream> ss(1); std::vector<alz_result> rs;
             memset(&ss[0], 0, sizeof(alz_stream));
             const size_t hist = linked ? out - origin : 0;
@@ -236,7 +248,10 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
             const uint32_t full = ss[0].dst_cap;
             if (!linked) ss[0].dst_cap = lz4_tight_cap(full, ss[0].src_len);
             int e = run(ss, rs); if (e != ALZ_OK) return e;
-            if (rs[0].status == ALZ_ST_OUTPUT_CAPACITY && ss[0].dst_cap < full) { ss[0].dst_cap = full; e = run(ss, rs); if (e != ALZ_OK) return e; }   // (a block that compressed more than 32 : 1)
+            if (rs[0].status == ALZ_ST_OUTPUT_CAPACITY && ss[0].dst_cap < full) {                                   // (a block that compressed more than 32 : 1)
+                count(CNT_TIGHT_RETRIES);
+                ss[0].dst_cap = full; e = run(ss, rs); if (e != ALZ_OK) return e;
+            }
             out += rs[0].dst_len;
             if (rs[0].status != ALZ_ST_OK) st = rs[0].status;
         }
@@ -245,7 +260,7 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
     // independent blocks: one batch, block k at origin + k * nominal; falls back to in-order decoding from the first
     // block that did not fill its nominal slot
     auto run_independent = [&](const std::vector<Lz4Block>& bl, uint32_t nominal) -> int {
-        if (bl.size() <= 1) return run_sequential(bl, 0, out, false);
+        if (bl.size() <= 1) return run_sequential(bl, 0, out, false, false);
         const size_t origin = out;
         std::vector<alz_stream> ss; std::vector<size_t> idx; std::vector<bool> tightened;
         for (size_t i = 0; i < bl.size(); i++) {
@@ -265,7 +280,9 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
         {
             std::vector<alz_stream> sa, sb; std::vector<size_t> ia, ib;
             for (size_t k = 0; k < ss.size(); k++) { if (lz4_long_block(ss[k])) { sa.push_back(ss[k]); ia.push_back(k); } else { sb.push_back(ss[k]); ib.push_back(k); } }
+            count(CNT_BATCH_BLOCKS, ss.size());
             if (!sa.empty() && !sb.empty() && sa.size() <= 32) {
+                count(CNT_SPLIT_PLANS);
                 std::vector<alz_result> ra, rb;
                 int e = run(sa, ra); if (e != ALZ_OK) return e;
                 e = run(sb, rb); if (e != ALZ_OK) return e;
@@ -279,15 +296,16 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
             uint32_t produced; int32_t bst = ALZ_ST_OK;
             if (bl[i].raw) {
                 produced = bl[i].len;
-                if (out != o || out + produced > cap) return run_sequential(bl, i, origin, false);
+                if (out != o || out + produced > cap) return run_sequential(bl, i, origin, false, true);
                 int e = alz_memcpy_h2d(ctx, (uint8_t*)d_dst.p + out, src + bl[i].off, produced); if (e != ALZ_OK) return e;
+                count(CNT_STORED_BLOCKS);
             } else {
                 produced = rs[k].dst_len; bst = rs[k].status;
                 const bool tight = tightened[k]; k++;
-                if (out != o) return run_sequential(bl, i, origin, false);
-                if (bst == ALZ_ST_OUTPUT_CAPACITY && tight) return run_sequential(bl, i, origin, false);             // it compressed better than 32 : 1: again, with all the room there is
+                if (out != o) return run_sequential(bl, i, origin, false, true);
+                if (bst == ALZ_ST_OUTPUT_CAPACITY && tight) return run_sequential(bl, i, origin, false, true);             // it compressed better than 32 : 1: again, with all the room there is
             }
-            if (bst == ALZ_ST_OUTPUT_CAPACITY && o + nominal <= cap) return run_sequential(bl, i, origin, false);   // the block is larger than nominal
+            if (bst == ALZ_ST_OUTPUT_CAPACITY && o + nominal <= cap) return run_sequential(bl, i, origin, false, true);   // the block is larger than nominal
             out = o + produced;
             if (bst != ALZ_ST_OK) { st = bst; return ALZ_OK; }
         }
@@ -329,18 +347,20 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
             if (pos + 1 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
             pos += 1;                                                                    // HeaderChecksum: read, not verified
             if (flg & 1) return ALZ_E_UNSUPPORTED;                                       // external dictionaries  LZ4.Frame.cs:113-114
-            std::vector<Lz4Block> bl; bool trunc = false;
+            // A block too large for the frame or with a wrong checksum ends the collection; it decides the outcome only if the blocks in
+            // front of it decode cleanly (the managed reader meets it after them).
+            std::vector<Lz4Block> bl; bool trunc = false; int fault = ALZ_OK;
             for (;;) {
                 if (pos + 4 > len) { trunc = true; break; }
                 const uint32_t bsz = le32(src + pos); pos += 4;
                 if (bsz == 0) break;                                                     // EndMark
                 const bool raw = (bsz & 0x80000000u) != 0; const uint32_t n = bsz & 0x7FFFFFFFu;
-                if (n > bmax) return ALZ_E_FORMAT;
+                if (n > bmax) { fault = ALZ_E_FORMAT; break; }
                 if (n > len - pos) { trunc = true; break; }
                 const size_t boff = pos; pos += n;
                 if (flg & 16) {                                                          // block checksum over the stored bytes
                     if (pos + 4 > len) { trunc = true; break; }
-                    if (le32(src + pos) != xxh32(src + boff, n, 0)) return ALZ_E_CHECKSUM;
+                    if (le32(src + pos) != xxh32(src + boff, n, 0)) { fault = ALZ_E_CHECKSUM; break; }
                     pos += 4;
                 }
                 bl.push_back(Lz4Block{ boff, n, raw });
@@ -352,8 +372,9 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
             // writes -- 16 MB in 64 KiB blocks: 256 blocks -- were decoded one launch after the other, each with the output so far as its history: 112 ms.
             bool indep = true;
             for (size_t i = 1; indep && i < bl.size(); i++) if (!bl[i].raw && lz4_block_reaches_back(src + bl[i].off, bl[i].len)) indep = false;
-            if (indep) rc = run_independent(bl, bmax); else rc = run_sequential(bl, 0, frame_start, true);
+            if (indep) rc = run_independent(bl, bmax); else rc = run_sequential(bl, 0, frame_start, true, false);
             if (rc != ALZ_OK) return rc;
+            if (st == ALZ_ST_OK && fault != ALZ_OK) return fault;
             if (st == ALZ_ST_OK && trunc) st = ALZ_ST_INPUT_TRUNCATED;
             if (st != ALZ_ST_OK) break;
             if ((flg & 8) && (uint64_t)(out - frame_start) != content) { st = ALZ_ST_OUTPUT_SIZE_MISMATCH; break; }   // LZ4.Frame.cs:152-155
@@ -443,14 +464,50 @@ inline uint32_t snappy_varint(const uint8_t* p, size_t len, size_t* used) {     
     return v;
 }
 
+// Snappy.Decompress  Formats/Common/Snappy.cs:39-69, chunk after chunk from `pos` with `out` bytes produced: the path of a file whose
+// chunk decodes to more than it declares (its last element runs past the size), which moves every later chunk.
+int snappy_in_order(alz_ctx* ctx, const uint8_t* src, size_t len, size_t pos, size_t out, uint8_t* dst, size_t cap, size_t* dst_len, size_t* src_used, int32_t* status) {
+    int32_t st = ALZ_ST_OK;
+    while (pos < len) {
+        if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
+        const uint32_t type = src[pos], cl = (uint32_t)src[pos + 1] | ((uint32_t)src[pos + 2] << 8) | ((uint32_t)src[pos + 3] << 16); pos += 4;
+        if (type == 0) {
+            if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
+            pos += 4;
+            alz_result r;
+            int rc = run_body(ctx, ALZ_FMT_SNAPPY_RAW, nullptr, src + pos, len - pos, 0, 0, 0, dst + out, out < cap ? cap - out : 0, &r);
+            if (rc != ALZ_OK) return rc;
+            out += r.dst_len;
+            if (r.status != ALZ_ST_OK) { st = r.status; break; }
+            if ((uint64_t)r.src_used + 4 != cl) return ALZ_E_FORMAT;                     // (as below: a body that does not end at the declared length)
+            pos += r.src_used;
+        } else if (type == 1) {
+            if (pos + 4 > len || cl < 4) { st = ALZ_ST_INPUT_TRUNCATED; break; }
+            pos += 4;
+            uint32_t n = cl - 4; if (n > len - pos) n = (uint32_t)(len - pos);
+            if (out + n > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
+            memcpy(dst + out, src + pos, n); out += n; pos += n;
+        } else {
+            if (type >= 0x02 && type <= 0x7F) return ALZ_E_FORMAT;
+            pos = (uint64_t)pos + cl > len ? len : pos + cl;
+        }
+    }
+    if (dst_len) *dst_len = out;
+    if (src_used) *src_used = pos;
+    if (status) *status = st;
+    return st == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM;
+}
+
 // Snappy.Decompress  Formats/Common/Snappy.cs:39-69.  Every compressed chunk declares its size, so all chunks of a file
 // decode as ONE GPU batch; CRCs are skipped as in the reference.  The managed decoder continues wherever a chunk's body
-// stopped; here a chunk whose body does not end at its declared length is refused (ALZ_E_FORMAT).
+// stopped; here a chunk whose body does not end at its declared length is refused (ALZ_E_FORMAT).  Whatever fails first in
+// file order decides, as in the managed decoder.
 int snappy_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* dst_len, size_t* src_used, int32_t* status) {
     if (len < 10 || memcmp(src, kSnappyId, 10)) return ALZ_E_FORMAT;
-    size_t pos = 10; uint64_t out = 0; int32_t st = ALZ_ST_OK;
-    std::vector<alz_stream> ss; std::vector<uint32_t> clen;
+    size_t pos = 10; uint64_t out = 0; int32_t st = ALZ_ST_OK; bool reserved = false;
+    std::vector<alz_stream> ss; std::vector<uint32_t> clen; std::vector<size_t> chdr;
     struct Raw { size_t off; uint32_t n; uint64_t out; }; std::vector<Raw> raws;
+    std::vector<bool> stored;                                                            // file order: stored (true) or compressed chunk
     while (pos < len) {
         if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
         const uint32_t type = src[pos], cl = (uint32_t)src[pos + 1] | ((uint32_t)src[pos + 2] << 8) | ((uint32_t)src[pos + 3] << 16); pos += 4;
@@ -461,33 +518,38 @@ int snappy_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t
             alz_stream s; memset(&s, 0, sizeof(s));
             s.src_off = body; s.src_len = clamp32(len - body); s.dst_off = out < cap ? out : cap;
             s.dst_cap = clamp32(out < cap ? (cap - out < size ? cap - out : size) : 0); s.format = ALZ_FMT_SNAPPY_RAW;
-            ss.push_back(s); clen.push_back(cl);
+            ss.push_back(s); clen.push_back(cl); chdr.push_back(pos - 4); stored.push_back(false);
             out += size; pos = (uint64_t)pos + cl > len ? len : pos + cl;
         } else if (type == 1) {
             if (pos + 4 > len || cl < 4) { st = ALZ_ST_INPUT_TRUNCATED; break; }
             uint32_t n = cl - 4; if (n > len - pos - 4) n = (uint32_t)(len - pos - 4);    // SubStream.CopyTo copies what is there
-            raws.push_back(Raw{ pos + 4, n, out }); out += n; pos += 4 + n;
+            raws.push_back(Raw{ pos + 4, n, out }); stored.push_back(true); out += n; pos += 4 + n;
         } else {
-            if (type >= 0x02 && type <= 0x7F) return ALZ_E_FORMAT;                       // reserved unskippable chunk  Snappy.cs:61-62
+            if (type >= 0x02 && type <= 0x7F) { reserved = true; break; }                 // reserved unskippable chunk  Snappy.cs:61-62: E_FORMAT once reached
             pos = (uint64_t)pos + cl > len ? len : pos + cl;
         }
     }
     std::vector<alz_result> rs(ss.size());
     if (!ss.empty()) { int rc = alz_decode_batch(ctx, nullptr, (uint32_t)ss.size(), src, len, ss.data(), dst, cap, rs.data()); if (rc != ALZ_OK) return rc; }
-    // first failing chunk in file order decides status and length
-    size_t produced = (size_t)(out < cap ? out : cap); int32_t fst = ALZ_ST_OK; uint64_t fail_at = ~0ull;
-    for (size_t i = 0; i < ss.size(); i++) {
+    // the first failing chunk in file order, compressed or stored, decides status and length; stored chunks are copied up to it
+    size_t produced = (size_t)(out < cap ? out : cap); int32_t fst = ALZ_ST_OK;
+    for (size_t c = 0, i = 0, k = 0; c < stored.size() && fst == ALZ_ST_OK; c++) {
+        if (stored[c]) {
+            const Raw& r = raws[k++];
+            if (r.out + r.n > cap) { fst = ALZ_ST_OUTPUT_CAPACITY; produced = (size_t)r.out; break; }
+            memcpy(dst + r.out, src + r.off, r.n);
+            continue;
+        }
         const uint32_t size = snappy_varint(src + ss[i].src_off, len - ss[i].src_off, nullptr);
         int32_t cs = rs[i].status;
+        if (cs == ALZ_ST_OUTPUT_CAPACITY && ss[i].dst_cap == size && ss[i].dst_off + (uint64_t)size < cap)     // it decodes to more than it declares
+            return snappy_in_order(ctx, src, len, chdr[i], (size_t)ss[i].dst_off, dst, cap, dst_len, src_used, status);
         if (cs == ALZ_ST_OK && rs[i].dst_len < size) cs = ALZ_ST_OUTPUT_CAPACITY;        // the declared size did not fit dst
         if (cs == ALZ_ST_OK && (uint64_t)rs[i].src_used + 4 != clen[i]) return ALZ_E_FORMAT;
-        if (cs != ALZ_ST_OK) { fst = cs; fail_at = ss[i].dst_off; produced = (size_t)(ss[i].dst_off + rs[i].dst_len); break; }
+        if (cs != ALZ_ST_OK) { fst = cs; produced = (size_t)(ss[i].dst_off + rs[i].dst_len); }
+        i++;
     }
-    for (const Raw& r : raws) {
-        if (r.out >= fail_at) break;
-        if (r.out + r.n > cap) { if (fst == ALZ_ST_OK || r.out < fail_at) { fst = ALZ_ST_OUTPUT_CAPACITY; produced = (size_t)r.out; } break; }
-        memcpy(dst + r.out, src + r.off, r.n);
-    }
+    if (fst == ALZ_ST_OK && reserved) return ALZ_E_FORMAT;
     if (fst == ALZ_ST_OK && st != ALZ_ST_OK) fst = st;
     if (dst_len) *dst_len = produced;
     if (src_used) *src_used = pos;
@@ -1243,6 +1305,15 @@ int alz_container_compress(alz_ctx* ctx, uint32_t container, const alz_container
     }
     if (dst_len) *dst_len = hdr + r.dst_len;
     return ALZ_OK;
+}
+
+/* not in the public header: the LZ4 file decode's branch counters, process-wide and never reset -- blocks decoded in an independent batch, split
+   (long + short) plan pairs, tight-capacity retries, blocks decoded in order after a batch fell back, blocks decoded in a linked frame, stored
+   blocks copied.  Writes the first min(n, 6) of them and returns 6. */
+int alz_debug_container_counters(uint64_t* out, int n) {
+    if (!out || n < 0) return ALZ_E_INVALID;
+    for (int i = 0; i < n && i < CNT_COUNT; i++) out[i] = g_counters[i].load(std::memory_order_relaxed);
+    return CNT_COUNT;
 }
 
 }  // extern "C"

@@ -110,6 +110,11 @@ class _Format:
                     return self.Decompress(data, hint)
                 except BufferError:
                     pass                                   # (a frame whose blocks decode to more than their nominal size: grow as for any other)
+                except MemoryError:
+                    pass                                   # (a hint the host or the device cannot back: the growing loop)
+                except AlzError as e:
+                    if e.code != A.E_NOMEM:
+                        raise
             cap = max(len(data) * 8, 1 << 16)
             while True:
                 try:
@@ -354,7 +359,7 @@ def _lz4_capacity_hint(data):
                 total += 0x800000; pos += 4 + bs
                 if pos < n and data[pos] == 0xFF:
                     break
-            return total + 64 if total else None
+            return _lz4_clamp_hint(total, n)
         while pos + 7 <= n and int.from_bytes(data[pos:pos + 4], "little") == 0x184D2204:
             flg, bd = data[pos + 4], data[pos + 5]
             bmax = {4: 0x10000, 5: 0x40000, 6: 0x100000, 7: 0x400000}.get((bd >> 4) & 7)
@@ -368,7 +373,16 @@ def _lz4_capacity_hint(data):
                 total += bmax
                 pos += (bsz & 0x7FFFFFFF) + (4 if flg & 16 else 0)
             pos += 4 if flg & 4 else 0
-        return total + 64 if total else None
+        return _lz4_clamp_hint(total, n)
+
+
+def _lz4_clamp_hint(total, n):
+        """No LZ4 input decodes to more than 255 bytes per byte (a match token followed by one length-extension byte after another), so the hint need not exceed
+        that: a 100 KB frame of 20 000 one-byte blocks at 4 MiB would otherwise ask for 78 GiB.  A hint of 2 GiB or more is not one (None)."""
+        if not total:
+            return None
+        total = min(total + 64, 255 * n + (1 << 16))
+        return total if total < (1 << 31) else None
 
 
 class LZ4Legacy(_Format):

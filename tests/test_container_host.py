@@ -251,3 +251,71 @@ def test_lz4_capacity_hint_of_the_wrapper(test_bmp):
     assert F._lz4_capacity_hint(b"") is None and F._lz4_capacity_hint(b"\x00" * 64) is None and F._lz4_capacity_hint(raw[:100]) is None
     blocks, expect = FC.lz4_linked_blocks(7, 5, 30000)
     assert F._lz4_capacity_hint(FC.lz4_frame(blocks, O.xxh32, flg=0x40 | 4 | 8 | 16, bd=0x40, content=expect)) == 5 * 0x10000 + 64
+
+
+# ---------------------------------------------------------------------------------------------- generated files (tests/framing_cases.py)
+_CT = {"lz4": A.C_LZ4_FRAME, "legacy": A.C_LZ4_LEGACY, "snappy": A.C_SNAPPY}
+
+
+@pytest.fixture(scope="module")
+def generated():
+    return FC.generated_cases(O.xxh32)
+
+
+def test_generated_files_oracle_equals_model(generated):
+    """The oracle's frame window, E1 (offset 0 = 65 536) and E2 (zeros in front of a window) against the generator's independent byte-wise model, on
+    every valid shape: block sizes at BD 4-7 and legacy, stored blocks, maximum-ratio blocks, linked frames, offset 0, flags, concatenation, Snappy."""
+    assert len(generated) >= 40
+    for case in generated:
+        out, st = O.container_decompress(_CT[case.container], case.data, cap=len(case.expect) + 64)
+        assert st == A.ST_OK, case
+        if out != case.expect:
+            i = next((k for k in range(min(len(out), len(case.expect))) if out[k] != case.expect[k]), min(len(out), len(case.expect)))
+            pytest.fail("%r: first differing byte %d of %d / %d" % (case, i, len(out), len(case.expect)))
+    # the shapes the issue lists are all there
+    labels = " ".join(c.label for c in generated)
+    for want in ("bd4", "bd5", "bd6", "bd7", "legacy", "stored first", "max-ratio 64K", "max-ratio 1M", "max-ratio 4M", "linked", "offset 0 at history 1000",
+                 "offset 0 at history 65536", "offset 0 at history 100000", "junk", "snappy csk", "snappy ksc", "snappy zeros"):
+        assert want in labels, want
+
+
+def test_model_reads_zeros_in_front_of_the_frame_and_65536_for_offset_0():
+    """The model itself, by hand: E1 and E2 at a frame's start."""
+    m = FC.Model()
+    m.lit(b"abc")
+    m.origin = 3
+    m.lit(b"xy")
+    m.match(4, 6)                                         # 2 bytes in front of the window: zeros, then x y, then the period repeats
+    assert bytes(m.out) == b"abcxy" + bytes([0, 0]) + b"xy" + bytes([0, 0])
+    m.lit(bytes(65536 - len(m.out) + 3))
+    m.match(0, 3)                                         # offset 0: distance 65 536 = the window's first bytes
+    assert bytes(m.out[-3:]) == b"xy\0"
+
+
+def test_mutants_are_seeded_and_structural(generated):
+    a = [m.data for m in FC.mutants(generated[0], 99)]
+    assert a == [m.data for m in FC.mutants(generated[0], 99)] and len(set(a)) == len(a) > 5
+    labels = " ".join(m.label for c in generated for m in FC.mutants(c, 5, per_case=None))
+    for want in ("size@", "lsize@", "truncated", "flip body", "flip bsum", "flip csum", "EndMark removed", "EndMark doubled", "content size", "chunk length",
+                 "declared size"):
+        assert want in labels, want
+
+
+def test_lz4_capacity_hint_bounded(generated):
+    """_lz4_capacity_hint: never above 255 output bytes per input byte plus 64 KiB (no LZ4 input decodes to more), None or at least the true size for every
+    valid file whose blocks stay within their maximum -- the maximum-ratio blocks included, so the clamp is not too tight."""
+    for case in generated:
+        if case.container == "snappy":
+            continue
+        h = F._lz4_capacity_hint(case.data)
+        assert h is None or h <= 255 * len(case.data) + (1 << 16), case
+        if "larger than its maximum" not in case.label:
+            assert h is None or h >= len(case.expect), (case, h, len(case.expect))
+    tiny = FC.many_tiny_blocks(O.xxh32)
+    assert len(tiny.data) < 110000
+    h = F._lz4_capacity_hint(tiny.data)
+    assert h is not None and len(tiny.expect) <= h <= 255 * len(tiny.data) + (1 << 16)       # 20 000 x 4 MiB before the clamp
+    # a 4 MiB block of one length-extension byte after another (the maximum ratio), alone in its frame
+    rng, m, f = FC.random.Random(1), FC.Model(), FC.File()
+    FC.lz4_frame_into(f, m, rng, O.xxh32, 7, [("maxratio", 0x400000, "")])
+    assert len(f.b) < 0x400000 // 250 and len(m.out) <= F._lz4_capacity_hint(bytes(f.b))
