@@ -2643,6 +2643,83 @@ __global__ __launch_bounds__(64) void enc_compose_kernel(const u32* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the host side: which way a format goes, what a launch carries
+#ifndef ALZ_SPEC_LONG11
+#define ALZ_SPEC_LONG11 1     /* LZ11 / LZ40 (matches of up to 16 KiB and more) on the speculative walk as well -- 0: synchronisation points with a 16 KiB look-back, up to 256 buffers.  64 KiB windows of
+                                 Test.bmp as LZ11, ms per call, 0 / 1: quality 8 16 buffers 0.44 / 0.33, 64 1.06 / 0.70, 256 2.77 / 1.82, 512 4.46 (one wavefront per buffer) / 3.13, 1 024 6.92 / 5.93; quality 0 at 256
+                                 1.56 / 0.61; quality 12 at 64 / 256: 6.1 / 2.0, 22.9 / 3.8 (the stretches with capped entries were walked serially) */
+#endif
+// the formats whose segments are walked speculatively (alz_encode_seg_seq.h): no longest match that a look-back could be bounded by
+#ifndef ALZ_SPEC_FLAG
+#define ALZ_SPEC_FLAG 0       /* the flag-bit formats with matches of at most 273 bytes on it too: measured, not taken -- 16 / 256 / 1 024 x 64 KiB as Yaz0 at quality 8 0.19 / 1.74 / 5.96 ms with the synchronisation
+                                 points against 0.32 / 1.81 / 5.83 (every segment is a step of its buffer's serial fix-up: 64 steps of ~2 us for a 64 KiB buffer, which the synchronisation points do not have),
+                                 quality 12 at 64 buffers 2.66 against 9.65 */
+#endif
+// ONE line per format says which way its streams go; everything on the host that asks "which formats?" reads it here.
+//   family: the parse + emit kernel of a full batch -- flag bits (enc_parse_emit_kernel), LZ4 / Snappy sequences (enc_parse_seq_kernel), PRS (enc_emit_prs_kernel), LZO
+//           (enc_parse_lzo_kernel), or an emitter of its own behind the roles walk and its start mask (enc_emit_kernel)
+//   scan: streams whose parse visits few positions may go without kernels A and B (enc_scan_select_kernel); tail: the bytes at a stream's end the finder is not given (LZ4.cs:208)
+//   seg: a batch of few buffers is cut into segments (alz_encode_seg.h) walked from synchronisation points or speculatively (alz_encode_seg_seq.h), or is not;
+//        long_match: matches of up to 16 KiB and more (what the synchronisation points then look back over)
+enum EncFamily { ENC_FLAG, ENC_SEQ, ENC_PRS, ENC_LZO, ENC_SERIAL };
+enum EncSegWalk { ENC_SEG_NONE, ENC_SEG_SYNC, ENC_SEG_SPEC, ENC_SEG_FLAG = ALZ_SPEC_FLAG ? ENC_SEG_SPEC : ENC_SEG_SYNC, ENC_SEG_LONG = ALZ_SPEC_LONG11 ? ENC_SEG_SPEC : ENC_SEG_SYNC };
+struct EncPath { bool known; EncFamily family; bool scan; EncSegWalk seg; int tail; bool long_match; };
+#define ALZ_ENC_PATHS(X) \
+    X(ALZ_FMT_LZSS,       ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_LZ10,       ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_LZ11,       ENC_FLAG,   true,  ENC_SEG_LONG, 0, true)  \
+    X(ALZ_FMT_LZ40,       ENC_FLAG,   true,  ENC_SEG_LONG, 0, true)  \
+    X(ALZ_FMT_YAZ0,       ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_YAY0,       ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_MIO0,       ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_CLZ0,       ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_BLZ,        ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_LZHUDSON,   ENC_FLAG,   true,  ENC_SEG_FLAG, 0, false) \
+    X(ALZ_FMT_LZ4_BLOCK,  ENC_SEQ,    true,  ENC_SEG_SPEC, 5, false) \
+    X(ALZ_FMT_SNAPPY_RAW, ENC_SEQ,    true,  ENC_SEG_SYNC, 0, false) \
+    X(ALZ_FMT_PRS_BE,     ENC_PRS,    false, ENC_SEG_SYNC, 0, false) \
+    X(ALZ_FMT_PRS_LE,     ENC_PRS,    false, ENC_SEG_SYNC, 0, false) \
+    X(ALZ_FMT_LZO,        ENC_LZO,    false, ENC_SEG_SPEC, 0, false) \
+    X(ALZ_FMT_SMSR00,     ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_FASTLZ,     ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_HIG,        ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_LZSHREK,    ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_WFLZ,       ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_WFLZ_BE,    ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_REFPACK,    ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_LZ02,       ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_CNS,        ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_FMT_CNX2,       ENC_SERIAL, false, ENC_SEG_NONE, 0, false)
+constexpr EncPath enc_path(int fmt) {
+    switch (fmt) {
+#define ALZ_ENC_ROW(F, FAMILY, SCAN, SEG, TAIL, LONG) case F: return EncPath{ true, FAMILY, SCAN, SEG, TAIL, LONG };
+    ALZ_ENC_PATHS(ALZ_ENC_ROW)
+#undef ALZ_ENC_ROW
+    default: return EncPath{ false, ENC_SERIAL, false, ENC_SEG_NONE, 0, false };
+    }
+}
+// f(std::integral_constant<int, fmt>) for the runtime `fmt`; false: no such format
+template <class Fn>
+static bool with_format(int fmt, Fn&& f) {
+    switch (fmt) {
+#define ALZ_ENC_ROW(F, ...) case F: f(std::integral_constant<int, F>()); return true;
+    ALZ_ENC_PATHS(ALZ_ENC_ROW)
+#undef ALZ_ENC_ROW
+    default: return false;
+    }
+}
+
+// What every launcher of one alz_launch_encode gets: the launch's arrays under their names (filled once, the casts made there); the kernels take them one by one.
+struct EncLaunch {
+    hipStream_t s;
+    const u8* src; u8* dst;
+    const alz_stream* streams; const u32* index; u32 count, max_len;
+    int* prev4; int* prevm; mentry* match; const u64* pos_off;           // prev4: the links kernel B and the parse read (kernel A's, or the narrowed ones)
+    u8* side; u64* mask; alz_result* results; alz_encode_aux* aux;
+    EncGeom g; int tail;
+    struct { void* mem; u32 seg_len, kmax; } seg;                      // mem != nullptr: the launch is on the segmented path
+};
+
 #include "alz_encode_seg.h"
 
 int isqrt_floor(int v) { int r = 0; while ((r + 1) * (r + 1) <= v) r++; return r; }
@@ -3539,44 +3616,48 @@ __global__ __launch_bounds__(64) void enc_parse_lzo_kernel(const u8* __restrict_
 }
 
 template <int FMT>
-static void launch_emit(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, const mentry* match,
-                        const u64* pos_off, const int* prev4, const int* prevm, u8* side, alz_result* results, alz_encode_aux* aux, const EncGeom& g,
-                        u64* mask = nullptr) {
+static void launch_emit(const EncLaunch& L) {
     // one stream per wavefront (lane 0 parses and emits; 64 streams per wavefront were the union of 64 divergent token paths), the
     // parse from the roles walk's start mask
-    const int tail = FMT == ALZ_FMT_LZ4_BLOCK ? 5 : 0;
-    if (mask) hipLaunchKernelGGL((enc_roles_kernel<false>), dim3(count), dim3(64), 0, s, src, streams, index, count, (mentry*)match, pos_off, prev4, prevm, mask, g, tail, (const u32*)nullptr, 0u);
-    hipLaunchKernelGGL((enc_emit_kernel<FMT>), dim3(count), dim3(64), 0, s, src, dst, streams, index, count, match, pos_off, side, results, aux, g, 1u,
-                       (const u64*)mask);
+    const dim3 grid(L.count), wave(64);
+    if (L.mask) hipLaunchKernelGGL((enc_roles_kernel<false>), grid, wave, 0, L.s, L.src, L.streams, L.index, L.count, L.match, L.pos_off, L.prev4, L.prevm, L.mask, L.g, L.tail, nullptr, 0u);
+    hipLaunchKernelGGL((enc_emit_kernel<FMT>), grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.side, L.results, L.aux, L.g, 1u, L.mask);
 }
 
 // one candidate per position and a format whose parse and emit are one kernel: the search is in that kernel too (no kernel B, no match array)
 static bool searches_in_the_parse(int fmt, const EncGeom& g) {
-    const bool par = fmt == ALZ_FMT_LZSS || fmt == ALZ_FMT_LZ10 || fmt == ALZ_FMT_LZ11 || fmt == ALZ_FMT_LZ40 || fmt == ALZ_FMT_YAZ0 || fmt == ALZ_FMT_YAY0 ||
-                     fmt == ALZ_FMT_MIO0 || fmt == ALZ_FMT_CLZ0 || fmt == ALZ_FMT_BLZ || fmt == ALZ_FMT_LZHUDSON ||
-                     fmt == ALZ_FMT_LZ4_BLOCK || fmt == ALZ_FMT_SNAPPY_RAW ||                        // (enc_parse_seq_kernel)
-                     fmt == ALZ_FMT_PRS_BE || fmt == ALZ_FMT_PRS_LE ||                               // (enc_emit_prs_kernel)
-                     fmt == ALZ_FMT_LZO;                                                             // (enc_parse_lzo_kernel)
-    return par && g.max_chain == 1 && g.nprops <= 1 && !g.use_min_table && g.link16;
+    const EncPath path = enc_path(fmt);
+    return path.known && path.family != ENC_SERIAL && g.max_chain == 1 && g.nprops <= 1 && !g.use_min_table && g.link16;
 }
 
 // 1: the format's emitter runs behind enc_roles_kernel and reads its start mask (the formats without a parallel emitter); the others walk inside their emitter
-int alz_encode_format_needs_mask(int fmt) {
-    switch (fmt) {
-    case ALZ_FMT_SMSR00: case ALZ_FMT_FASTLZ: case ALZ_FMT_HIG: case ALZ_FMT_LZSHREK: case ALZ_FMT_WFLZ: case ALZ_FMT_WFLZ_BE: case ALZ_FMT_REFPACK:
-    case ALZ_FMT_LZ02: case ALZ_FMT_CNS: case ALZ_FMT_CNX2: return 1;
-    default: return 0;
-    }
-}
+int alz_encode_format_needs_mask(int fmt) { const EncPath path = enc_path(fmt); return path.known && path.family == ENC_SERIAL ? 1 : 0; }
 
 int alz_encode_geom_needs_match(int fmt, const void* geom) { EncGeom g; memcpy(&g, geom, sizeof(g)); return searches_in_the_parse(fmt, g) ? 0 : 1; }
 
+// the parse + emit kernel of a full batch, by family; IN_PARSE: it searches too (searches_in_the_parse)
+template <int FMT, bool IN_PARSE>
+static void launch_parse_emit(const EncLaunch& L) {
+    constexpr EncFamily fam = enc_path(FMT).family;
+    const dim3 grid(L.count), wave(64);
+    if constexpr (fam == ENC_FLAG) hipLaunchKernelGGL((enc_parse_emit_kernel<FMT, IN_PARSE>), grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.prev4, L.prevm, L.side, L.results, L.aux, L.g);
+    if constexpr (fam == ENC_SEQ) hipLaunchKernelGGL((enc_parse_seq_kernel<FMT, IN_PARSE>), grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.prev4, L.prevm, L.results, L.aux, L.g);
+    if constexpr (fam == ENC_PRS) hipLaunchKernelGGL((enc_emit_prs_kernel<FMT == ALZ_FMT_PRS_BE, IN_PARSE>), grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.results, L.aux, L.prev4, L.prevm, L.g);
+    if constexpr (fam == ENC_LZO) hipLaunchKernelGGL((enc_parse_lzo_kernel<IN_PARSE>), grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.results, L.aux, L.prev4, L.prevm, L.g);
+}
+
+// parse + emit of a launch: the family's segmented launcher (alz_encode_seg.h, alz_encode_seg_seq.h), its one kernel, or the roles walk and the format's own emitter
 template <int FMT>
-static void launch_emit_par(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, mentry* match,
-                            const u64* pos_off, const int* prev4, const int* prevm, u64* mask, u8* side, alz_result* results, alz_encode_aux* aux, const EncGeom& g) {
-    (void)mask;
-    if (searches_in_the_parse(FMT, g)) hipLaunchKernelGGL((enc_parse_emit_kernel<FMT, true>), dim3(count), dim3(64), 0, s, src, dst, streams, index, count, match, pos_off, prev4, prevm, side, results, aux, g);
-    else hipLaunchKernelGGL((enc_parse_emit_kernel<FMT, false>), dim3(count), dim3(64), 0, s, src, dst, streams, index, count, match, pos_off, prev4, prevm, side, results, aux, g);
+static void launch_emit_any(const EncLaunch& L) {
+    constexpr EncFamily fam = enc_path(FMT).family;
+    if constexpr (fam == ENC_SERIAL) launch_emit<FMT>(L);
+    else if (L.seg.mem) {
+        if constexpr (fam == ENC_FLAG) launch_emit_seg_flag<FMT>(L);
+        else if constexpr (fam == ENC_PRS) launch_emit_seg_prs<FMT == ALZ_FMT_PRS_BE>(L);
+        else launch_emit_seg_seq<FMT>(L);
+    }
+    else if (searches_in_the_parse(FMT, L.g)) launch_parse_emit<FMT, true>(L);
+    else launch_parse_emit<FMT, false>(L);
 }
 
 // one pass over the stream whatever the hash width: formats whose matches reach back at most 8 KiB (enc_prev_cu_kernel<2, true>)
@@ -3843,36 +3924,33 @@ __global__ __launch_bounds__(256) void enc_narrow_lds_kernel(const u8* __restric
     }
 }
 
+// kernel A for the streams of `index` at the geometry `g` (the finder's own, or its 15-bit form in front of a narrowing), the links into `links` (and L.prevm)
+static hipError_t launch_prev(const EncLaunch& L, const EncGeom& g, const u32* index, int* links, bool split_passes = false, bool no_win = false) {
+    if (g.hash_bits < 15 || g.hash_bits > 20) return hipErrorInvalidValue;
+    const bool win = uses_win_prev(g) && !no_win, one = !win && g.hash_bits == 15 && !g.use_min_table;     // one pass with the tag / link rings; one pass at the finder's own 15 bits; else passes:
+    const u32 passes = (1u << (g.hash_bits - 15)) + (g.use_min_table ? 2u : 0u);       // (as the kernel counts them)
+    // (a workgroup per (stream, pass) where a workgroup per stream leaves CUs idle: 16 x 64 KiB as raw Snappy at quality 8 -- 16 passes -- 383 -> 32 us of the
+    // call's 560; from 256 streams on the two arrangements are the same work on the same CUs)
+    const bool split = !win && !one && (split_passes || L.count < 256u);
+    hipLaunchKernelGGL((win ? enc_prev_cu_kernel<2, true> : one ? enc_prev_cu_kernel<2, false> : enc_prev_cu_kernel<3, false>), dim3(L.count, split ? passes : 1u), dim3(1024), 0,
+                       L.s, L.src, L.streams, index, L.count, links, L.prevm, L.pos_off, g, L.tail);
+    return hipSuccess;
+}
+
 // kernel A over segments (alz_encode_seg.h): `aseg` = the scratch behind the launch's segment records, 0 = one workgroup per buffer
 struct AsegPlan { void* mem; u32 SA, ka, W, stride; };
-static hipError_t launch_prev(hipStream_t stream, const u8* src, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count,
-                              int* d_prev4, int* d_prevm, const uint64_t* d_pos_off, const EncGeom& g, int tail, bool split_passes, bool no_win);
-static hipError_t launch_prev_aseg(hipStream_t stream, const u8* src, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, uint32_t max_len,
-                                   int* d_prev4, const uint64_t* d_pos_off, const EncGeom& g15, const AsegPlan& a, int tail) {
-    const size_t V = (size_t)count * a.ka;
+static hipError_t launch_prev_aseg(const EncLaunch& L, const EncGeom& g15, const u32* index, const AsegPlan& a) {
+    const size_t V = (size_t)L.count * a.ka;
     u8* base = (u8*)a.mem;
     alz_stream* vs = (alz_stream*)base; base += V * sizeof(alz_stream);
     u64* vpos = (u64*)base; base += V * sizeof(u64);
     u32* vindex = (u32*)base; base += ((V * sizeof(u32)) + 63u) & ~(size_t)63u;
     int* seg4 = (int*)base;
-    hipLaunchKernelGGL(enc_aseg_setup_kernel, dim3((u32)((V + 255u) / 256u)), dim3(256), 0, stream, d_streams, d_index, count, vs, vindex, vpos, a.ka, a.SA, a.W, a.stride, tail);
-    const hipError_t e = launch_prev(stream, src, vs, vindex, (u32)V, seg4, nullptr, vpos, g15, 0, false, true);
+    hipLaunchKernelGGL(enc_aseg_setup_kernel, dim3((u32)((V + 255u) / 256u)), dim3(256), 0, L.s, L.streams, index, L.count, vs, vindex, vpos, a.ka, a.SA, a.W, a.stride, L.tail);
+    EncLaunch v = L; v.streams = vs; v.count = (u32)V; v.prevm = nullptr; v.pos_off = vpos; v.tail = 0;      // the segments as streams of their own
+    const hipError_t e = launch_prev(v, g15, vindex, seg4, false, true);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(enc_aseg_gather_kernel, dim3((max_len + 255u) / 256u, count), dim3(256), 0, stream, d_streams, d_index, (const int*)seg4, d_prev4, d_pos_off, a.ka, a.SA, a.W, a.stride, tail);
-    return hipSuccess;
-}
-static hipError_t launch_prev(hipStream_t stream, const u8* src, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count,
-                              int* d_prev4, int* d_prevm, const uint64_t* d_pos_off, const EncGeom& g, int tail, bool split_passes = false, bool no_win = false) {
-    if (g.hash_bits < 15 || g.hash_bits > 20) return hipErrorInvalidValue;
-    if (uses_win_prev(g) && !no_win) hipLaunchKernelGGL((enc_prev_cu_kernel<2, true>), dim3(count), dim3(1024), 0, stream, src, d_streams, d_index, count, d_prev4, d_prevm, d_pos_off, g, tail);
-    else if (g.hash_bits == 15 && !g.use_min_table) hipLaunchKernelGGL((enc_prev_cu_kernel<2, false>), dim3(count), dim3(1024), 0, stream, src, d_streams, d_index, count, d_prev4, d_prevm, d_pos_off, g, tail);
-    else {
-        const u32 passes = (1u << (g.hash_bits - 15)) + (g.use_min_table ? 2u : 0u);       // (as the kernel counts them)
-        // (a workgroup per (stream, pass) where a workgroup per stream leaves CUs idle: 16 x 64 KiB as raw Snappy at quality 8 -- 16 passes -- 383 -> 32 us of the
-        // call's 560; from 256 streams on the two arrangements are the same work on the same CUs)
-        const bool split = split_passes || count < 256u;
-        hipLaunchKernelGGL((enc_prev_cu_kernel<3, false>), dim3(count, split ? passes : 1u), dim3(1024), 0, stream, src, d_streams, d_index, count, d_prev4, d_prevm, d_pos_off, g, tail);
-    }
+    hipLaunchKernelGGL(enc_aseg_gather_kernel, dim3((L.max_len + 255u) / 256u, L.count), dim3(256), 0, L.s, L.streams, index, seg4, L.prev4, L.pos_off, a.ka, a.SA, a.W, a.stride, L.tail);
     return hipSuccess;
 }
 
@@ -3890,11 +3968,16 @@ static int choose_b_cap(const EncGeom& g) {
     return g.max_len > cap ? cap : ALZ_LEN_CAP;
 }
 
-// kernel B over `count` streams; `wg_cap`: workgroups per stream of the one-position-per-lane form (32 in a batch; a lone stream takes
+// one form of kernel B: they all take the launch's arrays in this order, the two-phase ones two words more
+template <class Kernel, class... More>
+static void launch_b(Kernel kernel, dim3 grid, dim3 block, const EncLaunch& L, More... more) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, L.s, L.src, L.streams, L.index, L.prev4, L.prevm, L.match, L.pos_off, L.g, L.tail, more...);
+}
+
+// kernel B over the launch's streams; `wg_cap`: workgroups per stream of the one-position-per-lane form (32 in a batch; a lone stream takes
 // as many as it has blocks of 256 positions)
-static void launch_match(hipStream_t stream, const u8* src, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, uint32_t max_len,
-                         const int* d_prev4, const int* d_prevm, void* d_match, const uint64_t* d_pos_off, const EncGeom& g_in, int tail, u32 wg_cap, bool dense_ok = true, u32* d_sel = nullptr, u32 sel_pitch = 0) {
-    const EncGeom& g = g_in;
+static void launch_match(const EncLaunch& L, u32 wg_cap, bool dense_ok = true, u32* d_sel = nullptr, u32 sel_pitch = 0) {
+    const EncGeom& g = L.g; const u32 count = L.count, max_len = L.max_len;
     u32 bx = (max_len + 255) / 256; if (bx == 0) bx = 1; if (bx > 4096) bx = 4096;
     if (bx > wg_cap) bx = wg_cap;
     // (workgroups per stream, each with one contiguous range: 32 -- 8 Ki positions of a 256 KiB stream, 4 KiB of history in front of them fetched
@@ -3911,47 +3994,144 @@ static void launch_match(hipStream_t stream, const u8* src, const alz_stream* d_
         // (per stream: the two-phase kernel or the one-position-per-lane one -- enc_probe_kernel; both are launched, each leaves the other's streams alone)
         const u32* sel = nullptr;
         if (d_sel && g.link16 && g.nprops <= 1) {
-            const u32 thr = ALZ_PROBE_THRESH16;
             u32* list = d_sel + sel_pitch;                          // [0]: how many streams, then their ids
-            (void)hipMemsetAsync(list, 0, 4, stream);
-            hipLaunchKernelGGL((enc_probe_kernel<true>), dim3(count), dim3(64), 0, stream, src, d_streams, d_index, d_prev4, d_pos_off, g, tail, d_sel, list, thr);
+            (void)hipMemsetAsync(list, 0, 4, L.s);
+            hipLaunchKernelGGL((enc_probe_kernel<true>), dim3(count), dim3(64), 0, L.s, L.src, L.streams, L.index, L.prev4, L.pos_off, g, L.tail, d_sel, list, ALZ_PROBE_THRESH16);
             sel = d_sel;
-            const u32 gy = count < 512u ? count : 512u;
+            const dim3 gl(bx, count < 512u ? count : 512u), wg(256);
             // (lanes that take the next position when their walk ends -- enc_match_dyn_kernel -- where walks are long or compares short; with
             // long matches AND walks of 6-32 candidates the lanes' compare loops fall out of step and every one of them runs for the whole
             // wavefront: 1 024 windows at quality 8 as Yaz0 40 -> 47 ms, as LZ4 blocks 56 -> 63, but as LZSS 17.1 -> 14.1, and at quality 12
             // Yaz0 139 -> 125, LZ11 ~160 -> 92, LZSS 40 -> 26)
             const bool dynk = g.max_len <= 32 || g.max_chain >= 64;
-            if (dynk) {
-                if (g.use_min_table) hipLaunchKernelGGL((enc_match_dyn_kernel<true>), dim3(bx, gy), dim3(256), 0, stream, src, d_streams, d_index, d_prev4, d_prevm, (mentry*)d_match, d_pos_off, g, tail, list);
-                else hipLaunchKernelGGL((enc_match_dyn_kernel<false>), dim3(bx, gy), dim3(256), 0, stream, src, d_streams, d_index, d_prev4, d_prevm, (mentry*)d_match, d_pos_off, g, tail, list);
-            }
-            else if (g.use_min_table) hipLaunchKernelGGL((enc_match_kernel<true, true, true>), dim3(bx, gy), dim3(256), 0, stream, src, d_streams, d_index, d_prev4, d_prevm, (mentry*)d_match, d_pos_off, g, tail, list);
-            else hipLaunchKernelGGL((enc_match_kernel<false, true, true>), dim3(bx, gy), dim3(256), 0, stream, src, d_streams, d_index, d_prev4, d_prevm, (mentry*)d_match, d_pos_off, g, tail, list);
+            if (g.use_min_table) launch_b(dynk ? enc_match_dyn_kernel<true> : enc_match_kernel<true, true, true>, gl, wg, L, list);
+            else launch_b(dynk ? enc_match_dyn_kernel<false> : enc_match_kernel<false, true, true>, gl, wg, L, list);
         }
-#define ALZ_LB(K, grid, block) hipLaunchKernelGGL(K, grid, block, 0, stream, src, d_streams, d_index, d_prev4, d_prevm, (mentry*)d_match, d_pos_off, g, tail, xlog, sel)
-        const dim3 gd(bd, count);
-        if (dyn) {
-            if (g.use_min_table) { if (g.link16) ALZ_LB((enc_match_dense_kernel<true, true, 256, true>), gd, dim3(64)); else ALZ_LB((enc_match_dense_kernel<true, true, 256, false>), gd, dim3(64)); }
-            else { if (g.link16) ALZ_LB((enc_match_dense_kernel<false, true, 256, true>), gd, dim3(64)); else ALZ_LB((enc_match_dense_kernel<false, true, 256, false>), gd, dim3(64)); }
-        } else {
-            if (g.use_min_table) { if (g.link16) ALZ_LB((enc_match_dense_kernel<true, false, 64, true>), gd, dim3(64)); else ALZ_LB((enc_match_dense_kernel<true, false, 64, false>), gd, dim3(64)); }
-            else { if (g.link16) ALZ_LB((enc_match_dense_kernel<false, false, 64, true>), gd, dim3(64)); else ALZ_LB((enc_match_dense_kernel<false, false, 64, false>), gd, dim3(64)); }
-        }
-#undef ALZ_LB
+        static constexpr decltype(&enc_match_dense_kernel<true, true, 256, true>) dense[2][2][2] = {                   // [dyn][min-length table][16-bit links]
+            { { enc_match_dense_kernel<false, false, 64, false>, enc_match_dense_kernel<false, false, 64, true> }, { enc_match_dense_kernel<true, false, 64, false>, enc_match_dense_kernel<true, false, 64, true> } },
+            { { enc_match_dense_kernel<false, true, 256, false>, enc_match_dense_kernel<false, true, 256, true> }, { enc_match_dense_kernel<true, true, 256, false>, enc_match_dense_kernel<true, true, 256, true> } } };
+        launch_b(dense[dyn][g.use_min_table != 0][g.link16 != 0], dim3(bd, count), dim3(64), L, xlog, sel);
         return;
     }
-#define ALZ_LB(K, grid, block) hipLaunchKernelGGL(K, grid, block, 0, stream, src, d_streams, d_index, d_prev4, d_prevm, (mentry*)d_match, d_pos_off, g, tail)
+    const dim3 gb(bx, count), wg(256);
     if (!dense_ok && g.max_chain >= 3 && g.max_len <= 32 && g.link16 && g.nprops <= 1) {   // (the whole-GPU path of ONE stream; short compares only: see above)
-        if (g.use_min_table) ALZ_LB((enc_match_dyn_kernel<true>), dim3(bx, count), dim3(256)); else ALZ_LB((enc_match_dyn_kernel<false>), dim3(bx, count), dim3(256));
+        if (g.use_min_table) launch_b(enc_match_dyn_kernel<true>, gb, wg, L, nullptr); else launch_b(enc_match_dyn_kernel<false>, gb, wg, L, nullptr);
         return;
     }
     // (PRUNE in match_search_b: a candidate that cannot win is not measured -- with 16-bit links, i.e. every finder but RefPack's and FastLZ level 2's)
     // (not with one candidate per position -- quality 0 --: nothing to prune there, and the test costs the synthetic LZ4 batch 5 %: 58.2 -> 61.1 ms)
     const bool prune = g.link16 && g.max_chain > 1;
-    if (g.use_min_table) { if (prune) ALZ_LB((enc_match_kernel<true, true, true>), dim3(bx, count), dim3(256)); else if (g.link16) ALZ_LB((enc_match_kernel<true, true>), dim3(bx, count), dim3(256)); else ALZ_LB((enc_match_kernel<true, false>), dim3(bx, count), dim3(256)); }
-    else { if (prune) ALZ_LB((enc_match_kernel<false, true, true>), dim3(bx, count), dim3(256)); else if (g.link16) ALZ_LB((enc_match_kernel<false, true>), dim3(bx, count), dim3(256)); else ALZ_LB((enc_match_kernel<false, false>), dim3(bx, count), dim3(256)); }
-#undef ALZ_LB
+    if (g.use_min_table) { if (prune) launch_b(enc_match_kernel<true, true, true>, gb, wg, L, nullptr); else if (g.link16) launch_b(enc_match_kernel<true, true>, gb, wg, L, nullptr); else launch_b(enc_match_kernel<true, false>, gb, wg, L, nullptr); }
+    else { if (prune) launch_b(enc_match_kernel<false, true, true>, gb, wg, L, nullptr); else if (g.link16) launch_b(enc_match_kernel<false, true>, gb, wg, L, nullptr); else launch_b(enc_match_kernel<false, false>, gb, wg, L, nullptr); }
+}
+
+// ---- the steps of alz_launch_encode.  The cap of kernel B's compares for this launch:
+// (the segmented path of a small batch, alz_encode_seg.h: no cap -- its longest match is at most 2 040 bytes, kernel B has the GPU to itself, and
+// every capped position the roles walk stands on costs that ONE wavefront two exact searches: 16 x 64 KiB of Test.bmp as Yaz0 at quality 8 1.17 ms of walk)
+// (LZ4 blocks and LZO keep the cap: their segments are walked all at once -- alz_encode_seg_seq.h, enc_spec_walk_kernel --, so the exact searches of capped cursors run side by side,
+// while no cap means every position of a flat stretch compared over 2 040 bytes: 256 x 64 KiB of Test.bmp at quality 8, kernel B 1.70 ms of the call's 3.37)
+#ifndef ALZ_SPEC_BCAP_SHORT
+#define ALZ_SPEC_BCAP_SHORT 48
+#endif
+static int launch_b_cap(int fmt, const EncLaunch& L) {
+    const EncGeom& g = L.g; const bool segmented = L.seg.mem != nullptr;
+    if (segmented && seg_spec_format(fmt) && g.max_chain <= 5 && g.max_len > ALZ_SPEC_BCAP_SHORT) return ALZ_SPEC_BCAP_SHORT;
+    // (a lower cap for them, -DALZ_SPEC_BCAP=48 / 96 / 128 against choose_b_cap's 256 at quality 8, 256 x 64 KiB of Test.bmp, ms per call: windows 4 KiB apart 2.10 / 2.04 / 2.07 against 2.23,
+    // windows spread over the whole file -- flat stretches, where the true cursor lands on capped positions and its searches stay serial per buffer -- 6.37 / 3.67 / 3.78 against 2.69: not taken)
+    return (segmented && !seg_spec_format(fmt)) ? ALZ_LEN_CAP : choose_b_cap(g);
+}
+
+// ---- the streams whose parse visits few positions go without kernels A and B (enc_scan_select_kernel; mode 0: the probe decides, 1: every stream, 2: none).
+// The flag-bit formats of enc_parse_emit_kernel with windows up to 8 KiB, one property set, no min-length table (quality 2-9), a full batch (not the segmented path).
+struct EncScan {
+    int mode; u32* sel; u32 sel_pitch; u32* taken; const alz_encode_side* side_q;     // what the caller gave
+    const u32* regular; bool forked;                                                  // launch_scan: the streams that stay on the regular way; the side stream is to be joined
+};
+static bool takes_scan_path(const EncPath& path, int fmt, const EncLaunch& L, const EncScan& sc) {
+    const EncGeom& g = L.g; const bool seqf = path.family == ENC_SEQ;                                         // (enc_scan_seq_kernel; windows of 64 / 32 KiB: the nearest blocks scanned, kernel A's links behind them)
+    return sc.mode != 2 && path.scan && sc.sel != nullptr && !L.seg.mem && g.nprops <= 1 && !g.use_min_table && g.max_chain >= 3 &&
+           g.max_chain <= 32 /* (a block's candidates are measured at once, two lanes each at least) */ && (seqf || g.max_dist <= 8192) && g.link16 && !searches_in_the_parse(fmt, g) &&
+           (sc.mode == 1 || (g.max_len >= 64 && L.count >= ALZ_SCAN_MIN_STREAMS));  /* (matches of at most 18 bytes -- LZ10, MIO0, the default LZSS -- keep kernel B's compares short and every stream above the probe's
+                                                                  line: 10 000 windows of Test.bmp at quality 8 as LZ10 86.7 ms without the path, 95.0 with it; LZSS 86.5 / 106.1.  Forced: the parity tests.) */
+}
+// (`links`: kernel A's, for the formats whose search follows them behind the nearest blocks -- their select + scan kernels are launched behind kernel A, which then runs for every stream)
+static hipError_t launch_scan(int fmt, const EncLaunch& L, EncScan& sc, const int* links) {
+    u32* idx_regular = sc.sel + 2u * (size_t)sc.sel_pitch + 64u;      // (behind the probe's and the narrowing's lists; sel_pitch words each)
+    u32* idx_scan = idx_regular + sc.sel_pitch;
+    hipLaunchKernelGGL(enc_scan_select_kernel, dim3(L.count), dim3(64), 0, L.s, L.src, L.streams, L.index, L.count, L.g, L.tail, sc.mode == 1 ? 1 : 0, idx_regular, idx_scan, sc.taken, links, L.pos_off);
+    sc.regular = idx_regular;
+    // the scan streams' ONE kernel: on the side stream where there is one (a wavefront per stream walking serially -- latency, not throughput -- beside the other streams'
+    // kernels A / B / parse, which fill the GPU), joined at the end of this launch
+    hipStream_t sq = L.s; const alz_encode_side* q = sc.side_q;
+    if (q && q->s && q->fork && q->join && hipEventRecord(q->fork, L.s) == hipSuccess && hipStreamWaitEvent(q->s, q->fork, 0) == hipSuccess) sq = q->s;
+    with_format(fmt, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        if constexpr (enc_path(F).scan && enc_path(F).family == ENC_SEQ) hipLaunchKernelGGL((enc_scan_seq_kernel<F>), dim3(L.count), dim3(64), 0, sq, L.src, L.dst, L.streams, idx_scan, L.count, links, L.pos_off, L.results, L.aux, L.g);
+        else if constexpr (enc_path(F).scan) hipLaunchKernelGGL((enc_scan_emit_kernel<F>), dim3(L.count), dim3(64), 0, sq, L.src, L.dst, L.streams, idx_scan, L.count, L.pos_off, L.side, L.results, L.aux, L.g);
+    });
+    if (sq != L.s) { if (hipEventRecord(q->join, sq) != hipSuccess) return hipGetLastError(); sc.forked = true; }
+    return hipSuccess;
+}
+
+// ---- the links (kernel A): over segments where the launch is on the segmented path with at most 128 buffers (alz_encode_aseg) ...
+static AsegPlan plan_aseg(int fmt, const EncLaunch& L, const void* geom) {
+    AsegPlan aseg = { nullptr, 0, 0, 0, 0 };
+    if (L.seg.mem) {
+        size_t ab = 0; const u32 hist = seg_rec_hist(fmt, L.g, L.seg.seg_len);      // (as alz_encode_segmented sized the records)
+        if (alz_encode_aseg(geom, L.count, L.max_len, &aseg.SA, &aseg.ka, &aseg.W, &aseg.stride, &ab))
+            aseg.mem = (u8*)L.seg.mem + ((SegLayout(L.seg.mem, L.count, L.seg.kmax, hist).bytes + 255u) & ~(size_t)255u);
+    }
+    return aseg;
+}
+#ifndef ALZ_NARROW_BX_MAX
+#define ALZ_NARROW_BX_MAX 256u
+#endif
+// the links of the streams of `list` at the finder's own width, from the 15-bit ones in L.prev4 into `d_narrow`
+static void launch_narrow(const EncLaunch& L, const u32* list, int* d_narrow) {
+    const EncGeom& g = L.g; const u32 count = L.count, max_len = L.max_len;
+    if (g.max_dist <= 8192) {                                               // (range and window in LDS)
+        const u32 look = g.max_dist <= 4096 ? 4096u : 8192u, range = look == 4096u ? ALZ_NARROW_RANGE : 8192u;
+        u32 gx = (max_len + range - 1u) / range; if (gx == 0u) gx = 1u; if (gx > 4096u) gx = 4096u;
+        if (look == 4096u) hipLaunchKernelGGL((enc_narrow_lds_kernel<4096, ALZ_NARROW_RANGE>), dim3(gx, count), dim3(256), 0, L.s, L.src, L.streams, list, L.prev4, d_narrow, L.pos_off, g, L.tail);
+        else hipLaunchKernelGGL((enc_narrow_lds_kernel<8192, 8192>), dim3(gx, count), dim3(256), 0, L.s, L.src, L.streams, list, L.prev4, d_narrow, L.pos_off, g, L.tail);
+        return;
+    }
+    // (workgroups per stream, each with one contiguous range -- and the window behind it fetched again: ranges of 8 KiB for windows up to 8 KiB -- 16 KiB
+    // move the same 15 GB: what is fetched are the lines of the scattered candidate words --; for 64 KiB windows as few as still fill the GPU)
+    u32 bx = (max_len + 255u) / 256u; if (bx == 0u) bx = 1u;
+    // (... and for a handful of long buffers more than 32 each: 16 x 4 MiB as LZ4 blocks at quality 8 were 512 workgroups, two wavefronts per SIMD for a kernel of dependent loads)
+    if (!uses_win_prev(g)) { const u32 want = (ALZ_NARROW_WGS + count - 1u) / count; if (bx > want) bx = want; if (bx > ALZ_NARROW_BX_MAX) bx = ALZ_NARROW_BX_MAX; }
+    else if (bx > 32u) bx = 32u;
+    hipLaunchKernelGGL(enc_narrow_kernel, dim3(bx, count), dim3(256), 0, L.s, L.src, L.streams, list, L.prev4, d_narrow, L.pos_off, g, L.tail);
+}
+// ... or kernel A at 15 bits and the links of the finder's own hash width narrowed from them (enc_narrow_kernel), into an array of their own (`d_narrow`): what
+// follows reads its links there (the min-length table's links, where there are any, are kernel A's own either way).  Which streams:
+//   windows up to 8 KiB, no min-length table (quality 1-9): all -- a 15-bit chain meets a collision once in eight positions, the walk is short
+//     on any data, and range + window fit the LDS: synthetic LZSS batch at quality 8 94.2 -> 84.5 ms, Test.bmp windows -2 %;
+//   windows up to 8 KiB with the min-length table (quality >= 10): those of MANY distinct words.  Kernel A's alternative there is its one-pass
+//     form with tags, which does both tables at once and suits repetitive data (Test.bmp as Yaz0 at quality 12 121.8 ms against 126.9 behind
+//     1 + 2 passes at 15 bits), data of many distinct words does not (synthetic LZSS batch at quality 15 188.5 -> 175.3 ms);
+//   64 KiB windows: those of FEW distinct words (enc_words_kernel); the others through kernel A's 2^(hashBits - 15) passes.
+static hipError_t launch_links_narrowed(const EncLaunch& L, const AsegPlan& aseg, int* d_narrow, u32* d_sel, u32 sel_pitch) {
+    const EncGeom& g = L.g; const u32 count = L.count;
+    EncGeom g15 = g; g15.hash_bits = 15;
+    if (uses_win_prev(g) && !g.use_min_table) {
+        const hipError_t e15 = aseg.mem ? launch_prev_aseg(L, g15, L.index, aseg) : launch_prev(L, g15, L.index, L.prev4);
+        if (e15 != hipSuccess) return e15;
+        launch_narrow(L, L.index, d_narrow);
+        return hipSuccess;
+    }
+    const bool winm = uses_win_prev(g);                                                        // (small windows with the min-length table: the choice the other way round)
+    u32* l_narrow = d_sel; u32* l_wide = d_sel + sel_pitch + 2u;                               // (count + 1 words each; the probe of kernel B takes the array over afterwards)
+    (void)hipMemsetAsync(d_sel, 0xFF, ((size_t)sel_pitch + 2u + count + 1u) * sizeof(u32), L.s);
+    (void)hipMemsetAsync(l_narrow, 0, 4, L.s); (void)hipMemsetAsync(l_wide, 0, 4, L.s);
+    hipLaunchKernelGGL(enc_words_kernel, dim3(count), dim3(256), 0, L.s, L.src, L.streams, L.index, L.tail, d_sel, sel_pitch + 2u,
+                       winm ? ALZ_NARROW_MIN_THRESH16 : ALZ_NARROW_THRESH16, winm);
+    if (count < ALZ_NARROW_SPLIT_MIN) hipLaunchKernelGGL(enc_words_merge_kernel, dim3(1), dim3(256), 0, L.s, d_sel, sel_pitch + 2u);
+    const hipError_t e15 = (aseg.mem && !winm) ? launch_prev_aseg(L, g15, l_narrow + 1, aseg) : launch_prev(L, g15, l_narrow + 1, L.prev4, false, true);
+    if (e15 != hipSuccess) return e15;
+    launch_narrow(L, l_narrow + 1, d_narrow);
+    return launch_prev(L, g, l_wide + 1, d_narrow);
 }
 
 hipError_t alz_launch_encode(int fmt, hipStream_t stream, const void* d_src, void* d_dst, const alz_stream* d_streams, const uint32_t* d_index,
@@ -3959,173 +4139,26 @@ hipError_t alz_launch_encode(int fmt, hipStream_t stream, const void* d_src, voi
                              const uint64_t* d_pos_off, void* d_side, void* d_mask, alz_result* d_results, alz_encode_aux* d_aux, const void* geom,
                              uint32_t* d_sel, uint32_t sel_pitch, void* d_seg, uint32_t seg_len, uint32_t seg_kmax, int scan_mode, uint32_t* d_scan_taken, const alz_encode_side* side_q) {
     if (count == 0) return hipSuccess;
-    EncGeom g; memcpy(&g, geom, sizeof(g));
-    // (the segmented path of a small batch, alz_encode_seg.h: no cap -- its longest match is at most 2 040 bytes, kernel B has the GPU to itself, and
-    // every capped position the roles walk stands on costs that ONE wavefront two exact searches: 16 x 64 KiB of Test.bmp as Yaz0 at quality 8 1.17 ms of walk)
-    // (LZ4 blocks and LZO keep the cap: their segments are walked all at once -- alz_encode_seg_seq.h, enc_spec_walk_kernel --, so the exact searches of capped cursors run side by side,
-    // while no cap means every position of a flat stretch compared over 2 040 bytes: 256 x 64 KiB of Test.bmp at quality 8, kernel B 1.70 ms of the call's 3.37)
-    g.b_cap = (d_seg != nullptr && seg_len != 0u && !seg_spec_format(fmt)) ? ALZ_LEN_CAP : choose_b_cap(g);
-#ifndef ALZ_SPEC_BCAP_SHORT
-#define ALZ_SPEC_BCAP_SHORT 48
-#endif
-    if (d_seg != nullptr && seg_len != 0u && seg_spec_format(fmt) && g.max_chain <= 5 && g.max_len > ALZ_SPEC_BCAP_SHORT) g.b_cap = ALZ_SPEC_BCAP_SHORT;
-    // (a lower cap for them, -DALZ_SPEC_BCAP=48 / 96 / 128 against choose_b_cap's 256 at quality 8, 256 x 64 KiB of Test.bmp, ms per call: windows 4 KiB apart 2.10 / 2.04 / 2.07 against 2.23,
-    // windows spread over the whole file -- flat stretches, where the true cursor lands on capped positions and its searches stay serial per buffer -- 6.37 / 3.67 / 3.78 against 2.69: not taken)
-    const u8* src = (const u8*)d_src; u8* dst = (u8*)d_dst;
-    const int tail = fmt == ALZ_FMT_LZ4_BLOCK ? 5 : 0;
-    // ---- the streams whose parse visits few positions go without kernels A and B (enc_scan_select_kernel; scan_mode 0: the probe decides, 1: every stream, 2: none).
-    // The flag-bit formats of enc_parse_emit_kernel with windows up to 8 KiB, one property set, no min-length table (quality 2-9), a full batch (not the segmented path).
-    const u32* d_index_scan = nullptr;
-    bool scan_joined = true; const alz_encode_side* scan_side = nullptr;
-    const bool seqf = fmt == ALZ_FMT_LZ4_BLOCK || fmt == ALZ_FMT_SNAPPY_RAW;          // (enc_scan_seq_kernel; windows of 64 / 32 KiB: the nearest blocks scanned, kernel A's links behind them)
-    const bool scan_fam = seqf || fmt == ALZ_FMT_LZSS || fmt == ALZ_FMT_LZ10 || fmt == ALZ_FMT_LZ11 || fmt == ALZ_FMT_LZ40 || fmt == ALZ_FMT_YAZ0 || fmt == ALZ_FMT_YAY0 || fmt == ALZ_FMT_MIO0 ||
-                          fmt == ALZ_FMT_CLZ0 || fmt == ALZ_FMT_BLZ || fmt == ALZ_FMT_LZHUDSON;
-    const bool scan_ok = scan_mode != 2 && scan_fam && d_sel != nullptr && !(d_seg != nullptr && seg_len != 0u) && g.nprops <= 1 && !g.use_min_table && g.max_chain >= 3 &&
-                         g.max_chain <= 32 /* (a block's candidates are measured at once, two lanes each at least) */ && (seqf || g.max_dist <= 8192) && g.link16 && !searches_in_the_parse(fmt, g) &&
-                         (scan_mode == 1 || (g.max_len >= 64 && count >= ALZ_SCAN_MIN_STREAMS));  /* (matches of at most 18 bytes -- LZ10, MIO0, the default LZSS -- keep kernel B's compares short and every stream above the probe's
-                                                                  line: 10 000 windows of Test.bmp at quality 8 as LZ10 86.7 ms without the path, 95.0 with it; LZSS 86.5 / 106.1.  Forced: the parity tests.) */
-    // (`links`: kernel A's, for the formats whose search follows them behind the nearest blocks -- their select + scan kernels are launched behind kernel A, which then runs for every stream)
-    auto launch_scan = [&](const int* links) -> hipError_t {
-        u32* idx_regular = d_sel + 2u * (size_t)sel_pitch + 64u;      // (behind the probe's and the narrowing's lists; sel_pitch words each)
-        u32* idx_scan = idx_regular + sel_pitch;
-        hipLaunchKernelGGL(enc_scan_select_kernel, dim3(count), dim3(64), 0, stream, src, d_streams, d_index, count, g, tail, scan_mode == 1 ? 1 : 0, idx_regular, idx_scan, d_scan_taken, links, d_pos_off);
-        d_index = idx_regular; d_index_scan = idx_scan;
-        // the scan streams' ONE kernel: on the side stream where there is one (a wavefront per stream walking serially -- latency, not throughput -- beside the other streams'
-        // kernels A / B / parse, which fill the GPU), joined at the end of this launch
-        hipStream_t sq = stream;
-        if (side_q && side_q->s && side_q->fork && side_q->join && hipEventRecord(side_q->fork, stream) == hipSuccess && hipStreamWaitEvent(side_q->s, side_q->fork, 0) == hipSuccess) sq = side_q->s;
-        u8* side = (u8*)d_side;
-#define ALZ_SCANK(F) case F: hipLaunchKernelGGL((enc_scan_emit_kernel<F>), dim3(count), dim3(64), 0, sq, src, dst, d_streams, d_index_scan, count, d_pos_off, side, d_results, d_aux, g); break;
-        switch (fmt) {
-        ALZ_SCANK(ALZ_FMT_LZSS) ALZ_SCANK(ALZ_FMT_LZ10) ALZ_SCANK(ALZ_FMT_LZ11) ALZ_SCANK(ALZ_FMT_LZ40) ALZ_SCANK(ALZ_FMT_YAZ0) ALZ_SCANK(ALZ_FMT_YAY0) ALZ_SCANK(ALZ_FMT_MIO0)
-        ALZ_SCANK(ALZ_FMT_CLZ0) ALZ_SCANK(ALZ_FMT_BLZ) ALZ_SCANK(ALZ_FMT_LZHUDSON)
-        case ALZ_FMT_LZ4_BLOCK: hipLaunchKernelGGL((enc_scan_seq_kernel<ALZ_FMT_LZ4_BLOCK>), dim3(count), dim3(64), 0, sq, src, dst, d_streams, d_index_scan, count, links, d_pos_off, d_results, d_aux, g); break;
-        case ALZ_FMT_SNAPPY_RAW: hipLaunchKernelGGL((enc_scan_seq_kernel<ALZ_FMT_SNAPPY_RAW>), dim3(count), dim3(64), 0, sq, src, dst, d_streams, d_index_scan, count, links, d_pos_off, d_results, d_aux, g); break;
-        default: break;
-        }
-#undef ALZ_SCANK
-        if (sq != stream) { if (hipEventRecord(side_q->join, sq) != hipSuccess) return hipGetLastError(); scan_joined = false; scan_side = side_q; }
-        return hipSuccess;
-    };
-    if (scan_ok && !seqf) { const hipError_t es = launch_scan(nullptr); if (es != hipSuccess) return es; }
-    AsegPlan aseg = { nullptr, 0, 0, 0, 0 };                                   // (kernel A over segments: a launch on the segmented path with at most 128 buffers)
-    if (d_seg != nullptr && seg_len != 0u) {
-        size_t ab = 0; const u32 hist = seg_rec_hist(fmt, g, seg_len);      // (as alz_encode_segmented sized the records)
-        if (alz_encode_aseg(geom, count, max_len, &aseg.SA, &aseg.ka, &aseg.W, &aseg.stride, &ab))
-            aseg.mem = (u8*)d_seg + ((alz_encode_seg_bytes(count, seg_kmax, hist) + 255u) & ~(size_t)255u);
-    }
-    if (narrows_links(g) && d_narrow != nullptr && d_sel != nullptr) {
-        // Kernel A at 15 bits and the links of the finder's own hash width narrowed from them (enc_narrow_kernel), into an array of their own: what
-        // follows reads its links there (the min-length table's links, where there are any, are kernel A's own either way).  Which streams:
-        //   windows up to 8 KiB, no min-length table (quality 1-9): all -- a 15-bit chain meets a collision once in eight positions, the walk is short
-        //     on any data, and range + window fit the LDS: synthetic LZSS batch at quality 8 94.2 -> 84.5 ms, Test.bmp windows -2 %;
-        //   windows up to 8 KiB with the min-length table (quality >= 10): those of MANY distinct words.  Kernel A's alternative there is its one-pass
-        //     form with tags, which does both tables at once and suits repetitive data (Test.bmp as Yaz0 at quality 12 121.8 ms against 126.9 behind
-        //     1 + 2 passes at 15 bits), data of many distinct words does not (synthetic LZSS batch at quality 15 188.5 -> 175.3 ms);
-        //   64 KiB windows: those of FEW distinct words (enc_words_kernel); the others through kernel A's 2^(hashBits - 15) passes.
-        EncGeom g15 = g; g15.hash_bits = 15;
-        // (workgroups per stream, each with one contiguous range -- and the window behind it fetched again: ranges of 8 KiB for windows up to 8 KiB -- 16 KiB
-        // move the same 15 GB: what is fetched are the lines of the scattered candidate words --; for 64 KiB windows as few as still fill the GPU)
-        u32 bx = (max_len + 255u) / 256u; if (bx == 0u) bx = 1u;
-#ifndef ALZ_NARROW_BX_MAX
-#define ALZ_NARROW_BX_MAX 256u
-#endif
-        // (... and for a handful of long buffers more than 32 each: 16 x 4 MiB as LZ4 blocks at quality 8 were 512 workgroups, two wavefronts per SIMD for a kernel of dependent loads)
-        if (!uses_win_prev(g)) { const u32 want = (ALZ_NARROW_WGS + count - 1u) / count; if (bx > want) bx = want; if (bx > ALZ_NARROW_BX_MAX) bx = ALZ_NARROW_BX_MAX; }
-        else if (bx > 32u) bx = 32u;
-        auto narrow = [&](const u32* list) {
-            if (g.max_dist <= 8192) {                                               // (range and window in LDS)
-                const u32 look = g.max_dist <= 4096 ? 4096u : 8192u, range = look == 4096u ? ALZ_NARROW_RANGE : 8192u;
-                u32 gx = (max_len + range - 1u) / range; if (gx == 0u) gx = 1u; if (gx > 4096u) gx = 4096u;
-                if (look == 4096u) hipLaunchKernelGGL((enc_narrow_lds_kernel<4096, ALZ_NARROW_RANGE>), dim3(gx, count), dim3(256), 0, stream, src, d_streams, list, d_prev4, d_narrow, d_pos_off, g, tail);
-                else hipLaunchKernelGGL((enc_narrow_lds_kernel<8192, 8192>), dim3(gx, count), dim3(256), 0, stream, src, d_streams, list, d_prev4, d_narrow, d_pos_off, g, tail);
-                return;
-            }
-            hipLaunchKernelGGL(enc_narrow_kernel, dim3(bx, count), dim3(256), 0, stream, src, d_streams, list, d_prev4, d_narrow, d_pos_off, g, tail);
-        };
-        if (uses_win_prev(g) && !g.use_min_table) {
-            const hipError_t e15 = aseg.mem ? launch_prev_aseg(stream, src, d_streams, d_index, count, max_len, d_prev4, d_pos_off, g15, aseg, tail)
-                                            : launch_prev(stream, src, d_streams, d_index, count, d_prev4, d_prevm, d_pos_off, g15, tail);
-            if (e15 != hipSuccess) return e15;
-            narrow(d_index);
-        } else {
-            const bool winm = uses_win_prev(g);                                                        // (small windows with the min-length table: the choice the other way round)
-            u32* l_narrow = d_sel; u32* l_wide = d_sel + sel_pitch + 2u;                               // (count + 1 words each; the probe of kernel B takes the array over afterwards)
-            (void)hipMemsetAsync(d_sel, 0xFF, ((size_t)sel_pitch + 2u + count + 1u) * sizeof(u32), stream);
-            (void)hipMemsetAsync(l_narrow, 0, 4, stream); (void)hipMemsetAsync(l_wide, 0, 4, stream);
-            hipLaunchKernelGGL(enc_words_kernel, dim3(count), dim3(256), 0, stream, src, d_streams, d_index, tail, d_sel, sel_pitch + 2u,
-                               winm ? ALZ_NARROW_MIN_THRESH16 : ALZ_NARROW_THRESH16, winm);
-            if (count < ALZ_NARROW_SPLIT_MIN) hipLaunchKernelGGL(enc_words_merge_kernel, dim3(1), dim3(256), 0, stream, d_sel, sel_pitch + 2u);
-            const hipError_t e15 = (aseg.mem && !winm) ? launch_prev_aseg(stream, src, d_streams, l_narrow + 1, count, max_len, d_prev4, d_pos_off, g15, aseg, tail)
-                                                       : launch_prev(stream, src, d_streams, l_narrow + 1, count, d_prev4, d_prevm, d_pos_off, g15, tail, false, true);
-            if (e15 != hipSuccess) return e15;
-            narrow(l_narrow + 1);
-            const hipError_t ew = launch_prev(stream, src, d_streams, l_wide + 1, count, d_narrow, d_prevm, d_pos_off, g, tail);
-            if (ew != hipSuccess) return ew;
-        }
-        d_prev4 = d_narrow;
-    } else {
-        const hipError_t ea = (aseg.mem && g.hash_bits == 15) ? launch_prev_aseg(stream, src, d_streams, d_index, count, max_len, d_prev4, d_pos_off, g, aseg, tail)
-                                                              : launch_prev(stream, src, d_streams, d_index, count, d_prev4, d_prevm, d_pos_off, g, tail);
-        if (ea != hipSuccess) return ea;
-    }
-    if (scan_ok && seqf) { const hipError_t es = launch_scan(d_prev4); if (es != hipSuccess) return es; }
-    const bool segmented = d_seg != nullptr && seg_len != 0u;                   // (a batch of few buffers: alz_encode_seg.h -- always behind kernel B)
+    const EncPath path = enc_path(fmt);
+    EncLaunch L = { stream, (const u8*)d_src, (u8*)d_dst, d_streams, d_index, count, max_len, d_prev4, d_prevm, (mentry*)d_match, d_pos_off,
+                    (u8*)d_side, (u64*)d_mask, d_results, d_aux, EncGeom(), path.tail, { seg_len != 0u ? d_seg : nullptr, seg_len, seg_kmax } };
+    memcpy(&L.g, geom, sizeof(L.g));
+    L.g.b_cap = launch_b_cap(fmt, L);
+    EncScan scan = { scan_mode, d_sel, sel_pitch, d_scan_taken, side_q, nullptr, false };
+    const bool scan_ok = takes_scan_path(path, fmt, L, scan), seqf = path.family == ENC_SEQ;
+    hipError_t e = hipSuccess;
+    if (scan_ok && !seqf) { e = launch_scan(fmt, L, scan, nullptr); if (e != hipSuccess) return e; L.index = scan.regular; }       // (from here on: the streams that stay on the regular way)
+    const AsegPlan aseg = plan_aseg(fmt, L, geom);
+    const bool narrowed = narrows_links(L.g) && d_narrow != nullptr && d_sel != nullptr;
+    e = narrowed ? launch_links_narrowed(L, aseg, d_narrow, d_sel, sel_pitch) : (aseg.mem && L.g.hash_bits == 15) ? launch_prev_aseg(L, L.g, L.index, aseg) : launch_prev(L, L.g, L.index, L.prev4);
+    if (e != hipSuccess) return e;
+    if (narrowed) L.prev4 = d_narrow;                                           // (kernel B, the scan and the parse read the links of the finder's own width)
+    if (scan_ok && seqf) { e = launch_scan(fmt, L, scan, L.prev4); if (e != hipSuccess) return e; L.index = scan.regular; }
+    const bool segmented = L.seg.mem != nullptr;                                // (a batch of few buffers: alz_encode_seg.h -- always behind kernel B)
     const u32 wgc = !segmented ? 32u : count < 128u ? 128u : 64u;           // (workgroups per buffer in kernel B: 64 buffers of 64 KiB at quality 8 0.92 -> 0.79 ms with 128, 256 buffers 2.15 -> 2.08 with 64)
-    if (segmented || !searches_in_the_parse(fmt, g)) launch_match(stream, src, d_streams, d_index, count, max_len, d_prev4, d_prevm, d_match, d_pos_off, g, tail, wgc, true, d_sel, sel_pitch);
-#define ALZ_SEG(F) if (segmented) { launch_emit_seg_long<F>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-#define ALZ_SEGL(F) if (segmented) { launch_emit_seg_long<F>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-    const mentry* m = (const mentry*)d_match; u8* side = (u8*)d_side;
-    switch (fmt) {
-    case ALZ_FMT_LZSS: ALZ_SEG(ALZ_FMT_LZSS) launch_emit_par<ALZ_FMT_LZSS>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_LZ10: ALZ_SEG(ALZ_FMT_LZ10) launch_emit_par<ALZ_FMT_LZ10>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_LZ11: ALZ_SEGL(ALZ_FMT_LZ11) launch_emit_par<ALZ_FMT_LZ11>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_LZ40: ALZ_SEGL(ALZ_FMT_LZ40) launch_emit_par<ALZ_FMT_LZ40>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_YAZ0: ALZ_SEG(ALZ_FMT_YAZ0) launch_emit_par<ALZ_FMT_YAZ0>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_YAY0: ALZ_SEG(ALZ_FMT_YAY0) launch_emit_par<ALZ_FMT_YAY0>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_MIO0: ALZ_SEG(ALZ_FMT_MIO0) launch_emit_par<ALZ_FMT_MIO0>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_CLZ0: ALZ_SEG(ALZ_FMT_CLZ0) launch_emit_par<ALZ_FMT_CLZ0>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_BLZ: ALZ_SEG(ALZ_FMT_BLZ) launch_emit_par<ALZ_FMT_BLZ>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_LZHUDSON: ALZ_SEG(ALZ_FMT_LZHUDSON) launch_emit_par<ALZ_FMT_LZHUDSON>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, side, d_results, d_aux, g); break;
-    case ALZ_FMT_SMSR00: launch_emit<ALZ_FMT_SMSR00>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_PRS_BE: {
-        if (segmented) { launch_emit_seg_prs<true>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-        if (searches_in_the_parse(fmt, g)) hipLaunchKernelGGL((enc_emit_prs_kernel<true, true>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_results, d_aux, d_prev4, d_prevm, g);
-        else hipLaunchKernelGGL((enc_emit_prs_kernel<true, false>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_results, d_aux, d_prev4, d_prevm, g);
-        break; }
-    case ALZ_FMT_PRS_LE: {
-        if (segmented) { launch_emit_seg_prs<false>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-        if (searches_in_the_parse(fmt, g)) hipLaunchKernelGGL((enc_emit_prs_kernel<false, true>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_results, d_aux, d_prev4, d_prevm, g);
-        else hipLaunchKernelGGL((enc_emit_prs_kernel<false, false>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_results, d_aux, d_prev4, d_prevm, g);
-        break; }
-    case ALZ_FMT_LZ4_BLOCK: {
-        if (segmented) { launch_emit_seg_spec<ALZ_FMT_LZ4_BLOCK>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-        if (searches_in_the_parse(fmt, g)) hipLaunchKernelGGL((enc_parse_seq_kernel<ALZ_FMT_LZ4_BLOCK, true>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_prev4, d_prevm, d_results, d_aux, g);
-        else hipLaunchKernelGGL((enc_parse_seq_kernel<ALZ_FMT_LZ4_BLOCK, false>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_prev4, d_prevm, d_results, d_aux, g);
-        break; }
-    case ALZ_FMT_LZO: {
-        if (segmented) { launch_emit_seg_spec<ALZ_FMT_LZO>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-        if (searches_in_the_parse(fmt, g)) hipLaunchKernelGGL((enc_parse_lzo_kernel<true>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_results, d_aux, d_prev4, d_prevm, g);
-        else hipLaunchKernelGGL((enc_parse_lzo_kernel<false>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_results, d_aux, d_prev4, d_prevm, g);
-        break; }
-    case ALZ_FMT_SNAPPY_RAW: {
-        if (segmented) { launch_emit_seg_seq<ALZ_FMT_SNAPPY_RAW>(stream, count, src, dst, d_streams, d_index, (mentry*)d_match, d_pos_off, d_prev4, d_prevm, (u64*)d_mask, d_seg, seg_len, seg_kmax, d_results, d_aux, g); break; }
-        if (searches_in_the_parse(fmt, g)) hipLaunchKernelGGL((enc_parse_seq_kernel<ALZ_FMT_SNAPPY_RAW, true>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_prev4, d_prevm, d_results, d_aux, g);
-        else hipLaunchKernelGGL((enc_parse_seq_kernel<ALZ_FMT_SNAPPY_RAW, false>), dim3(count), dim3(64), 0, stream, src, dst, d_streams, d_index, count, m, d_pos_off, d_prev4, d_prevm, d_results, d_aux, g);
-        break; }
-    case ALZ_FMT_FASTLZ: launch_emit<ALZ_FMT_FASTLZ>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_HIG: launch_emit<ALZ_FMT_HIG>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_LZSHREK: launch_emit<ALZ_FMT_LZSHREK>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_WFLZ: launch_emit<ALZ_FMT_WFLZ>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_WFLZ_BE: launch_emit<ALZ_FMT_WFLZ_BE>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_REFPACK: launch_emit<ALZ_FMT_REFPACK>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_LZ02: launch_emit<ALZ_FMT_LZ02>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_CNS: launch_emit<ALZ_FMT_CNS>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    case ALZ_FMT_CNX2: launch_emit<ALZ_FMT_CNX2>(stream, count, src, dst, d_streams, d_index, m, d_pos_off, d_prev4, d_prevm, side, d_results, d_aux, g, (u64*)d_mask); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef ALZ_SEG
-    if (!scan_joined && hipStreamWaitEvent(stream, scan_side->join, 0) != hipSuccess) return hipGetLastError();      // (the scan streams' kernel)
+    if (segmented || !searches_in_the_parse(fmt, L.g)) launch_match(L, wgc, true, d_sel, sel_pitch);
+    if (!with_format(fmt, [&](auto f) { launch_emit_any<decltype(f)::value>(L); })) return hipErrorInvalidValue;
+    if (scan.forked && hipStreamWaitEvent(stream, side_q->join, 0) != hipSuccess) return hipGetLastError();      // (the scan streams' kernel)
     return hipGetLastError();
 }
 

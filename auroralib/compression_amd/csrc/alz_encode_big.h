@@ -905,7 +905,7 @@ bool alz_encode_big_eligible(int fmt, const void* geom, const alz_stream* st, ui
 size_t alz_encode_big_scratch_bytes(int fmt, const void* geom, const alz_stream* st) {
     EncGeom g; memcpy(&g, geom, sizeof(g));
     g.b_cap = ALZ_LEN_CAP;                                        // (not choose_b_cap's: here EVERY capped position somebody may land on is searched, generation by generation -- Yaz0 at quality 0 0.17 -> 1.5 ms with the cap at 48, quality 12 1.1 -> 500)
-    return BencLayout(*st, g, fmt == ALZ_FMT_LZ4_BLOCK ? 5 : 0).total + 256;
+    return BencLayout(*st, g, enc_path(fmt).tail).total + 256;
 }
 
 // Enqueues the whole-GPU encode of ONE stream.  d_result / d_aux: the stream's slots; d_ctl: 16 control words of the stream (the caller
@@ -915,7 +915,7 @@ hipError_t alz_launch_encode_big(int fmt, hipStream_t stream, const void* d_src_
                                  alz_encode_aux* d_aux, void* d_scratch, uint32_t* d_ctl, const void* geom) {
     EncGeom g; memcpy(&g, geom, sizeof(g));
     g.b_cap = ALZ_LEN_CAP;                                        // (not choose_b_cap's: here EVERY capped position somebody may land on is searched, generation by generation -- Yaz0 at quality 0 0.17 -> 1.5 ms with the cap at 48, quality 12 1.1 -> 500)
-    const int tail = fmt == ALZ_FMT_LZ4_BLOCK ? 5 : 0;
+    const int tail = enc_path(fmt).tail;
     BencLayout L(*st, g, tail);
     L.ctl_dev = d_ctl;
     u8* base = (u8*)d_scratch;
@@ -929,14 +929,16 @@ hipError_t alz_launch_encode_big(int fmt, hipStream_t stream, const void* d_src_
     hipError_t e;
     hipLaunchKernelGGL(benc_setup, dim3((a.K + 256u) / 256u), dim3(256), 0, stream, *st, a, vs, vindex, vpos, ctl, d_result, d_aux);
     // A': kernel A on the segments, then the links to where kernel B reads them
-    e = launch_prev(stream, (const u8*)d_src_base, vs, vindex, a.K, seg4, segm, vpos, g, 0, true);        // (a workgroup per segment AND pass: 1.24 -> 0.3 ms for an LZ4 block at quality 8)
+    EncLaunch v = {};                                             // (the segments as streams of kernel A, then the real stream -- entry K -- as kernel B's one)
+    v.s = stream; v.src = (const u8*)d_src_base; v.streams = vs; v.count = a.K; v.prevm = segm; v.pos_off = vpos; v.g = g;
+    e = launch_prev(v, g, vindex, seg4, true);                    // (a workgroup per segment AND pass: 1.24 -> 0.3 ms for an LZ4 block at quality 8)
     if (e != hipSuccess) return e;
     const u32 nbp = ((u32)a.limit + 256u) / 256u;
     if (g.link16) hipLaunchKernelGGL((benc_gather<true>), dim3(nbp), dim3(256), 0, stream, a, seg4, segm, fin4, finm, mark);
     else hipLaunchKernelGGL((benc_gather<false>), dim3(nbp), dim3(256), 0, stream, a, seg4, segm, fin4, finm, mark);
     // B: on the real stream (entry K)
-    launch_match(stream, (const u8*)d_src_base, vs, vindex + a.K, 1u, st->src_len, fin4, finm, match, vpos, g, tail, 4096u,
-                 false);                                           // (the two-phase kernel here too: tools/variants/r04_encode_switches.patch, -DALZ_BENC_DENSE)
+    v.index = vindex + a.K; v.count = 1u; v.max_len = st->src_len; v.prev4 = fin4; v.prevm = finm; v.match = match; v.tail = tail;
+    launch_match(v, 4096u, false);                                // (the two-phase kernel here too: tools/variants/r04_encode_switches.patch, -DALZ_BENC_DENSE)
     // C: the parse
     const u32 nbn = (a.nodes + 255u) / 256u;
     const bool caps = g.max_len > g.b_cap;                        // (only then can kernel B have capped anything)

@@ -27,6 +27,17 @@
 static inline u32 seg_table_hist(const EncGeom& g) { const u32 jl = g.max_len > ALZ_LEN_CAP ? (u32)ALZ_LEN_CAP : (u32)g.max_len; return (jl + 2u + 63u) & ~63u; }
 
 struct SegRec { u32 tok, pay, unc, head, tailbits, tailofs, fail, pad; };     // counts (C) -> exclusive prefix (P); the flag bits of straddling groups (E)
+// A launch's scratch behind `mem`: records, totals; synchronisation points, direct exits, entries, exit tables (`hist` words a segment) -- or, for the speculative
+// walk (alz_encode_seg_seq.h), in the place of those four its records of `recw` words.  ONE place for the host's sizing and every launcher's layout.
+struct SegLayout {
+    SegRec* seg; u32* stot; u32* sync; u32* direct; u32* entry; u32* ftab; u32* spec; u32 recw, kmax; size_t bytes; dim3 segs, bufs, wave;    // (the grids of a kernel per segment / per buffer)
+    SegLayout(void* mem, u32 count, u32 k, u32 hist) : kmax(k), segs(k, count), bufs(count), wave(64) {
+        const size_t ck = (size_t)count * kmax;
+        seg = (SegRec*)mem; stot = (u32*)(seg + ck); sync = stot + 4 * (size_t)count; direct = sync + ck; entry = direct + ck; ftab = entry + ck;
+        spec = sync; recw = 3u + hist;                                         // a record: SpecRec + the segment's cursor mask
+        bytes = ck * (sizeof(SegRec) + (3u + hist) * sizeof(u32)) + (size_t)count * 16u + 64u;
+    }
+};
 
 template <int FMT, bool EMIT>
 __global__ __launch_bounds__(64) void enc_seg_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
@@ -245,21 +256,7 @@ __global__ __launch_bounds__(64) void enc_seg_flags_kernel(u8* __restrict__ dst_
 // tests, tools/mid_batch_encode.py) -- never more than one launch of encode_core takes (65 535 buffers: the scratch is laid out for the launch's own count)
 // the words a segment's record holds behind its three fixed ones (alz_encode_seg_bytes): the exit table of the longest jump -- or, for the formats of the speculative walk
 // (LZ4 blocks, LZO: alz_encode_seg_seq.h), SpecRec and the segment's cursor mask.  ONE function for the host's sizing and the launch's layout.
-#ifndef ALZ_SPEC_LONG11
-#define ALZ_SPEC_LONG11 1     /* LZ11 / LZ40 (matches of up to 16 KiB and more) on the speculative walk as well -- 0: synchronisation points with a 16 KiB look-back, up to 256 buffers.  64 KiB windows of
-                                 Test.bmp as LZ11, ms per call, 0 / 1: quality 8 16 buffers 0.44 / 0.33, 64 1.06 / 0.70, 256 2.77 / 1.82, 512 4.46 (one wavefront per buffer) / 3.13, 1 024 6.92 / 5.93; quality 0 at 256
-                                 1.56 / 0.61; quality 12 at 64 / 256: 6.1 / 2.0, 22.9 / 3.8 (the stretches with capped entries were walked serially) */
-#endif
-// the formats whose segments are walked speculatively (alz_encode_seg_seq.h): no longest match that a look-back could be bounded by
-#ifndef ALZ_SPEC_FLAG
-#define ALZ_SPEC_FLAG 0       /* the flag-bit formats with matches of at most 273 bytes on it too: measured, not taken -- 16 / 256 / 1 024 x 64 KiB as Yaz0 at quality 8 0.19 / 1.74 / 5.96 ms with the synchronisation
-                                 points against 0.32 / 1.81 / 5.83 (every segment is a step of its buffer's serial fix-up: 64 steps of ~2 us for a 64 KiB buffer, which the synchronisation points do not have),
-                                 quality 12 at 64 buffers 2.66 against 9.65 */
-#endif
-static inline bool seg_spec_format(int fmt) {
-    if (ALZ_SPEC_FLAG && (fmt == ALZ_FMT_LZSS || fmt == ALZ_FMT_LZ10 || fmt == ALZ_FMT_YAZ0 || fmt == ALZ_FMT_YAY0 || fmt == ALZ_FMT_MIO0 || fmt == ALZ_FMT_CLZ0 || fmt == ALZ_FMT_BLZ || fmt == ALZ_FMT_LZHUDSON)) return true;
-    return fmt == ALZ_FMT_LZ4_BLOCK || fmt == ALZ_FMT_LZO || (ALZ_SPEC_LONG11 && (fmt == ALZ_FMT_LZ11 || fmt == ALZ_FMT_LZ40));
-}
+static constexpr bool seg_spec_format(int fmt) { return enc_path(fmt).seg == ENC_SEG_SPEC; }     // (walked speculatively, alz_encode_seg_seq.h: ALZ_SPEC_LONG11 / ALZ_SPEC_FLAG above enc_path)
 static inline u32 seg_rec_hist(int fmt, const EncGeom& g, u32 seg_len) {
     return seg_spec_format(fmt) ? 1u + (seg_len >> 5) : seg_table_hist(g);
 }
@@ -267,10 +264,10 @@ int alz_encode_seg_spec_format(int fmt) { return seg_spec_format(fmt) ? 1 : 0; }
 int alz_encode_segmented(int fmt, const void* geom, uint32_t count, uint32_t max_len, uint32_t max_streams, uint32_t* seg_len, uint32_t* kmax, uint32_t* hist_out) {
     EncGeom g; memcpy(&g, geom, sizeof(g));
     // LZ4 blocks, LZO (round 6): no synchronisation points -- every segment walked speculatively, the true walk strung together behind (alz_encode_seg_seq.h: enc_spec_walk_kernel)
-    const bool spec4 = seg_spec_format(fmt);
-    const bool long11 = !spec4 && (fmt == ALZ_FMT_LZ11 || fmt == ALZ_FMT_LZ40);                                                                                          // (matches of up to 16 KiB: round 6, seg_table_hist)
-    const bool fam = fmt == ALZ_FMT_LZSS || fmt == ALZ_FMT_LZ10 || fmt == ALZ_FMT_YAZ0 || fmt == ALZ_FMT_YAY0 || fmt == ALZ_FMT_MIO0 || fmt == ALZ_FMT_CLZ0 || long11 || spec4 ||
-                     fmt == ALZ_FMT_BLZ || fmt == ALZ_FMT_LZHUDSON || fmt == ALZ_FMT_SNAPPY_RAW || fmt == ALZ_FMT_PRS_BE || fmt == ALZ_FMT_PRS_LE;        // (raw Snappy, PRS: alz_encode_seg_seq.h)
+    const EncPath path = enc_path(fmt);
+    const bool spec4 = path.seg == ENC_SEG_SPEC;
+    const bool long11 = !spec4 && path.long_match;                          // (matches of up to 16 KiB: round 6, seg_table_hist)
+    const bool fam = path.seg != ENC_SEG_NONE;                               // (raw Snappy, PRS: alz_encode_seg_seq.h)
     const u32 rule = g.max_chain == 1 ? 1280u : g.max_chain < 64 ? 1536u : 512u;
     // (LZ11 / LZ40: enc_sync_kernel looks back 16 KiB per boundary and the stretches with capped entries stay serial -- 64 KiB windows of Test.bmp, ms per call, one wavefront per
     // buffer -> segments: 16 buffers 1.83 / 2.13 -> 0.42 / 0.44 at quality 0 / 8, 64: 1.84 / 2.57 -> 0.75 / 1.07, 256: 1.92 / 3.16 -> 1.57 / 2.78, 1 024: 2.71 / 5.19 -> 4.26 / 8.67)
@@ -327,7 +324,7 @@ int alz_encode_segmented(int fmt, const void* geom, uint32_t count, uint32_t max
     if (kmax) *kmax = (max_len + sl - 1u) / sl;
     return 1;
 }
-size_t alz_encode_seg_bytes(uint32_t count, uint32_t kmax, uint32_t hist) { return (size_t)count * kmax * (sizeof(SegRec) + (3u + hist) * sizeof(u32)) + (size_t)count * 16u + 64u; }   // records, totals; synchronisation points, direct exits, entries, exit tables
+size_t alz_encode_seg_bytes(uint32_t count, uint32_t kmax, uint32_t hist) { return SegLayout(nullptr, count, kmax, hist).bytes; }
 namespace {
 
 // ---- kernel A for a batch that does not even fill the CUs with a workgroup per buffer (at most 128 buffers): over overlapping SEGMENTS of the buffers, as
@@ -387,27 +384,19 @@ int alz_encode_aseg(const void* geom, uint32_t count, uint32_t max_len, uint32_t
 namespace {
 
 // the parse of a launch on this path: synchronisation points, exits, the cursor that enters every segment, the walk -- the start mask is complete behind it
-static void launch_seg_walk(hipStream_t s, u32 count, const u8* src, const alz_stream* streams, const u32* index, mentry* match, const u64* pos_off,
-                            const int* prev4, const int* prevm, u64* mask, u32* sync, u32 seglen, u32 kmax, const EncGeom& g) {
-    const u32 hist = seg_table_hist(g);
-    u32* direct = sync + (size_t)count * kmax;
-    u32* entry = direct + (size_t)count * kmax;
-    u32* ftab = entry + (size_t)count * kmax;
-    hipLaunchKernelGGL(enc_sync_kernel, dim3(kmax, count), dim3(64), 0, s, streams, index, (const mentry*)match, pos_off, sync, kmax, seglen, g);
-    hipLaunchKernelGGL(enc_exit_kernel, dim3(kmax, count), dim3(64), 0, s, streams, index, (const mentry*)match, pos_off, (const u32*)sync, direct, ftab, kmax, seglen, hist, g);
-    hipLaunchKernelGGL(enc_compose_kernel, dim3(count), dim3(64), 0, s, (const u32*)direct, (const u32*)ftab, entry, kmax, seglen, hist);
-    hipLaunchKernelGGL((enc_roles_kernel<true>), dim3(kmax, count), dim3(64), 0, s, src, streams, index, count, match, pos_off, prev4, prevm, mask, g, 0, (const u32*)entry, kmax);
+static void launch_seg_walk(const EncLaunch& L, const SegLayout& y) {
+    const u32 hist = seg_table_hist(L.g);
+    hipLaunchKernelGGL(enc_sync_kernel, y.segs, y.wave, 0, L.s, L.streams, L.index, L.match, L.pos_off, y.sync, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL(enc_exit_kernel, y.segs, y.wave, 0, L.s, L.streams, L.index, L.match, L.pos_off, y.sync, y.direct, y.ftab, y.kmax, L.seg.seg_len, hist, L.g);
+    hipLaunchKernelGGL(enc_compose_kernel, y.bufs, y.wave, 0, L.s, y.direct, y.ftab, y.entry, y.kmax, L.seg.seg_len, hist);
+    hipLaunchKernelGGL((enc_roles_kernel<true>), y.segs, y.wave, 0, L.s, L.src, L.streams, L.index, L.count, L.match, L.pos_off, L.prev4, L.prevm, L.mask, L.g, 0, y.entry, y.kmax);
 }
 
+// behind either walk, the flag-bit formats: tokens (counts), prefix, tokens (bytes), flags
 template <int FMT>
-static void launch_emit_seg(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, mentry* match, const u64* pos_off,
-                            const int* prev4, const int* prevm, u64* mask, void* d_seg, u32 seglen, u32 kmax, alz_result* results, alz_encode_aux* aux, const EncGeom& g) {
-    SegRec* seg = (SegRec*)d_seg;
-    u32* stot = (u32*)((u8*)d_seg + (size_t)count * kmax * sizeof(SegRec));
-    u32* sync = stot + 4 * (size_t)count;
-    launch_seg_walk(s, count, src, streams, index, match, pos_off, prev4, prevm, mask, sync, seglen, kmax, g);
-    hipLaunchKernelGGL((enc_seg_kernel<FMT, false>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL(enc_seg_prefix_kernel, dim3(count), dim3(64), 0, s, streams, index, seg, stot, kmax, seglen);
-    hipLaunchKernelGGL((enc_seg_kernel<FMT, true>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_seg_flags_kernel<FMT>), dim3(count), dim3(64), 0, s, dst, streams, index, (const SegRec*)seg, (const u32*)stot, kmax, seglen, results, aux);
+static void launch_seg_tokens(const EncLaunch& L, const SegLayout& y) {
+    hipLaunchKernelGGL((enc_seg_kernel<FMT, false>), y.segs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.seg, y.stot, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL(enc_seg_prefix_kernel, y.bufs, y.wave, 0, L.s, L.streams, L.index, y.seg, y.stot, y.kmax, L.seg.seg_len);
+    hipLaunchKernelGGL((enc_seg_kernel<FMT, true>), y.segs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.seg, y.stot, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL((enc_seg_flags_kernel<FMT>), y.bufs, y.wave, 0, L.s, L.dst, L.streams, L.index, y.seg, y.stot, y.kmax, L.seg.seg_len, L.results, L.aux);
 }

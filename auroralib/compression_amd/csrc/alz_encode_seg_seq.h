@@ -556,53 +556,39 @@ __global__ __launch_bounds__(64) void enc_lzo_head_kernel(const u8* __restrict__
     if (lane == 0) { tot[0] = olen; tot[1] = sp; tot[2] = mo; tot[3] = fail ? 2u : 0u; }
 }
 
+// the speculative parse of a launch: every segment walked from its own start, the true walk strung together behind, the long matches' masks
 template <int FMT>
-static void launch_emit_seg_spec(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, mentry* match, const u64* pos_off,
-                                 const int* prev4, const int* prevm, u64* mask, void* d_seg, u32 seglen, u32 kmax, alz_result* results, alz_encode_aux* aux, const EncGeom& g) {
-    SegRec* seg = (SegRec*)d_seg;
-    u32* stot = (u32*)((u8*)d_seg + (size_t)count * kmax * sizeof(SegRec));
-    u32* spec = stot + 4 * (size_t)count;
-    const u32 recw = 4u + (seglen >> 5);                                         // a record: SpecRec + the segment's cursor mask
-    hipLaunchKernelGGL((enc_spec_walk_kernel<FMT>), dim3(kmax, count), dim3(64), 0, s, src, streams, index, match, pos_off, prev4, prevm, mask, spec, kmax, seglen, recw, g);
-    hipLaunchKernelGGL((enc_spec_fix_kernel<FMT>), dim3(count), dim3(64), 0, s, src, streams, index, match, pos_off, prev4, prevm, mask, (const u32*)spec, kmax, seglen, recw, g);
-    hipLaunchKernelGGL((enc_spec_long_kernel<FMT>), dim3(kmax, count), dim3(64), 0, s, src, streams, index, match, pos_off, prev4, prevm, (const u64*)mask, seglen, g);
-    if (FMT == ALZ_FMT_LZO) hipLaunchKernelGGL(enc_lzo_head_kernel, dim3(count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, stot, results, aux);
-    hipLaunchKernelGGL((enc_seq_seg_kernel<FMT, false>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_seq_prefix_kernel<FMT>), dim3(count), dim3(64), 0, s, streams, index, seg, stot, kmax, seglen);
-    hipLaunchKernelGGL((enc_seq_seg_kernel<FMT, true>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_seq_finish_kernel<FMT>), dim3(count), dim3(64), 0, s, src, dst, streams, index, (const SegRec*)seg, (const u32*)stot, kmax, seglen, results, aux);
+static void launch_spec_walk(const EncLaunch& L, const SegLayout& y) {
+    hipLaunchKernelGGL((enc_spec_walk_kernel<FMT>), y.segs, y.wave, 0, L.s, L.src, L.streams, L.index, L.match, L.pos_off, L.prev4, L.prevm, L.mask, y.spec, y.kmax, L.seg.seg_len, y.recw, L.g);
+    hipLaunchKernelGGL((enc_spec_fix_kernel<FMT>), y.bufs, y.wave, 0, L.s, L.src, L.streams, L.index, L.match, L.pos_off, L.prev4, L.prevm, L.mask, y.spec, y.kmax, L.seg.seg_len, y.recw, L.g);
+    hipLaunchKernelGGL((enc_spec_long_kernel<FMT>), y.segs, y.wave, 0, L.s, L.src, L.streams, L.index, L.match, L.pos_off, L.prev4, L.prevm, L.mask, L.seg.seg_len, L.g);
 }
 
-// LZ11 / LZ40 (flag-bit formats whose matches reach 16 KiB and more): the speculative walk in front of alz_encode_seg.h's token / flag emitters -- or, with -DALZ_SPEC_LONG11=0, that
-// file's synchronisation points with their 16 KiB look-back
+// behind either walk, the sequence formats: sequences (counts), prefix, sequences (bytes), finish
 template <int FMT>
-static void launch_emit_seg_long(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, mentry* match, const u64* pos_off,
-                                 const int* prev4, const int* prevm, u64* mask, void* d_seg, u32 seglen, u32 kmax, alz_result* results, alz_encode_aux* aux, const EncGeom& g) {
-    if (!seg_spec_format(FMT)) { launch_emit_seg<FMT>(s, count, src, dst, streams, index, match, pos_off, prev4, prevm, mask, d_seg, seglen, kmax, results, aux, g); return; }
-    SegRec* seg = (SegRec*)d_seg;
-    u32* stot = (u32*)((u8*)d_seg + (size_t)count * kmax * sizeof(SegRec));
-    u32* spec = stot + 4 * (size_t)count;
-    const u32 recw = 4u + (seglen >> 5);
-    hipLaunchKernelGGL((enc_spec_walk_kernel<FMT>), dim3(kmax, count), dim3(64), 0, s, src, streams, index, match, pos_off, prev4, prevm, mask, spec, kmax, seglen, recw, g);
-    hipLaunchKernelGGL((enc_spec_fix_kernel<FMT>), dim3(count), dim3(64), 0, s, src, streams, index, match, pos_off, prev4, prevm, mask, (const u32*)spec, kmax, seglen, recw, g);
-    hipLaunchKernelGGL((enc_spec_long_kernel<FMT>), dim3(kmax, count), dim3(64), 0, s, src, streams, index, match, pos_off, prev4, prevm, (const u64*)mask, seglen, g);
-    hipLaunchKernelGGL((enc_seg_kernel<FMT, false>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL(enc_seg_prefix_kernel, dim3(count), dim3(64), 0, s, streams, index, seg, stot, kmax, seglen);
-    hipLaunchKernelGGL((enc_seg_kernel<FMT, true>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_seg_flags_kernel<FMT>), dim3(count), dim3(64), 0, s, dst, streams, index, (const SegRec*)seg, (const u32*)stot, kmax, seglen, results, aux);
+static void launch_seg_seqs(const EncLaunch& L, const SegLayout& y) {
+    hipLaunchKernelGGL((enc_seq_seg_kernel<FMT, false>), y.segs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.seg, y.stot, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL((enc_seq_prefix_kernel<FMT>), y.bufs, y.wave, 0, L.s, L.streams, L.index, y.seg, y.stot, y.kmax, L.seg.seg_len);
+    hipLaunchKernelGGL((enc_seq_seg_kernel<FMT, true>), y.segs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.seg, y.stot, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL((enc_seq_finish_kernel<FMT>), y.bufs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, y.seg, y.stot, y.kmax, L.seg.seg_len, L.results, L.aux);
 }
 
+// LZ4 blocks, LZO (speculative walk), raw Snappy (synchronisation points): enc_path says which
 template <int FMT>
-static void launch_emit_seg_seq(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, mentry* match, const u64* pos_off,
-                                const int* prev4, const int* prevm, u64* mask, void* d_seg, u32 seglen, u32 kmax, alz_result* results, alz_encode_aux* aux, const EncGeom& g) {
-    SegRec* seg = (SegRec*)d_seg;
-    u32* stot = (u32*)((u8*)d_seg + (size_t)count * kmax * sizeof(SegRec));
-    u32* sync = stot + 4 * (size_t)count;
-    launch_seg_walk(s, count, src, streams, index, match, pos_off, prev4, prevm, mask, sync, seglen, kmax, g);
-    hipLaunchKernelGGL((enc_seq_seg_kernel<FMT, false>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_seq_prefix_kernel<FMT>), dim3(count), dim3(64), 0, s, streams, index, seg, stot, kmax, seglen);
-    hipLaunchKernelGGL((enc_seq_seg_kernel<FMT, true>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, (const u32*)stot, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_seq_finish_kernel<FMT>), dim3(count), dim3(64), 0, s, src, dst, streams, index, (const SegRec*)seg, (const u32*)stot, kmax, seglen, results, aux);
+static void launch_emit_seg_seq(const EncLaunch& L) {
+    const SegLayout y(L.seg.mem, L.count, L.seg.kmax, seg_rec_hist(FMT, L.g, L.seg.seg_len));
+    if constexpr (seg_spec_format(FMT)) launch_spec_walk<FMT>(L, y); else launch_seg_walk(L, y);
+    if (FMT == ALZ_FMT_LZO) hipLaunchKernelGGL(enc_lzo_head_kernel, dim3(L.count), dim3(64), 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.stot, L.results, L.aux);
+    launch_seg_seqs<FMT>(L, y);
+}
+
+// The flag-bit formats.  LZ11 / LZ40 (matches reach 16 KiB and more): the speculative walk in front of alz_encode_seg.h's token / flag emitters -- or, with -DALZ_SPEC_LONG11=0, that
+// file's synchronisation points with their 16 KiB look-back.  (A plain `if`: both walks stay compiled for every one of these formats, whichever way the switches point.)
+template <int FMT>
+static void launch_emit_seg_flag(const EncLaunch& L) {
+    const SegLayout y(L.seg.mem, L.count, L.seg.kmax, seg_rec_hist(FMT, L.g, L.seg.seg_len));
+    if (seg_spec_format(FMT)) launch_spec_walk<FMT>(L, y); else launch_seg_walk(L, y);
+    launch_seg_tokens<FMT>(L, y);
 }
 
 // ---------------------------------------------------------------------------------------------- PRS over segments
@@ -826,14 +812,11 @@ __global__ __launch_bounds__(64) void enc_prs_flags_kernel(u8* __restrict__ dst_
 }
 
 template <bool BIG>
-static void launch_emit_seg_prs(hipStream_t s, u32 count, const u8* src, u8* dst, const alz_stream* streams, const u32* index, mentry* match, const u64* pos_off,
-                                const int* prev4, const int* prevm, u64* mask, void* d_seg, u32 seglen, u32 kmax, alz_result* results, alz_encode_aux* aux, const EncGeom& g) {
-    SegRec* seg = (SegRec*)d_seg;
-    u32* stot = (u32*)((u8*)d_seg + (size_t)count * kmax * sizeof(SegRec));
-    u32* sync = stot + 4 * (size_t)count;
-    launch_seg_walk(s, count, src, streams, index, match, pos_off, prev4, prevm, mask, sync, seglen, kmax, g);
-    hipLaunchKernelGGL((enc_prs_seg_kernel<BIG, false>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, kmax, seglen, g);
-    hipLaunchKernelGGL(enc_prs_prefix_kernel, dim3(count), dim3(64), 0, s, streams, index, seg, stot, kmax, seglen);
-    hipLaunchKernelGGL((enc_prs_seg_kernel<BIG, true>), dim3(kmax, count), dim3(64), 0, s, src, dst, streams, index, (const mentry*)match, pos_off, (const u64*)mask, seg, kmax, seglen, g);
-    hipLaunchKernelGGL((enc_prs_flags_kernel<BIG>), dim3(count), dim3(64), 0, s, dst, streams, index, (const SegRec*)seg, (const u32*)stot, kmax, seglen, results, aux);
+static void launch_emit_seg_prs(const EncLaunch& L) {
+    const SegLayout y(L.seg.mem, L.count, L.seg.kmax, seg_table_hist(L.g));
+    launch_seg_walk(L, y);
+    hipLaunchKernelGGL((enc_prs_seg_kernel<BIG, false>), y.segs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.seg, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL(enc_prs_prefix_kernel, y.bufs, y.wave, 0, L.s, L.streams, L.index, y.seg, y.stot, y.kmax, L.seg.seg_len);
+    hipLaunchKernelGGL((enc_prs_seg_kernel<BIG, true>), y.segs, y.wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.match, L.pos_off, L.mask, y.seg, y.kmax, L.seg.seg_len, L.g);
+    hipLaunchKernelGGL((enc_prs_flags_kernel<BIG>), y.bufs, y.wave, 0, L.s, L.dst, L.streams, L.index, y.seg, y.stot, y.kmax, L.seg.seg_len, L.results, L.aux);
 }

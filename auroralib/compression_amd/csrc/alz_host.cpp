@@ -128,7 +128,8 @@ struct alz_ctx {
     void* d_plan = nullptr; size_t d_plan_cap = 0;   // plan arrays of the host-buffer entry points (no hipMalloc / hipFree per call)
     // encoder scratch (prev links, narrowed links, matches, masks ...: ~45 GB for 10 000 x 256 KiB at quality 8), one grow-only slot
     // per purpose: allocating and freeing it per call cost 1-2 s, four times the kernels.  alz_ctx_release_scratch() returns it.
-    void* enc_buf[15] = {nullptr}; size_t enc_cap[15] = {0};
+    enum { ENC_STREAMS, ENC_RESULTS, ENC_AUX, ENC_INDEX, ENC_POS, ENC_PREV4, ENC_PREVM, ENC_MATCH, ENC_SIDE, ENC_MASK, ENC_TAIL, ENC_BIG, ENC_SEL, ENC_NARROW, ENC_SEG, ENC_SLOTS };
+    void* enc_buf[ENC_SLOTS] = {nullptr}; size_t enc_cap[ENC_SLOTS] = {0};
     copy_pool* pool = nullptr;                 // created with the pinned buffers
     std::vector<copy_job> jobs;                // (scratch of the staging loops)
     void copy(uint8_t* dst, const uint8_t* src, size_t len) { jobs.clear(); add_copy(jobs, dst, src, len); pool->run(jobs); }
@@ -912,27 +913,26 @@ int alz_decode(alz_ctx* c, uint32_t format, const alz_lz_properties* props, cons
 
 // Device buffers of one encode call, freed on every exit path
 struct EncScratch {
-    alz_ctx* c; int slot = 0;
+    alz_ctx* c; hipError_t err = hipSuccess;
     explicit EncScratch(alz_ctx* ctx) : c(ctx) {}
-    // slots are handed out in call order; `want` = false skips one (its buffer, if any, stays for a later call)
-    hipError_t alloc(void** p, size_t bytes, bool want = true) {
-        const int k = slot++;
-        if (!want) { *p = nullptr; return hipSuccess; }
+    // the context's buffer `k` (alz_ctx::ENC_...), grown to `bytes`; `want` = false leaves it alone (its buffer, if any, stays for a later call).
+    // nullptr then, and after a failure: `err` keeps the first one, and nothing more is allocated behind it
+    void* get(int k, size_t bytes, bool want = true) {
+        if (!want || err != hipSuccess) return nullptr;
         if (bytes < 16) bytes = 16;
         if (c->enc_cap[k] < bytes) {
             if (c->enc_buf[k]) { (void)hipFree(c->enc_buf[k]); c->enc_buf[k] = nullptr; c->enc_cap[k] = 0; }
-            hipError_t e = hipMalloc(&c->enc_buf[k], bytes);
-            if (e != hipSuccess) { c->enc_buf[k] = nullptr; return e; }
+            err = hipMalloc(&c->enc_buf[k], bytes);
+            if (err != hipSuccess) { c->enc_buf[k] = nullptr; return nullptr; }
             c->enc_cap[k] = bytes;
         }
-        *p = c->enc_buf[k];
-        return hipSuccess;
+        return c->enc_buf[k];
     }
 };
 // (alz_encode_seg.h) 1: a small batch of this format is walked speculatively per segment (alz_encode_seg_seq.h), not from synchronisation points
 extern "C++" int alz_encode_seg_spec_format(int fmt);
 static void release_scratch(alz_ctx* c) {
-    for (int k = 0; k < 15; k++) { if (c->enc_buf[k]) (void)hipFree(c->enc_buf[k]); c->enc_buf[k] = nullptr; c->enc_cap[k] = 0; }
+    for (int k = 0; k < alz_ctx::ENC_SLOTS; k++) { if (c->enc_buf[k]) (void)hipFree(c->enc_buf[k]); c->enc_buf[k] = nullptr; c->enc_cap[k] = 0; }
     void** bufs[] = {&c->d_src, &c->d_dst, &c->d_items, &c->d_pack, &c->d_plan, &c->d_bigbuf};
     size_t* caps[] = {&c->d_src_cap, &c->d_dst_cap, &c->d_items_cap, &c->d_pack_cap, &c->d_plan_cap, &c->d_bigbuf_cap};
     for (int i = 0; i < 6; i++) { if (*bufs[i]) (void)hipFree(*bufs[i]); *bufs[i] = nullptr; *caps[i] = 0; }
@@ -1058,7 +1058,6 @@ static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_set
         if (all) {
             HIP_TRY(hipSetDevice(c->device));
             EncScratch sc(c);
-            void *d_tail = nullptr, *d_big = nullptr, *skip = nullptr;
             size_t tail_bytes = 0;
             if (!src_has_slack)
                 for (uint32_t i = 0; i < n; i++)
@@ -1066,10 +1065,9 @@ static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_set
             // what travels back: per stream its result, its section offsets and the path's 16 control words -- one block, one copy
             const size_t out_one = sizeof(alz_result) + sizeof(alz_encode_aux) + 16 * sizeof(uint32_t), sb_al = (sb + 255) & ~(size_t)255;
             hipError_t e = hipSuccess;
-            for (int k = 0; k < 10 && e == hipSuccess; k++) e = sc.alloc(&skip, 0, false);   // (the batch pipeline's slots, in its order: the buffers are shared)
-            if (e == hipSuccess) e = sc.alloc(&d_tail, tail_bytes, tail_bytes != 0);
-            if (e == hipSuccess) e = sc.alloc(&d_big, sb_al + (size_t)n * out_one + 64);
-            if (e != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(e));
+            void* d_tail = sc.get(alz_ctx::ENC_TAIL, tail_bytes, tail_bytes != 0);                 // (shared with the batch pipeline below)
+            void* d_big = sc.get(alz_ctx::ENC_BIG, sb_al + (size_t)n * out_one + 64);
+            if (sc.err != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(sc.err));
             uint8_t* d_out = (uint8_t*)d_big + sb_al;
             alz_result* d_results = (alz_result*)d_out;
             alz_encode_aux* d_aux = (alz_encode_aux*)(d_out + (size_t)n * sizeof(alz_result));
@@ -1121,26 +1119,21 @@ static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_set
     // a launch carries the stream in gridDim.y; 70 000 went through on this runtime, the cap is caution)
     const uint32_t CH = 65535u;
     EncScratch sc(c);
-    alz_stream* d_streams = nullptr; alz_result* d_results = nullptr; alz_encode_aux* d_aux = nullptr; uint32_t* d_index = nullptr;
-    uint64_t* d_pos = nullptr; int *d_prev4 = nullptr, *d_prevm = nullptr; void *d_match = nullptr, *d_side = nullptr, *d_mask = nullptr;
-    hipError_t e = sc.alloc((void**)&d_streams, (size_t)n * sizeof(alz_stream));
-    if (e == hipSuccess) e = sc.alloc((void**)&d_results, (size_t)n * sizeof(alz_result));
-    if (e == hipSuccess) e = sc.alloc((void**)&d_aux, (size_t)n * sizeof(alz_encode_aux));
-    if (e == hipSuccess) e = sc.alloc((void**)&d_index, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = sc.alloc((void**)&d_pos, (size_t)n * sizeof(uint64_t));
-    if (e == hipSuccess) e = sc.alloc((void**)&d_prev4, (size_t)total * sizeof(int) + 256);   // (+ slack: the look-ahead of the fused parse kernel reads a link of an empty last stream)
-    if (e == hipSuccess) e = sc.alloc((void**)&d_prevm, (size_t)total * sizeof(int) + 256, any_min);   // the min-length table's links
-    if (e == hipSuccess) e = sc.alloc(&d_match, (size_t)total * 4 + 64, any_match);   // one 32-bit entry per position (alz_encode.hip: mentry); not when every launch searches inside its parse + emit kernel
-    if (e == hipSuccess) e = sc.alloc(&d_side, (size_t)total * 2 + 64, cnt[ALZ_FMT_YAY0] || cnt[ALZ_FMT_MIO0] || cnt[ALZ_FMT_SMSR00]);   // section buffers
-    if (e == hipSuccess) e = sc.alloc(&d_mask, (size_t)total / 8 + 64, any_mask);          // a bit per position: the start mask of enc_roles_kernel, for the formats whose emitter is a kernel of its own
-    void* d_tail = nullptr; uint32_t* d_sel = nullptr;
-    if (e == hipSuccess) e = sc.alloc(&d_tail, tail_bytes, !tail_ix.empty());
-    { void* skip_big = nullptr; if (e == hipSuccess) e = sc.alloc(&skip_big, 0, false); }        // (slot 11: the whole-GPU path's scratch)
-    if (e == hipSuccess) e = sc.alloc((void**)&d_sel, ((size_t)4 * n + 128) * sizeof(uint32_t), any_match);     // which kernel B per stream (enc_probe_kernel); behind it the two lists of enc_scan_select_kernel
-    int* d_narrow = nullptr;
-    if (e == hipSuccess) e = sc.alloc((void**)&d_narrow, (size_t)total * sizeof(int) + 256, any_narrow);   // slot 13: the links of the finder's own hash width, narrowed from 15-bit ones (enc_narrow_kernel)
-    void* d_seg = nullptr;
-    if (e == hipSuccess) e = sc.alloc(&d_seg, seg_bytes, seg_bytes != 0);                                  // slot 14: segment records of alz_encode_seg.h
+    alz_stream* d_streams = (alz_stream*)sc.get(alz_ctx::ENC_STREAMS, (size_t)n * sizeof(alz_stream));
+    alz_result* d_results = (alz_result*)sc.get(alz_ctx::ENC_RESULTS, (size_t)n * sizeof(alz_result));
+    alz_encode_aux* d_aux = (alz_encode_aux*)sc.get(alz_ctx::ENC_AUX, (size_t)n * sizeof(alz_encode_aux));
+    uint32_t* d_index = (uint32_t*)sc.get(alz_ctx::ENC_INDEX, (size_t)n * sizeof(uint32_t));
+    uint64_t* d_pos = (uint64_t*)sc.get(alz_ctx::ENC_POS, (size_t)n * sizeof(uint64_t));
+    int* d_prev4 = (int*)sc.get(alz_ctx::ENC_PREV4, (size_t)total * sizeof(int) + 256);   // (+ slack: the look-ahead of the fused parse kernel reads a link of an empty last stream)
+    int* d_prevm = (int*)sc.get(alz_ctx::ENC_PREVM, (size_t)total * sizeof(int) + 256, any_min);   // the min-length table's links
+    void* d_match = sc.get(alz_ctx::ENC_MATCH, (size_t)total * 4 + 64, any_match);   // one 32-bit entry per position (alz_encode.hip: mentry); not when every launch searches inside its parse + emit kernel
+    void* d_side = sc.get(alz_ctx::ENC_SIDE, (size_t)total * 2 + 64, cnt[ALZ_FMT_YAY0] || cnt[ALZ_FMT_MIO0] || cnt[ALZ_FMT_SMSR00]);   // section buffers
+    void* d_mask = sc.get(alz_ctx::ENC_MASK, (size_t)total / 8 + 64, any_mask);          // a bit per position: the start mask of enc_roles_kernel, for the formats whose emitter is a kernel of its own
+    void* d_tail = sc.get(alz_ctx::ENC_TAIL, tail_bytes, !tail_ix.empty());
+    uint32_t* d_sel = (uint32_t*)sc.get(alz_ctx::ENC_SEL, ((size_t)4 * n + 128) * sizeof(uint32_t), any_match);     // which kernel B per stream (enc_probe_kernel); behind it the two lists of enc_scan_select_kernel
+    int* d_narrow = (int*)sc.get(alz_ctx::ENC_NARROW, (size_t)total * sizeof(int) + 256, any_narrow);   // the links of the finder's own hash width, narrowed from 15-bit ones (enc_narrow_kernel)
+    void* d_seg = sc.get(alz_ctx::ENC_SEG, seg_bytes, seg_bytes != 0);                                  // segment records of alz_encode_seg.h
+    hipError_t e = sc.err;
     if (e != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(e));
     tm.mark("validate + allocate");
     std::vector<uint32_t> index(n), foff(ALZ_FMT_COUNT, 0), fill(ALZ_FMT_COUNT, 0);
@@ -1178,6 +1171,7 @@ static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_set
         const void* g = geom.data() + f * alz_encode_geom_size();
         for (uint32_t done = 0; done < count; done += CH) {
             const uint32_t k = count - done < CH ? count - done : CH;
+            // (positional on purpose: the prototype lives in alz_internal.h, which the decode counters are hashed over -- a struct in its place belongs to the change that next re-profiles the decoder)
             e = alz_launch_encode(fmt, c->stream, d_src_base, d_dst_base, d_streams, d_index + first + done, k, max_len, d_prev4, d_prevm, d_narrow,
                                   d_match, d_pos, d_side, d_mask, d_results, d_aux, g, d_sel, n, seg_len[f] ? d_seg : nullptr, seg_len[f], seg_kmax[f], (c->exact || c->variant != 0) ? 2 : c->scan_mode, c->d_big_accepted ? c->d_big_accepted + 1 : nullptr, &side_q);
             if (e != hipSuccess) return fail(ALZ_E_HIP, "encode launch (format %d) failed: %s", fmt, hipGetErrorString(e));
