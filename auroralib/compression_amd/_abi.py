@@ -70,4 +70,12 @@ class ContainerOptions(C.Structure):
                 ("key", C.c_uint32), ("name", C.c_uint8 * 32)]
 
 
+# the measure entry points (include/auroralz.h): decoded sizes without decoding
+MEASURE_NO_BOUND = 0xFFFFFF00          # the largest dst_cap: "count everything"
+MEASURE_PROTOTYPES = {
+    "alz_measure_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+    "alz_measure_batch_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+    "alz_container_measure": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)],
+}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16

@@ -102,6 +102,23 @@ class Context:
         check(self.lib.alz_decode(self.h, fmt, C.byref(lz) if lz is not None else None, src, len(src), decom_len, aux0, aux1, _vp(dst), cap, C.byref(r)))
         return dst[:r.dst_len].tobytes(), r
 
+    # ---- decoded sizes without decoding
+    def measure_batch(self, streams, src, lz=None):
+        """alz_measure_batch on a host buffer: the results alz_decode_batch would return for `streams` (status, dst_len, src_used), nothing decoded.
+        dst_off is ignored and dst_cap only bounds the count (A.MEASURE_NO_BOUND: the true size)."""
+        n = len(streams)
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        res = (A.Result * n)()
+        check(self.lib.alz_measure_batch(self.h, C.byref(lz) if lz is not None else None, n, _vp(src), src.nbytes, streams, res))
+        return res
+
+    def measure_batch_device(self, streams, d_src, src_bytes, lz=None):
+        """alz_measure_batch_device: the same with the source already in HBM at d_src; last_kernel_ms() is the device time of the launches."""
+        n = len(streams)
+        res = (A.Result * n)()
+        check(self.lib.alz_measure_batch_device(self.h, C.byref(lz) if lz is not None else None, n, d_src, src_bytes, streams, res))
+        return res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""
@@ -211,6 +228,17 @@ class MultiPlan:
         if self.h:
             self.lib.alz_plan_destroy_multi(self.h)
             self.h = None
+
+
+def layout_from_results(streams, results, align=16):
+    """The second step of a two-pass decode: fills dst_off / dst_cap of `streams` from measured lengths (exclusive prefix sum, every stream's
+    start rounded up to `align`) and returns the bytes the destination needs."""
+    off = 0
+    for s, r in zip(streams, results):
+        off = (off + align - 1) // align * align
+        s.dst_off, s.dst_cap = off, r.dst_len
+        off += r.dst_len
+    return off
 
 
 def partition_batch(streams, n_parts):

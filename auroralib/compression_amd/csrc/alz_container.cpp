@@ -643,6 +643,10 @@ static void lz00_keystream(uint8_t* p, size_t n, uint32_t key) {
     }
 }
 
+// shared with alz_container_measure.cpp (declared in alz_measure.h; not part of the ABI)
+uint32_t alz_host_xxh32(const uint8_t* p, size_t len, uint32_t seed) { return xxh32(p, len, seed); }
+int alz_host_prs_byte_order(const uint8_t* src, size_t len) { return prs_byte_order(src, len); }
+
 extern "C" {
 
 // IProvidesDecompressedSize.GetDecompressedSize  Interfaces/IProvidesDecompressedSize.cs:20

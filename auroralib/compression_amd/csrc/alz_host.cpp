@@ -18,6 +18,7 @@
 #include <sched.h>
 
 #include "alz_internal.h"
+#include "alz_measure.h"
 
 static thread_local char g_err[512] = "";
 
@@ -909,6 +910,62 @@ int alz_decode(alz_ctx* c, uint32_t format, const alz_lz_properties* props, cons
     alz_stream s; memset(&s, 0, sizeof(s));
     s.src_len = src_len; s.dst_cap = dst_cap; s.decom_len = decom_len; s.aux0 = aux0; s.aux1 = aux1; s.format = format;
     return alz_decode_batch(c, props, 1, src, src_len, &s, dst, dst_cap, result);
+}
+
+// ---------------------------------------------------------------- measure: decoded sizes without decoding (alz_measure.hip)
+// Grouped per format like a plan (one launch per format present, longest streams first inside a launch), on the context's stream; the
+// three tables live in the context's plan scratch.  No destination: dst_off is not looked at, dst_cap bounds the count.
+int alz_measure_batch_device(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                             const alz_stream* streams, alz_result* results) {
+    if (!c || (n && (!streams || !results || !d_src_base))) return fail(ALZ_E_INVALID, "alz_measure_batch: bad argument");
+    const alz_lz_properties lz = effective_lz(props);
+    uint32_t cnt[ALZ_FMT_COUNT] = {0}, off[ALZ_FMT_COUNT] = {0}, fill[ALZ_FMT_COUNT] = {0};
+    for (uint32_t i = 0; i < n; i++) {
+        if (streams[i].format >= ALZ_FMT_COUNT) return fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, streams[i].format);
+        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
+        cnt[streams[i].format]++;
+    }
+    if (cnt[ALZ_FMT_LZSS] && (lz.window_bits < 8 || lz.window_bits > 16 || lz.length_bits < 1 || lz.length_bits > 8))
+        return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path (window_bits 8..16, length_bits 1..8)");
+    c->last_kernel_ms = 0.f;
+    if (n == 0) return ALZ_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint32_t> index(n);
+    for (int f = 1; f < ALZ_FMT_COUNT; f++) off[f] = off[f - 1] + cnt[f - 1];
+    for (uint32_t i = 0; i < n; i++) { const uint32_t f = streams[i].format; index[off[f] + fill[f]++] = i; }
+    for (int f = 0; f < ALZ_FMT_COUNT; f++)     // a stream's cost is its tokens: the compressed bytes
+        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
+    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
+    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
+    alz_stream* d_streams = (alz_stream*)c->d_plan;
+    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
+    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
+    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    for (int f = 0; f < ALZ_FMT_COUNT && e == hipSuccess; f++)
+        if (cnt[f]) e = alz_launch_measure(f, c->stream, d_src_base, d_streams, d_index + off[f], cnt[f], d_results, &lz, c->exact);
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "alz_measure_batch failed: %s", hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+
+int alz_measure_batch(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                      const alz_stream* streams, alz_result* results) {
+    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base)) return fail(ALZ_E_INVALID, "alz_measure_batch: bad argument");
+    for (uint32_t i = 0; i < n; i++)
+        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
+    return alz_measure_batch_device(c, props, n, (const uint8_t*)c->d_src, src_bytes, streams, results);
 }
 
 // Device buffers of one encode call, freed on every exit path

@@ -54,9 +54,27 @@ def _context():
     return _ctx
 
 
+def _raise_for_outcome(rc, status, dst_len):
+    """rc / status of a container call as the reference's exception types"""
+    if rc == A.E_FORMAT:
+        raise InvalidIdentifierException()
+    if rc == A.E_CHECKSUM:
+        raise InvalidDataException("Checksum mismatch")
+    if rc == A.E_STREAM:
+        if status == A.ST_INPUT_TRUNCATED:
+            raise EndOfStreamException()
+        if status == A.ST_OUTPUT_SIZE_MISMATCH:
+            raise DecompressedSizeException(dst_len)
+        if status == A.ST_OUTPUT_CAPACITY:
+            raise BufferError("destination too small")    # NotSupportedException of a fixed-size stream
+        raise ValueError("bad token")
+    check(rc)
+
+
 class _Format:
     container = None
     provides_size = True
+    first_guess_failures = (BufferError,)     # what Decompress without a capacity raises when its first guess was too small
 
     def __init__(self):
         self.FormatByteOrder = "Big"      # IEndianDependentFormat.FormatByteOrder default (Yaz0.cs:30, PRS.cs:24)
@@ -101,28 +119,22 @@ class _Format:
 
     def Decompress(self, data, capacity=None):
         """ICompressionDecoder.Decompress: returns the decompressed bytes; raises the reference's exception types.
-        Formats without a size field grow the destination until it fits (a managed Stream grows by itself)."""
+        Formats without a size field start from a guess (a managed Stream grows by itself); when it does not hold the size is measured."""
         data = bytes(data)
         if capacity is None and not self.provides_size:
             hint = self._capacity_hint(data)
-            if hint is not None:
-                try:
-                    return self.Decompress(data, hint)
-                except BufferError:
-                    pass                                   # (a frame whose blocks decode to more than their nominal size: grow as for any other)
-                except MemoryError:
-                    pass                                   # (a hint the host or the device cannot back: the growing loop)
-                except AlzError as e:
-                    if e.code != A.E_NOMEM:
-                        raise
-            cap = max(len(data) * 8, 1 << 16)
-            while True:
-                try:
-                    return self.Decompress(data, cap)
-                except BufferError:
-                    if cap >= 1 << 31:
-                        raise
-                    cap *= 4
+            try:
+                return self.Decompress(data, hint if hint is not None else max(len(data) * 8, 1 << 16))
+            except self.first_guess_failures:
+                pass                                       # (more than the guess: a frame whose blocks decode to more than their nominal size, a long run)
+            except MemoryError:
+                pass                                       # (a hint the host or the device cannot back: the measured size is what the file needs)
+            except AlzError as e:
+                if e.code != A.E_NOMEM:
+                    raise
+            # the first guess did not hold: ONE size query on the GPU, then a decode into exactly that much (at most two decodes, and never a
+            # destination larger than the file needs)
+            return self.Decompress(data, self.MeasureDecompressedSize(data))
         if capacity is None and getattr(self, "size_either_order", False):
             # Yaz0.Decompress retries with the size field byte-swapped (Yaz0.cs:66-78) into a stream that grows by itself: the
             # capacity is the reading in FormatByteOrder unless that one is absurd, the other reading when it was not enough
@@ -144,21 +156,22 @@ class _Format:
         lib = load()
         lib.alz_container_decompress.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         rc = lib.alz_container_decompress(_context().h, self.container, C.byref(o), data, len(data), dst, capacity, C.byref(dl), C.byref(su), C.byref(st))
-        if rc == A.E_FORMAT:
-            raise InvalidIdentifierException()
-        if rc == A.E_CHECKSUM:
-            raise InvalidDataException("Checksum mismatch")
-        if rc == A.E_STREAM:
-            if st.value == A.ST_INPUT_TRUNCATED:
-                raise EndOfStreamException()
-            if st.value == A.ST_OUTPUT_SIZE_MISMATCH:
-                raise DecompressedSizeException(dl.value)
-            if st.value == A.ST_OUTPUT_CAPACITY:
-                raise BufferError("destination too small")    # NotSupportedException of a fixed-size stream
-            raise ValueError("bad token")
-        check(rc)
+        _raise_for_outcome(rc, st.value, dl.value)
         self.last_src_used = su.value
         return dst_arr[:dl.value].tobytes()
+
+    def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
+        """The decompressed size of a file of a format WITHOUT a size field (PRS, LZO, FastLZ, LZ4, LZ4Legacy, Snappy), measured on the GPU
+        without decoding (alz_container_measure).  Raises what Decompress raises for truncated / bad input, and BufferError when the file decodes
+        to more than `limit` bytes (a bound against decompression bombs; the default is the largest size the library counts to)."""
+        if self.provides_size:
+            raise NotImplementedError("%s states its size: GetDecompressedSize" % type(self).__name__)
+        data = bytes(data)
+        o = self._opt()
+        size, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
+        rc = load().alz_container_measure(_context().h, self.container, C.byref(o), data, len(data), limit, C.byref(size), C.byref(su), C.byref(st))
+        _raise_for_outcome(rc, st.value, size.value)
+        return size.value
 
     def Compress(self, data, settings=None):
         data = bytes(data)
@@ -209,6 +222,17 @@ class MIO0(_Format):
 
 class PRS(_Format):
     container, provides_size = A.C_PRS, False
+    # PRS.Decompress reads a file that failed again in the other byte order (PRS.cs:42-57), so a destination that was too small surfaces as
+    # whatever the OTHER order ends in; the size query that follows has no bound and raises what the file itself deserves
+    first_guess_failures = (BufferError, EndOfStreamException, DecompressedSizeException, ValueError)
+
+    def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
+        # PRS.Decompress reads a file that failed again in the other byte order (PRS.cs:42-57), and "the limit was reached" is such a failure: the
+        # size is counted without a bound (counting allocates nothing) and held against the limit here
+        size = super().MeasureDecompressedSize(data)
+        if size > limit:
+            raise BufferError("destination too small")
+        return size
 
 
 class LZO(_Format):

@@ -283,6 +283,24 @@ int alz_decode(alz_ctx* ctx, uint32_t format, const alz_lz_properties* props,
                const uint8_t* src, uint32_t src_len, uint32_t decom_len, uint32_t aux0, uint32_t aux1,
                uint8_t* dst, uint32_t dst_cap, alz_result* result);
 
+/* ---------------------------------------- measure: decoded sizes without decoding
+ * PRS, LZ4 blocks, LZO, FastLZ, WFLZ and raw Snappy carry no size a caller could read before the call, and every batch entry
+ * point wants dst_off / dst_cap for every stream first.  The measure kernels walk a stream's tokens as the decoder does and
+ * count: results[i] is what alz_decode_batch would return for streams[i] -- status, dst_len, and src_used wherever it is
+ * defined (every status but OUTPUT_CAPACITY) -- for all formats.  dst_off is ignored, no destination exists, nothing is written
+ * on the device but the results.  dst_cap only bounds the count: pass 0xFFFFFF00 for "the size", or a limit of your own to have a
+ * stream that decodes to more end in ALZ_ST_OUTPUT_CAPACITY (dst_len = that limit).  An LZ4 block with history (aux0) counts like one
+ * without (E2: bytes in front of a stream are zeros at worst, never an error), so the blocks of a linked frame can be measured
+ * as one batch.  Two passes then lay a batch out exactly: sizes, exclusive prefix sum, alz_plan_create + execute.
+ * alz_ctx_set_exact_kernels selects the family (the counting sink under the exact parsers alone / lane-parallel parse rounds
+ * for the bulk of the size-less bodies); alz_last_kernel_ms reports the device time of the call's launches. */
+int alz_measure_batch(alz_ctx* ctx, const alz_lz_properties* props, uint32_t n,
+                      const uint8_t* src_base, size_t src_bytes, const alz_stream* streams, alz_result* results);
+/* the same on a source that is already in HBM: d_src_base is a DEVICE pointer (typed as the bytes the offsets count, like src_base
+ * above; 64 readable bytes behind the last stream, as for the plans below); results come back to the host */
+int alz_measure_batch_device(alz_ctx* ctx, const alz_lz_properties* props, uint32_t n,
+                             const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results);
+
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's
  * [dst_off, dst_off + dst_len) (tests/test_gpu_canary.py); they READ the input in aligned 16-byte granules and, for the 64 KiB
@@ -465,6 +483,17 @@ int alz_container_is_match(uint32_t container, const uint8_t* src, size_t src_le
 int alz_container_decompress(alz_ctx* ctx, uint32_t container, const alz_container_options* opt,
                              const uint8_t* src, size_t src_len,
                              uint8_t* dst, size_t dst_cap, size_t* dst_len, size_t* src_used, int32_t* status);
+/* Decompressed size of a file of a container WITHOUT a size field -- PRS, LZO, FASTLZ, LZ4_FRAME, LZ4_LEGACY, SNAPPY -- by
+ * measuring its bodies on the GPU (alz_measure_batch: all blocks / chunks of the file as one batch, linked LZ4 blocks included).
+ * The outcome is that of reading the file in order into a destination of size_limit bytes: rc, *status, *size_out (what
+ * *dst_len would be) and *src_used -- with an LZ4 frame's CONTENT checksum taken as correct (it needs the bytes; block checksums
+ * cover stored bytes and are verified), and a framed Snappy chunk whose body ends short of its declared length read on from
+ * where the body stopped, as the managed reader does (alz_container_decompress refuses such a chunk with ALZ_E_FORMAT).
+ * A size_limit below the true size gives ALZ_E_STREAM / ALZ_ST_OUTPUT_CAPACITY.  Other containers: ALZ_E_UNSUPPORTED (they
+ * have alz_container_decompressed_size). */
+int alz_container_measure(alz_ctx* ctx, uint32_t container, const alz_container_options* opt,
+                          const uint8_t* src, size_t src_len, size_t size_limit,
+                          size_t* size_out, size_t* src_used, int32_t* status);
 /* ICompressionEncoder.Compress(ReadOnlySpan<byte>, Stream, CompressionSettings) */
 int alz_container_compress(alz_ctx* ctx, uint32_t container, const alz_container_options* opt,
                            const alz_settings* settings,

@@ -34,7 +34,7 @@ namespace AuroraLib.Compression.Amd
         /// alz_decode, the output is written to <paramref name="destination"/> (partial output too, as the managed bodies leave
         /// it), <c>source.Position</c> ends just past the consumed bytes (Yay0.cs:89-90, MIO0.cs:92-93, LZSS.cs:68) and the
         /// status becomes the managed exception.  <paramref name="capacity"/>: bytes the body may produce (declared size plus the
-        /// longest token for bodies that may overshoot it; a guess that is doubled on OUTPUT_CAPACITY for bodies without a size).
+        /// longest token for bodies that may overshoot it; a first guess for bodies without a size: on OUTPUT_CAPACITY the size is measured once).
         /// </summary>
         internal static void Decode(AlzFormat format, AlzLzProperties* props, Stream source, Stream destination, uint decomLength,
                                     uint aux0, uint aux1, uint capacity, bool hasSize)
@@ -50,6 +50,7 @@ namespace AuroraLib.Compression.Amd
                                           uint decomLength, uint aux0, uint aux1, uint capacity, bool hasSize)
         {
             {
+                bool measured = false;
                 for (;;)
                 {
                     byte[] dst = ArrayPool<byte>.Shared.Rent((int)Math.Min(capacity, int.MaxValue - 64));
@@ -60,9 +61,18 @@ namespace AuroraLib.Compression.Amd
                             fixed (byte* ps = src, pd = dst)
                                 AmdContext.Check(Native.alz_decode(AmdContext.Handle, (uint)format, props, ps, (uint)srcLen, decomLength, aux0, aux1,
                                                                    pd, (uint)Math.Min(capacity, (uint)dst.Length), &r));
-                        if (!hasSize && r.Status == (int)AlzStatus.OutputCapacity && capacity < 0x7FFF0000u)
+                        if (!hasSize && r.Status == (int)AlzStatus.OutputCapacity && !measured && capacity < 0x7FFF0000u)
                         {
-                            capacity = capacity < 0x3FFF0000u ? capacity * 2 : 0x7FFF0000u;    // a managed destination Stream simply grows
+                            // a managed destination Stream simply grows; here the size is measured ONCE on the GPU (no bytes decoded) and the
+                            // second decode rents exactly that much
+                            AlzStream st = new AlzStream { SrcOff = 0, DstOff = 0, SrcLen = (uint)srcLen, DstCap = 0x7FFF0000u, DecomLen = decomLength,
+                                                           Aux0 = aux0, Aux1 = aux1, Format = (uint)format };
+                            AlzResult m;
+                            lock (AmdContext.Lock)
+                                fixed (byte* ps = src)
+                                    AmdContext.Check(Native.alz_measure_batch(AmdContext.Handle, props, 1, ps, (UIntPtr)(uint)srcLen, &st, &m));
+                            measured = true;
+                            capacity = Math.Max(m.DstLen, 1u);
                             continue;
                         }
                         destination.Write(dst, 0, (int)r.DstLen);

@@ -97,6 +97,18 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib)] internal static extern int alz_decode_batch(IntPtr ctx, AlzLzProperties* props, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
 
+        // decoded sizes without decoding: results[i] is what alz_decode_batch would return for streams[i]; dst_off is ignored, dst_cap bounds the count
+        [DllImport(Lib)] internal static extern int alz_measure_batch(IntPtr ctx, AlzLzProperties* props, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
+
+        // ... on a source that is already in HBM (dSrcBase is a device pointer)
+        [DllImport(Lib)] internal static extern int alz_measure_batch_device(IntPtr ctx, AlzLzProperties* props, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
+
+        // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
+        [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
+            byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
+
         // the same batch over several contexts (one per GPU), partitioned by the library
         [DllImport(Lib)] internal static extern int alz_decode_batch_multi(IntPtr* ctxs, uint nCtx, AlzLzProperties* props, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results, uint* partOfOut);
