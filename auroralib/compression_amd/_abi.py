@@ -30,9 +30,19 @@ C_REFPACK = 40
 C_WFLZ = 41
 C_LZSHREK = 42
 C_HIG = 43
-C_COUNT = 44
+C_RLE30 = 44
+C_HUF20 = 45
+C_COUNT = 46
 LZ77_LZ10, LZ77_LZ11, LZ77_CHUNKLZ10 = 0x10, 0x11, 0xF7
+LZ77_HUF20_4, LZ77_HUF20_8, LZ77_RLE30 = 0x24, 0x28, 0x30
 LEVEL5_ONLYSAVE, LEVEL5_LZ10 = 0, 1
+LEVEL5_HUFFMAN4, LEVEL5_HUFFMAN8, LEVEL5_RLE = 2, 3, 4
+
+# alz_rlh_format: the non-LZ bodies of the GBA / DS family (an entry-point family of their own, not alz_format values)
+RLH_RLE30, RLH_HUF20_4, RLH_HUF20_8 = range(3)
+RLH_COUNT = 3
+RLH_NAMES = ["rle30", "huf20_4", "huf20_8"]
+HUF20_MAX_DECOM = 0x10000000           # decom_len from here on is refused (the managed int symbol count overflows)
 
 
 class LzProperties(C.Structure):
@@ -77,5 +87,9 @@ MEASURE_PROTOTYPES = {
     "alz_measure_batch_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
     "alz_container_measure": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)],
 }
+
+# the RLE30 / HUF20 entry points: (ctx, n, src_base, src_bytes, streams, dst_base, dst_bytes, results)
+RLH_PROTOTYPES = {name: [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+                  for name in ("alz_rlh_decode_batch", "alz_rlh_decode_batch_device", "alz_rlh_encode_batch", "alz_rlh_encode_batch_device")}
 
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16

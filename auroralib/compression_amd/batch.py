@@ -119,6 +119,35 @@ class Context:
         check(self.lib.alz_measure_batch_device(self.h, C.byref(lz) if lz is not None else None, n, d_src, src_bytes, streams, res))
         return res
 
+    # ---- RLE30 / HUF20: the non-LZ bodies of the GBA / DS family (streams[i].format is an A.RLH_* value)
+    def _rlh_host(self, fn, streams, src, dst_bytes):
+        n = len(streams)
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
+        res = (A.Result * n)()
+        check(fn(self.h, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def rlh_decode_batch(self, streams, src, dst_bytes):
+        """alz_rlh_decode_batch on host buffers: RLE30 / HUF20 bodies; aux0 of a HUF20_4 stream is the nibble order (1 = big, Level5)."""
+        return self._rlh_host(self.lib.alz_rlh_decode_batch, streams, src, dst_bytes)
+
+    def rlh_encode_batch(self, streams, src, dst_bytes):
+        """alz_rlh_encode_batch: RLE30.CompressHeaderless of raw buffers (a HUF format raises AlzError E_UNSUPPORTED: there is no encoder)."""
+        return self._rlh_host(self.lib.alz_rlh_encode_batch, streams, src, dst_bytes)
+
+    def rlh_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_rlh_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
+        res = (A.Result * len(streams))()
+        check(self.lib.alz_rlh_decode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
+        return res
+
+    def rlh_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_rlh_encode_batch_device: raw buffers in HBM at d_src, RLE30 streams left at d_dst."""
+        res = (A.Result * len(streams))()
+        check(self.lib.alz_rlh_encode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
+        return res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

@@ -15,6 +15,12 @@
 
 #include "auroralz.h"
 
+// The RLE30 / HUF20 entry points are referenced WEAKLY from here: the sanitized fuzz binary of these header parsers (oracle/Makefile,
+// fuzz_container) links this file alone against its own stand-ins for the GPU side of the ABI and has none for this family; there the two
+// helpers below answer ALZ_E_NO_DEVICE as those stand-ins do.  In libauroralz.so the definitions of alz_host.cpp are bound.
+#pragma weak alz_rlh_decode_batch
+#pragma weak alz_rlh_encode_batch
+
 namespace {
 
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -108,6 +114,27 @@ uint32_t clamp32(size_t v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)
 int run_body(alz_ctx* ctx, uint32_t fmt, const alz_lz_properties* lz, const uint8_t* body, size_t body_len, uint32_t size,
              uint32_t aux0, uint32_t aux1, uint8_t* dst, size_t cap, alz_result* r) {
     return alz_decode(ctx, fmt, lz, body, clamp32(body_len), size, aux0, aux1, dst, clamp32(cap), r);
+}
+// the same for the non-LZ bodies of the GBA / DS family (fmt: alz_rlh_format; nibble_big: HUF20's Endian.Big, Level5 only)
+int run_rlh(alz_ctx* ctx, uint32_t fmt, uint32_t nibble_big, const uint8_t* body, size_t body_len, uint32_t size, uint8_t* dst, size_t cap, alz_result* r) {
+    if (!alz_rlh_decode_batch) return ALZ_E_NO_DEVICE;
+    alz_stream s; memset(&s, 0, sizeof(s));
+    s.src_len = clamp32(body_len); s.dst_cap = clamp32(cap); s.decom_len = size; s.aux0 = nibble_big; s.format = fmt;
+    return alz_rlh_decode_batch(ctx, 1, body, body_len, &s, dst, cap, r);
+}
+// RLE30.CompressHeaderless of one buffer behind `hdr` header bytes the caller writes
+int rlh_compress_body(alz_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t hdr, size_t* dst_len) {
+    if (!alz_rlh_encode_batch) return ALZ_E_NO_DEVICE;
+    if (cap < hdr) return ALZ_E_NOMEM;
+    alz_stream s; memset(&s, 0, sizeof(s));
+    s.src_len = clamp32(n); s.dst_cap = clamp32(cap - hdr); s.format = ALZ_RLH_RLE30;
+    alz_result r;
+    const int rc = alz_rlh_encode_batch(ctx, 1, src, n, &s, dst + hdr, cap - hdr, &r);
+    if (rc != ALZ_OK) return rc;
+    if (r.status == ALZ_ST_OUTPUT_CAPACITY) return ALZ_E_NOMEM;
+    if (r.status != ALZ_ST_OK) return ALZ_E_INVALID;
+    if (dst_len) *dst_len = hdr + r.dst_len;
+    return ALZ_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- checksums (host side)
@@ -658,6 +685,8 @@ int alz_container_decompressed_size(uint32_t container, const alz_container_opti
     case ALZ_C_LZ10: return nin_header(src, len, 0x10, size_out) < 0 ? ALZ_E_FORMAT : ALZ_OK;                                  // LZ10.cs:44-57
     case ALZ_C_LZ11: return nin_header(src, len, 0x11, size_out) < 0 ? ALZ_E_FORMAT : ALZ_OK;                                  // LZ11.cs:40-53
     case ALZ_C_LZ40: return nin_header(src, len, 0x40, size_out) < 0 ? ALZ_E_FORMAT : ALZ_OK;                                  // LZ40.cs:40-52
+    case ALZ_C_RLE30: return nin_header(src, len, 0x30, size_out) < 0 ? ALZ_E_FORMAT : ALZ_OK;                                 // RLE30.cs:40-50
+    case ALZ_C_HUF20: return (len < 1 || (src[0] != 0x24 && src[0] != 0x28) || nin_header(src, len, src[0], size_out) < 0) ? ALZ_E_FORMAT : ALZ_OK;   // HUF20.cs:57-67
     case ALZ_C_LZHUDSON: if (len < 4) return ALZ_E_FORMAT; *size_out = be32(src); return ALZ_OK;                                        // LZHudson.cs:30-31
     case ALZ_C_LZ00: if (len < 52 || memcmp(src, "LZ00", 4)) return ALZ_E_FORMAT; *size_out = le32(src + 48); return ALZ_OK;               // LZ00.cs:31-37
     case ALZ_C_CNX2: if (len < 16 || memcmp(src, "CNX\x02", 4)) return ALZ_E_FORMAT; *size_out = be32(src + 12); return ALZ_OK;             // CNX2.cs:36-42
@@ -747,6 +776,16 @@ int alz_container_is_match(uint32_t container, const uint8_t* src, size_t len) {
     case ALZ_C_LZON: return len > 0x10 && !memcmp(src, kLzonMagic, 8);
     case ALZ_C_LZ40: case ALZ_C_LZ60:                                                       // "no distinct header, recognition is inaccurate"  LZ40.cs:36-38
         return len > 0x8 && src[0] == (container == ALZ_C_LZ40 ? 0x40 : 0x60) && ((src[1] | src[2] | src[3]) != 0 || le32(src + 4) != 0);
+    case ALZ_C_RLE30: {                                                                     // RLE30.cs:33-34 (a read past the end throws: no match)
+        if (len < 6 || src[0] != 0x30) return 0;
+        if ((src[1] | src[2] | src[3]) != 0) return src[4] != 0;
+        return len >= 9 && le32(src + 4) != 0 && src[8] != 0;
+    }
+    case ALZ_C_HUF20: {                                                                     // HUF20.cs:50-51 (ReadByte() at the end gives -1, which is not 0)
+        if (len <= 6 || (src[0] != 0x24 && src[0] != 0x28)) return 0;
+        if ((src[1] | src[2] | src[3]) != 0) return src[4] != 0;
+        return len >= 8 && le32(src + 4) != 0 && (len == 8 || src[8] != 0);
+    }
     case ALZ_C_LZHUDSON: return len > 0x8 && le32(src) != 0;                                // (+ the file extension when one is given)  LZHudson.cs:27-28
     case ALZ_C_SMSR00: return len > 0x10 && !memcmp(src, "SMSR00", 6);                      // SMSR00.cs:30-31
     case ALZ_C_LZ00: return len > 0x40 && !memcmp(src, "LZ00", 4);                           // LZ00.cs:36-37
@@ -969,6 +1008,21 @@ int alz_container_decompress(alz_ctx* ctx, uint32_t container, const alz_contain
         rc = run_body(ctx, ALZ_FMT_LZSS, nullptr, plain.data(), plain.size(), size, 0, 0, dst, dst_cap, &r);
         break;
     }
+    case ALZ_C_RLE30: {                                                                     // RLE30.cs:53-57
+        int h = nin_header(src, len, 0x30, &size);
+        if (h < 0) return ALZ_E_FORMAT;
+        hdr = (size_t)h;
+        rc = run_rlh(ctx, ALZ_RLH_RLE30, 0, src + hdr, len - hdr, size, dst, dst_cap, &r);
+        break;
+    }
+    case ALZ_C_HUF20: {                                                                     // HUF20.cs:70-74: bitDepth = type - 0x20, Endian.Little
+        if (len < 1 || (src[0] != 0x24 && src[0] != 0x28)) return ALZ_E_FORMAT;
+        int h = nin_header(src, len, src[0], &size);
+        if (h < 0) return ALZ_E_FORMAT;
+        hdr = (size_t)h;
+        rc = run_rlh(ctx, src[0] == 0x24 ? ALZ_RLH_HUF20_4 : ALZ_RLH_HUF20_8, 0, src + hdr, len - hdr, size, dst, dst_cap, &r);
+        break;
+    }
     case ALZ_C_LZ40: case ALZ_C_LZ60: {                                                     // LZ40.cs:54-61, LZ60.cs:43-47
         int h = nin_header(src, len, container == ALZ_C_LZ40 ? 0x40 : 0x60, &size);
         if (h < 0) return ALZ_E_FORMAT;
@@ -1029,7 +1083,10 @@ int alz_container_decompress(alz_ctx* ctx, uint32_t container, const alz_contain
             if (dst_cap < size) { r.status = ALZ_ST_OUTPUT_CAPACITY; break; }
             memcpy(dst, src + hdr, size); r.dst_len = size; r.src_used = size; r.status = ALZ_ST_OK;
         } else if ((ts & 7) == ALZ_LEVEL5_LZ10) rc = run_body(ctx, ALZ_FMT_LZ10, nullptr, src + hdr, len - hdr, size, 0, 0, dst, dst_cap, &r);
-        else return ALZ_E_UNSUPPORTED;                                                      // RLE / Huffman: not LZ
+        else if ((ts & 7) == ALZ_LEVEL5_RLE) rc = run_rlh(ctx, ALZ_RLH_RLE30, 0, src + hdr, len - hdr, size, dst, dst_cap, &r);               // Level5.cs:97-99
+        else if ((ts & 7) == ALZ_LEVEL5_HUFFMAN4) rc = run_rlh(ctx, ALZ_RLH_HUF20_4, 1, src + hdr, len - hdr, size, dst, dst_cap, &r);         // Endian.Big  :100-102
+        else if ((ts & 7) == ALZ_LEVEL5_HUFFMAN8) rc = run_rlh(ctx, ALZ_RLH_HUF20_8, 1, src + hdr, len - hdr, size, dst, dst_cap, &r);         // :103-105
+        else return ALZ_E_UNSUPPORTED;                                                      // NotSupportedException  :106-107
         break;
     }
     case ALZ_C_LZ77: {                                                                      // LZ77.cs:105-153
@@ -1041,7 +1098,12 @@ int alz_container_decompress(alz_ctx* ctx, uint32_t container, const alz_contain
             rc = run_body(ctx, type == ALZ_LZ77_LZ10 ? ALZ_FMT_LZ10 : ALZ_FMT_LZ11, nullptr, src + hdr, len - hdr, size, 0, 0, dst, dst_cap, &r);
             break;
         }
-        if (type != ALZ_LZ77_CHUNKLZ10) return ALZ_E_UNSUPPORTED;                            // RLE30 / HUF20: not LZ
+        if (type == ALZ_LZ77_RLE30) { rc = run_rlh(ctx, ALZ_RLH_RLE30, 0, src + hdr, len - hdr, size, dst, dst_cap, &r); break; }   // LZ77.cs:128-130
+        if (type == ALZ_LZ77_HUF20_4 || type == ALZ_LZ77_HUF20_8) {                          // bitDepth = type - 0x20, Endian.Little  LZ77.cs:124-127
+            rc = run_rlh(ctx, type == ALZ_LZ77_HUF20_4 ? ALZ_RLH_HUF20_4 : ALZ_RLH_HUF20_8, 0, src + hdr, len - hdr, size, dst, dst_cap, &r);
+            break;
+        }
+        if (type != ALZ_LZ77_CHUNKLZ10) return ALZ_E_UNSUPPORTED;
         // ChunkLZ10: u16 end offsets until (last + position == length), then one LZ10 FILE per chunk.  The chunks are
         // independent streams: they go to the GPU as ONE batch.
         std::vector<uint32_t> ends; size_t pos = hdr;
@@ -1093,6 +1155,12 @@ size_t alz_container_compress_bound(uint32_t container, size_t n) {
 // ICompressionEncoder.Compress(ReadOnlySpan<byte>, Stream, CompressionSettings)  Interfaces/ICompressionEncoder.cs:19
 int alz_container_compress(alz_ctx* ctx, uint32_t container, const alz_container_options* opt, const alz_settings* settings,
                            const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* dst_len) {
+    {   // HUF20 has no encoder: the managed output is not a function of the input (include/auroralz.h, alz_rlh_format).  Level5's "quality 0 -> OnlySave" comes first (Level5.cs:120-121).
+        const uint32_t v = opt ? opt->variant : 0u;
+        if (container == ALZ_C_HUF20 || (container == ALZ_C_LZ77 && (v == ALZ_LZ77_HUF20_4 || v == ALZ_LZ77_HUF20_8)) ||
+            (container == ALZ_C_LEVEL5 && (v == ALZ_LEVEL5_HUFFMAN4 || v == ALZ_LEVEL5_HUFFMAN8) && !(settings && settings->quality == 0)))
+            return ALZ_E_UNSUPPORTED;
+    }
     if (!ctx || (!src && n) || !dst) return ALZ_E_INVALID;
     const bool big = opt ? opt->big_endian != 0 : true;
     const alz_lz_properties* lz = opt ? &opt->lz : nullptr;
@@ -1147,6 +1215,12 @@ int alz_container_compress(alz_ctx* ctx, uint32_t container, const alz_container
         if (type == ALZ_LZ77_LZ10 || type == ALZ_LZ77_LZ11 || (type == ALZ_LZ77_CHUNKLZ10 && chunk >= n)) {
             size_t inner = 0;
             int rc2 = alz_container_compress(ctx, type == ALZ_LZ77_LZ11 ? ALZ_C_LZ11 : ALZ_C_LZ10, opt, settings, src, n, dst + 4, cap - 4, &inner);
+            if (dst_len) *dst_len = 4 + inner;
+            return rc2;
+        }
+        if (type == ALZ_LZ77_RLE30) {                                                        // new RLE30().Compress  LZ77.cs:65, :103
+            size_t inner = 0;
+            int rc2 = alz_container_compress(ctx, ALZ_C_RLE30, opt, settings, src, n, dst + 4, cap - 4, &inner);
             if (dst_len) *dst_len = 4 + inner;
             return rc2;
         }
@@ -1209,8 +1283,15 @@ int alz_container_compress(alz_ctx* ctx, uint32_t container, const alz_container
         if (cap < 4) return ALZ_E_NOMEM;
         wr32(dst, type | ((uint32_t)n << 3), false);
         if (type == ALZ_LEVEL5_ONLYSAVE) { if (cap < 4 + n) return ALZ_E_NOMEM; memcpy(dst + 4, src, n); if (dst_len) *dst_len = 4 + n; return ALZ_OK; }
+        if (type == ALZ_LEVEL5_RLE) return rlh_compress_body(ctx, src, n, dst, cap, 4, dst_len);   // RLE30.CompressHeaderless  Level5.cs:137-139
         if (type != ALZ_LEVEL5_LZ10) return ALZ_E_UNSUPPORTED;
         break;
+    }
+    case ALZ_C_RLE30: {                                                                     // RLE30.cs:60-74
+        const size_t h = n <= 0xFFFFFF ? 4 : 8;
+        if (cap < h) return ALZ_E_NOMEM;
+        if (n <= 0xFFFFFF) wr32(dst, 0x30u | ((uint32_t)n << 8), false); else { wr32(dst, 0x30u, false); wr32(dst + 4, (uint32_t)n, false); }
+        return rlh_compress_body(ctx, src, n, dst, cap, h, dst_len);
     }
     default: break;
     }

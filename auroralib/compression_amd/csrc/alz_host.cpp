@@ -19,6 +19,7 @@
 
 #include "alz_internal.h"
 #include "alz_measure.h"
+#include "alz_rlh.h"
 
 static thread_local char g_err[512] = "";
 
@@ -966,6 +967,98 @@ int alz_measure_batch(alz_ctx* c, const alz_lz_properties* props, uint32_t n, co
     if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
     if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
     return alz_measure_batch_device(c, props, n, (const uint8_t*)c->d_src, src_bytes, streams, results);
+}
+
+// ---------------------------------------------------------------- RLE30 / HUF20: the non-LZ bodies of the GBA / DS family (alz_rlh.hip)
+// An entry-point family of its own, shaped like measure: grouped per alz_rlh_format (one launch per format present, longest
+// streams first), on the context's stream, tables in the context's plan scratch, results to the host.
+// what a call is refused for, before anything is allocated or copied
+static int rlh_validate(bool encode, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes) {
+    const char* what = encode ? "alz_rlh_encode_batch" : "alz_rlh_decode_batch";
+    for (uint32_t i = 0; i < n; i++) {
+        const alz_stream& s = streams[i];
+        if (s.format >= ALZ_RLH_COUNT) return fail(ALZ_E_INVALID, "%s: stream %u: unknown alz_rlh_format %u", what, i, s.format);
+        if (!range_ok(s.src_off, s.src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: source range exceeds src_bytes", what, i);
+        if (!range_ok(s.dst_off, s.dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: destination range exceeds dst_bytes", what, i);
+        if (s.format != ALZ_RLH_RLE30) {
+            // HuffmanTree.CreateTree sorts equal frequencies with the unstable List.Sort(): the managed bytes are not a function of the input
+            if (encode) return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: HUF20 has no encoder (the managed output is not a function of its input)", what, i);
+            if (s.decom_len >= 0x10000000u)   // symbolsToDecompress = destination.Length * 8 / bitDepth overflows the managed int  HUF20.cs:117
+                return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: HUF20 decom_len >= 0x10000000", what, i);
+        }
+    }
+    return ALZ_OK;
+}
+
+static int rlh_core(alz_ctx* c, bool encode, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                    uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    const char* what = encode ? "alz_rlh_encode_batch" : "alz_rlh_decode_batch";
+    uint32_t cnt[ALZ_RLH_COUNT] = {0}, off[ALZ_RLH_COUNT] = {0}, fill[ALZ_RLH_COUNT] = {0};
+    if (int rc = rlh_validate(encode, n, src_bytes, streams, dst_bytes)) return rc;
+    for (uint32_t i = 0; i < n; i++) cnt[streams[i].format]++;
+    c->last_kernel_ms = 0.f;
+    if (n == 0) return ALZ_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint32_t> index(n);
+    for (int f = 1; f < ALZ_RLH_COUNT; f++) off[f] = off[f - 1] + cnt[f - 1];
+    for (uint32_t i = 0; i < n; i++) { const uint32_t f = streams[i].format; index[off[f] + fill[f]++] = i; }
+    for (int f = 0; f < ALZ_RLH_COUNT; f++)
+        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
+    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
+    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
+    alz_stream* d_streams = (alz_stream*)c->d_plan;
+    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
+    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
+    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    for (int f = 0; f < ALZ_RLH_COUNT && e == hipSuccess; f++) {
+        if (!cnt[f]) continue;
+        e = encode ? alz_launch_rlh_encode(f, c->stream, d_src_base, d_dst_base, d_streams, d_index + off[f], cnt[f], d_results, c->exact)
+                   : alz_launch_rlh_decode(f, c->stream, d_src_base, d_dst_base, d_streams, d_index + off[f], cnt[f], d_results, c->exact);
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+
+static int rlh_host(alz_ctx* c, bool encode, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                    uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return fail(ALZ_E_INVALID, "alz_rlh_%s_batch: bad argument", encode ? "encode" : "decode");
+    if (n == 0) return ALZ_OK;
+    int rc;
+    if ((rc = rlh_validate(encode, n, src_bytes, streams, dst_bytes))) return rc;   // (first, as alz_decode_batch: a refused call pays for no upload)
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
+    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
+    if ((rc = rlh_core(c, encode, n, (const uint8_t*)c->d_src, src_bytes, streams, (uint8_t*)c->d_dst, dst_bytes, results))) return rc;
+    return download_outputs(c, n, streams, results, dst_base, encode);   // decode: what each stream produced, whatever its status (as alz_decode_batch)
+}
+
+int alz_rlh_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                         uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return rlh_host(c, false, n, src_base, src_bytes, streams, dst_base, dst_bytes, results);
+}
+int alz_rlh_encode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                         uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return rlh_host(c, true, n, src_base, src_bytes, streams, dst_base, dst_bytes, results);
+}
+int alz_rlh_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_rlh_decode_batch_device: bad argument");
+    return rlh_core(c, false, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
+}
+int alz_rlh_encode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_rlh_encode_batch_device: bad argument");
+    return rlh_core(c, true, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
 }
 
 // Device buffers of one encode call, freed on every exit path

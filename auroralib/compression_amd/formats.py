@@ -471,16 +471,60 @@ class SDPC(_Format):
     container = A.C_SDPC
 
 
-class LZ77(_Format):
-    """src/AuroraLib.Compression.Nintendo/Nintendo/LZ77.cs -- Type: LZ10 (default) / LZ11 / ChunkLZ10."""
+HUF20_NO_ENCODER = ("HUF20 has no encoder here: the managed output is not a function of the input -- HuffmanTree.CreateTree orders equal frequencies "
+                    "with the unstable List.Sort(), and the 4-bit path indexes its table with un-shifted high nibbles (DESIGN.md 7)")
+
+
+class _NoHuffmanEncoder(_Format):
+    """Compress of a Huffman type raises NotImplementedError with the reason (the library answers ALZ_E_UNSUPPORTED)."""
+    huffman_types = ()
+
+    def _is_huffman(self, settings):
+        return self.Type in self.huffman_types
+
+    def Compress(self, data, settings=None):
+        if self._is_huffman(settings):
+            raise NotImplementedError(HUF20_NO_ENCODER)
+        return super().Compress(data, settings)
+
+
+class RLE30(_Format):
+    """src/AuroraLib.Compression.Nintendo/Nintendo/RLE30.cs -- 0x30 + size + run-length body (alz_rlh_*).  Compress keeps the managed
+    defect: a literal run of 129 bytes (127 literals followed by fewer than 3 bytes) does not decode back."""
+    container = A.C_RLE30
+
+
+class HUF20(_NoHuffmanEncoder):
+    """src/AuroraLib.Compression.Nintendo/Nintendo/HUF20.cs -- 0x24 / 0x28 + size + Huffman body (alz_rlh_*); decode only."""
+    container = A.C_HUF20
+    Huffman4bits, Huffman8bits = 0x24, 0x28
+
+    def __init__(self):
+        super().__init__()
+        self.Type = self.Huffman8bits                 # HUF20.cs:37
+
+    def _is_huffman(self, settings):
+        return True
+
+
+class LZ77(_NoHuffmanEncoder):
+    """src/AuroraLib.Compression.Nintendo/Nintendo/LZ77.cs -- Type: LZ10 (default) / LZ11 / ChunkLZ10 / RLE30 / HUF20_4bits / HUF20_8bits (decode only)."""
     container = A.C_LZ77
     LZ10, LZ11, ChunkLZ10 = A.LZ77_LZ10, A.LZ77_LZ11, A.LZ77_CHUNKLZ10
+    RLE30, HUF20_4bits, HUF20_8bits = A.LZ77_RLE30, A.LZ77_HUF20_4, A.LZ77_HUF20_8
+    huffman_types = (A.LZ77_HUF20_4, A.LZ77_HUF20_8)
 
 
-class Level5(_Format):
+class Level5(_NoHuffmanEncoder):
+    """src/AuroraLib.Compression.Nintendo/Level5/Level5.cs -- Type: OnlySave / LZ10 (default) / Huffman4Bit / Huffman8Bit (decode only) / RLE."""
     container = A.C_LEVEL5
     OnlySave, LZ10 = A.LEVEL5_ONLYSAVE, A.LEVEL5_LZ10
+    Huffman4Bit, Huffman8Bit, RLE = A.LEVEL5_HUFFMAN4, A.LEVEL5_HUFFMAN8, A.LEVEL5_RLE
+    huffman_types = (A.LEVEL5_HUFFMAN4, A.LEVEL5_HUFFMAN8)
+
+    def _is_huffman(self, settings):
+        return self.Type in self.huffman_types and not (settings is not None and settings.Quality == 0)   # quality 0 -> OnlySave first  Level5.cs:120-121
 
 
-ALL_FORMATS = [LZSS, LZ10, LZ11, Yaz0, Yay0, MIO0, PRS, LZO, LZ4, LZ4Legacy, Snappy, GCLZ, CXLZ, LZ_3DS, COMP, Yaz1, AKLZ, LZ01, LZSega, Level5LZSS, LZOn, MDB4, FCMP, IECP, GCZ, ECD, SDPC, LZ40, LZ60, LZHudson, SMSR00, LZ00, FastLZ, CNX2, BLZ, CLZ0, CNS, LZ02, RefPack, WFLZ, LZShrek, HIG, LZ77, Level5]
+ALL_FORMATS = [LZSS, LZ10, LZ11, Yaz0, Yay0, MIO0, PRS, LZO, LZ4, LZ4Legacy, Snappy, GCLZ, CXLZ, LZ_3DS, COMP, Yaz1, AKLZ, LZ01, LZSega, Level5LZSS, LZOn, MDB4, FCMP, IECP, GCZ, ECD, SDPC, LZ40, LZ60, LZHudson, SMSR00, LZ00, FastLZ, CNX2, BLZ, CLZ0, CNS, LZ02, RefPack, WFLZ, LZShrek, HIG, LZ77, Level5, RLE30, HUF20]
 __all__ = [c.__name__ for c in ALL_FORMATS] + ["CompressionSettings", "DecompressedSizeException", "EndOfStreamException", "InvalidIdentifierException", "InvalidDataException", "AlzError"]

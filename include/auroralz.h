@@ -301,6 +301,50 @@ int alz_measure_batch(alz_ctx* ctx, const alz_lz_properties* props, uint32_t n,
 int alz_measure_batch_device(alz_ctx* ctx, const alz_lz_properties* props, uint32_t n,
                              const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results);
 
+/* ---------------------------------------- RLE30 / HUF20: the non-LZ bodies of the Nintendo GBA / DS family
+ * The BIOS family that LZ10 / LZ11 belong to has two members without a window: run-length (type 0x30) and Huffman (types 0x24 /
+ * 0x28).  They are no alz_format -- no match copy, no LzWindows, no body in the CPU oracle -- and have an entry-point family of
+ * their own, as measure has.  alz_stream and alz_result are reused: `format` holds an alz_rlh_format; aux0 is, for
+ * ALZ_RLH_HUF20_4, the nibble order (0 = Endian.Little: HUF20 and LZ77; 1 = Endian.Big: Level5) and otherwise ignored, aux1 is
+ * ignored.  The slack rules are those of the plans: 64 readable bytes behind the last stream of both device buffers, never a
+ * write outside [dst_off, dst_off + dst_cap).  alz_ctx_set_exact_kernels selects the kernel family (one token / one bit at a
+ * time against the lane-parallel kernels); alz_last_kernel_ms reports the device time of the call's launches.
+ *
+ * RLE30.DecompressHeaderless (Nintendo/RLE30.cs:76-105): control byte c, n = (c & 0x7F) + 1; c >= 0x80: the next byte n + 2
+ *   times (3..130), else n literals (1..128).  Input that ends at a control byte, at a run byte or inside a literal run:
+ *   INPUT_TRUNCATED, src_used = src_len, dst_len = the whole tokens before it (the managed code reads a literal run into a
+ *   temporary and throws before it writes).  The last token may overshoot decom_len: written, OUTPUT_SIZE_MISMATCH (E4, the '>'
+ *   rule of :101).  A token that would exceed dst_cap is clipped and ends decoding (E5, as LZ10).  decom_len 0: OK, nothing read.
+ * RLE30.CompressHeaderless (:110-129 over MatchFinder/RleMatchFinder.cs:29-64, minMatch 3, maxMatch 127): bit-identical to the managed
+ *   bytes INCLUDING ITS DEFECT (E7): 127 literals followed by fewer than 3 bytes become ONE literal run of up to 129 bytes
+ *   (`duration = source.Length - offset`, RleMatchFinder.cs:43), whose control byte wraps to 0x80 -- such a stream does not decode
+ *   back (129 or 256 non-repeating bytes; 128 and 130 round-trip).  Over dst_cap: OUTPUT_CAPACITY, dst_len 0.
+ * HUF20.DecompressHeaderless (Nintendo/HUF20.cs:94-152): byte 0 treeSize, byte 1 treeRoot, treeSize * 2 tree bytes (a short read
+ *   leaves zeros and is no error), then little-endian 32-bit words consumed MSB first; decom_len * 8 / bitDepth symbols.  4-bit
+ *   mode ORs the WHOLE tree byte, shifted by 4 or 0, into a cleared destination: a leaf value above 0xF pollutes or loses bits
+ *   exactly as the managed code does.  A missing header byte or word: INPUT_TRUNCATED, src_used = src_len; an index beyond the
+ *   tree (IndexOutOfRangeException): INPUT_TRUNCATED, src_used just behind the last word read; a stream that decodes into
+ *   dst_cap < decom_len: OUTPUT_CAPACITY (a stream error wins over it).  The managed code hands its destination nothing unless
+ *   the whole decode succeeded (:103-107): dst_len = 0 for EVERY non-OK status, the bytes inside [dst_off, dst_off +
+ *   min(dst_cap, decom_len)) are then unspecified, and nothing outside is written.  decom_len 0 still reads the header and the
+ *   tree.  decom_len >= 0x10000000 is refused with ALZ_E_UNSUPPORTED (the managed `int` symbol count overflows).
+ * HUF20 HAS NO ENCODER: alz_rlh_encode_batch* with a HUF format, and alz_container_compress of every HUF type, answer
+ *   ALZ_E_UNSUPPORTED.  The project's bar is bit-identity with the managed encoder, and the managed output is not a function of
+ *   the input that can be restated: HuffmanTree.CreateTree (Huffman/HuffmanTree.cs:89-101) orders equal frequencies with the
+ *   UNSTABLE List.Sort() over a comparer that looks at Frequency only (HuffmanNode.cs:66-67), and the 4-bit path indexes its
+ *   16-entry table with un-shifted high nibbles (HUF20.cs:189-196). */
+typedef enum alz_rlh_format { ALZ_RLH_RLE30 = 0, ALZ_RLH_HUF20_4 = 1, ALZ_RLH_HUF20_8 = 2, ALZ_RLH_COUNT = 3 } alz_rlh_format;
+int alz_rlh_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                         uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_rlh_decode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+/* src_* describe the raw input, dst_* the compressed output capacity (2 * src_len always suffices); results[i].dst_len is the compressed size */
+int alz_rlh_encode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                         uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+int alz_rlh_encode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's
  * [dst_off, dst_off + dst_len) (tests/test_gpu_canary.py); they READ the input in aligned 16-byte granules and, for the 64 KiB
@@ -417,8 +461,8 @@ typedef enum alz_container {
     ALZ_C_LZSEGA = 17, /* csize+size + LZSS              src/AuroraLib.Compression.Sega/Sega/LZSega.cs:49-68        */
     ALZ_C_LEVEL5LZSS = 18, /* "SSZL"+0+csize+size + LZSS src/AuroraLib.Compression.Nintendo/Level5/Level5LZSS.cs:42-72 */
     ALZ_C_LZON   = 19, /* "LZOn"+002FF171+BE size+csize + LZO  src/AuroraLib.Compression.Nintendo/Nintendo/LZOn.cs:41-79 */
-    ALZ_C_LZ77   = 20, /* "LZ77"+type: LZ10 / LZ11 / ChunkLZ10 (independent 4 KiB chunks = one GPU batch)  Nintendo/LZ77.cs:56-153 */
-    ALZ_C_LEVEL5 = 21, /* u32 type|size<<3: OnlySave / LZ10   src/AuroraLib.Compression.Nintendo/Level5/Level5.cs:62-146 */
+    ALZ_C_LZ77   = 20, /* "LZ77"+type: LZ10 / LZ11 / ChunkLZ10 (independent 4 KiB chunks = one GPU batch) / RLE30 / HUF20  Nintendo/LZ77.cs:56-153 */
+    ALZ_C_LEVEL5 = 21, /* u32 type|size<<3: OnlySave / LZ10 / Huffman4Bit / Huffman8Bit / RLE   src/AuroraLib.Compression.Nintendo/Level5/Level5.cs:62-146 */
     ALZ_C_LZ4_FRAME = 22, /* LZ4: frame 0x184D2204 (descriptor, linked or independent blocks, xxHash32 block / content
                              checksums), legacy and skippable frames, concatenated   LZ4.cs:50-93, LZ4.Frame.cs:107-215.
                              Decoding: a frame none of whose blocks reaches in front of itself (a host walk over the sequences)
@@ -452,21 +496,30 @@ typedef enum alz_container {
     ALZ_C_HIG    = 43, /* "HIG!" + 15 ints (data offset, ..., version, size) [+ compressed size + path[0x7C] for versions 5 / 6] + HIG body
                           src/AuroraLib.Compression-Extended/Specialized/HIG.cs:47-124 */
     ALZ_C_CNX2   = 35, /* "CNX\x02" + extension[4] + BE csize + BE size + CNX2 body   src/AuroraLib.Compression.Sega/Sega/CNX2.cs:45-81 */
-    ALZ_C_COUNT  = 44
+    /* the non-LZ bodies of the GBA / DS family (alz_rlh_*): a header of type + u24 LE size, or type + u24 0 + u32 LE size */
+    ALZ_C_RLE30  = 44, /* 0x30 + size + RLE30 body                        src/AuroraLib.Compression.Nintendo/Nintendo/RLE30.cs:29-74 */
+    ALZ_C_HUF20  = 45, /* 0x24 / 0x28 + size + HUF20 body (little nibble order); decode only   Nintendo/HUF20.cs:46-92 */
+    ALZ_C_COUNT  = 46
 } alz_container;
 
 /* alz_container_options.variant for ALZ_C_LZ77 (LZ77.CompressionType, LZ77.cs:156-164) and ALZ_C_LEVEL5 (Level5.cs:151-159) */
 #define ALZ_LZ77_LZ10      0x10u
 #define ALZ_LZ77_LZ11      0x11u
 #define ALZ_LZ77_CHUNKLZ10 0xF7u
+#define ALZ_LZ77_HUF20_4   0x24u   /* decode only (HUF20 has no encoder: see alz_rlh_format) */
+#define ALZ_LZ77_HUF20_8   0x28u   /* decode only */
+#define ALZ_LZ77_RLE30     0x30u
 #define ALZ_LEVEL5_ONLYSAVE 0u
 #define ALZ_LEVEL5_LZ10     1u
+#define ALZ_LEVEL5_HUFFMAN4 2u     /* decode only; big nibble order (Level5.cs:94-105) */
+#define ALZ_LEVEL5_HUFFMAN8 3u     /* decode only */
+#define ALZ_LEVEL5_RLE      4u
 
 typedef struct alz_container_options {
     uint32_t big_endian;          /* IEndianDependentFormat.FormatByteOrder: 1 = Endian.Big (default for Yaz0/Yay0/MIO0/PRS) */
     uint32_t memory_alignment;    /* Yaz0.MemoryAlignment (Yaz0.cs:39) */
     alz_lz_properties lz;         /* LZSS geometry */
-    uint32_t variant;             /* LZ77.Type / Level5.Type when compressing; 0 = the class default (LZ10) */
+    uint32_t variant;             /* LZ77.Type / Level5.Type / HUF20.Type (0x24 / 0x28) when compressing; 0 = the class default (LZ10) */
     uint32_t chunk_size;          /* LZ77.ChunkSize (default 0x1000); ALZ_C_LZ4_FRAME: LZ4.BlockSize, one of 0x10000 /
                                      0x40000 / 0x100000 / 0x400000 (0 = the class default Block4MB, LZ4.cs:33) */
     uint32_t key;                 /* ALZ_C_LZ00 when compressing: the keystream seed written to the header (LZ00.Compress(..., uint key, ...)

@@ -105,6 +105,17 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib)] internal static extern int alz_measure_batch_device(IntPtr ctx, AlzLzProperties* props, uint n,
             byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
 
+        // RLE30 / HUF20, the non-LZ bodies of the GBA / DS family: AlzStream.format holds an alz_rlh_format (0 RLE30, 1 HUF20 4-bit, 2 HUF20 8-bit);
+        // aux0 of a 4-bit stream is the nibble order (1 = Endian.Big, Level5).  HUF20 has no encoder (ALZ_E_UNSUPPORTED).
+        [DllImport(Lib)] internal static extern int alz_rlh_decode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_rlh_decode_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_rlh_encode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_rlh_encode_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
             byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
