@@ -92,4 +92,16 @@ MEASURE_PROTOTYPES = {
 RLH_PROTOTYPES = {name: [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
                   for name in ("alz_rlh_decode_batch", "alz_rlh_decode_batch_device", "alz_rlh_encode_batch", "alz_rlh_encode_batch_device")}
 
+# the aPLib entry points (decode only): batches of headerless bodies, their sizes without decoding, and the aPLib class on a file in host memory
+APLIB_WINDOW = 0x200000
+_APLIB_DECODE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+_APLIB_MEASURE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+APLIB_PROTOTYPES = {
+    "alz_aplib_decode_batch": _APLIB_DECODE, "alz_aplib_decode_batch_device": _APLIB_DECODE,
+    "alz_aplib_measure_batch": _APLIB_MEASURE, "alz_aplib_measure_batch_device": _APLIB_MEASURE,
+    "alz_aplib_is_match": [C.c_void_p, C.c_size_t],
+    "alz_aplib_decompressed_size": [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)],
+    "alz_aplib_decompress": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)],
+}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16

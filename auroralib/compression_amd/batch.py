@@ -148,6 +148,39 @@ class Context:
         check(self.lib.alz_rlh_encode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
         return res
 
+    # ---- aPLib (decode only): headerless bodies; format, decom_len, aux0 and aux1 of a stream are ignored
+    def aplib_decode_batch(self, streams, src, dst_bytes, dst=None):
+        """alz_aplib_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
+        n = len(streams)
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if dst is None:
+            dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
+        elif dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.nbytes < dst_bytes:
+            raise ValueError("dst must be a contiguous uint8 array of at least dst_bytes")
+        res = (A.Result * n)()
+        check(self.lib.alz_aplib_decode_batch(self.h, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def aplib_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_aplib_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launch."""
+        res = (A.Result * len(streams))()
+        check(self.lib.alz_aplib_decode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
+        return res
+
+    def aplib_measure_batch(self, streams, src):
+        """alz_aplib_measure_batch on a host buffer: the results aplib_decode_batch would return, nothing decoded; dst_cap only bounds the count."""
+        n = len(streams)
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        res = (A.Result * n)()
+        check(self.lib.alz_aplib_measure_batch(self.h, n, _vp(src), src.nbytes, streams, res))
+        return res
+
+    def aplib_measure_batch_device(self, streams, d_src, src_bytes):
+        """alz_aplib_measure_batch_device: the same with the source already in HBM at d_src."""
+        res = (A.Result * len(streams))()
+        check(self.lib.alz_aplib_measure_batch_device(self.h, len(streams), d_src, src_bytes, streams, res))
+        return res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

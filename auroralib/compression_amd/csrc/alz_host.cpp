@@ -20,6 +20,7 @@
 #include "alz_internal.h"
 #include "alz_measure.h"
 #include "alz_rlh.h"
+#include "alz_aplib.h"
 
 static thread_local char g_err[512] = "";
 
@@ -1059,6 +1060,85 @@ int alz_rlh_encode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_bas
                                 uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
     if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_rlh_encode_batch_device: bad argument");
     return rlh_core(c, true, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
+}
+
+// ---------------------------------------------------------------- aPLib: the last LzWindows user (alz_aplib.hip)
+// Decode and measure, shaped like the family above: one launch, longest streams first, on the context's stream, tables in the context's
+// plan scratch, results to the host.  `format`, decom_len, aux0 and aux1 of a stream are ignored.  measure: no destination (d_dst_base NULL).
+static int aplib_validate(bool measure, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes) {
+    const char* what = measure ? "alz_aplib_measure_batch" : "alz_aplib_decode_batch";
+    for (uint32_t i = 0; i < n; i++) {
+        const alz_stream& s = streams[i];
+        if (!range_ok(s.src_off, s.src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: source range exceeds src_bytes", what, i);
+        if (!measure && !range_ok(s.dst_off, s.dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: destination range exceeds dst_bytes", what, i);
+    }
+    return ALZ_OK;
+}
+
+static int aplib_core(alz_ctx* c, bool measure, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                      uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    const char* what = measure ? "alz_aplib_measure_batch" : "alz_aplib_decode_batch";
+    if (int rc = aplib_validate(measure, n, src_bytes, streams, dst_bytes)) return rc;
+    c->last_kernel_ms = 0.f;
+    if (n == 0) return ALZ_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint32_t> index(n);
+    for (uint32_t i = 0; i < n; i++) index[i] = i;
+    if (n > 1) std::stable_sort(index.begin(), index.end(), [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });   // a stream's cost is its tokens
+    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
+    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
+    alz_stream* d_streams = (alz_stream*)c->d_plan;
+    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
+    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
+    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess)
+        e = measure ? alz_launch_aplib_measure(c->stream, d_src_base, d_streams, d_index, n, d_results)
+                    : alz_launch_aplib_decode(c->stream, d_src_base, d_dst_base, d_streams, d_index, n, d_results,
+                                              c->exact ? ALZ_APLIB_EXACT : (c->variant != 0 ? ALZ_APLIB_PRODUCTION : ALZ_APLIB_DEFAULT));
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+
+int alz_aplib_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                           uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return fail(ALZ_E_INVALID, "alz_aplib_decode_batch: bad argument");
+    if (n == 0) return ALZ_OK;
+    int rc;
+    if ((rc = aplib_validate(false, n, src_bytes, streams, dst_bytes))) return rc;   // (first: a refused call pays for no upload)
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
+    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
+    if ((rc = aplib_core(c, false, n, (const uint8_t*)c->d_src, src_bytes, streams, (uint8_t*)c->d_dst, dst_bytes, results))) return rc;
+    return download_outputs(c, n, streams, results, dst_base, false);   // what each stream produced, whatever its status (as alz_decode_batch)
+}
+int alz_aplib_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                  uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_aplib_decode_batch_device: bad argument");
+    return aplib_core(c, false, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
+}
+int alz_aplib_measure_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
+    if (!c || (n && (!streams || !results || !d_src_base))) return fail(ALZ_E_INVALID, "alz_aplib_measure_batch_device: bad argument");
+    return aplib_core(c, true, n, d_src_base, src_bytes, streams, nullptr, 0, results);
+}
+int alz_aplib_measure_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
+    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base)) return fail(ALZ_E_INVALID, "alz_aplib_measure_batch: bad argument");
+    if (n == 0) return ALZ_OK;
+    int rc;
+    if ((rc = aplib_validate(true, n, src_bytes, streams, 0))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
+    return aplib_core(c, true, n, (const uint8_t*)c->d_src, src_bytes, streams, nullptr, 0, results);
 }
 
 // Device buffers of one encode call, freed on every exit path

@@ -528,3 +528,49 @@ class Level5(_NoHuffmanEncoder):
 
 ALL_FORMATS = [LZSS, LZ10, LZ11, Yaz0, Yay0, MIO0, PRS, LZO, LZ4, LZ4Legacy, Snappy, GCLZ, CXLZ, LZ_3DS, COMP, Yaz1, AKLZ, LZ01, LZSega, Level5LZSS, LZOn, MDB4, FCMP, IECP, GCZ, ECD, SDPC, LZ40, LZ60, LZHudson, SMSR00, LZ00, FastLZ, CNX2, BLZ, CLZ0, CNS, LZ02, RefPack, WFLZ, LZShrek, HIG, LZ77, Level5, RLE30, HUF20]
 __all__ = [c.__name__ for c in ALL_FORMATS] + ["CompressionSettings", "DecompressedSizeException", "EndOfStreamException", "InvalidIdentifierException", "InvalidDataException", "AlzError"]
+
+
+APLIB_NO_ENCODER = ("aPLib has no encoder here: CompressHeaderless runs the tiered LzChainMatchFinder with a 2 MiB window and unbounded lengths, the bar is "
+                    "bit-identity with the managed bytes checked against the CPU oracle, and the oracle has no aPLib (include/auroralz.h)")
+
+
+class APLib:
+    """src/AuroraLib.Compression/Formats/Common/aPLib.cs -- "AP32" + 24-byte header + body, or a headerless body (alz_aplib_*); decode only.
+    No alz_container value backs it, so it stays outside ALL_FORMATS."""
+    provides_size = True
+
+    def IsMatch(self, data):
+        data = bytes(data)
+        return bool(load().alz_aplib_is_match(data, len(data)))
+
+    def GetDecompressedSize(self, data):
+        data = bytes(data)
+        size = C.c_uint32()
+        rc = load().alz_aplib_decompressed_size(data, len(data), C.byref(size))
+        if rc == A.E_FORMAT:
+            raise InvalidIdentifierException()
+        check(rc)
+        return size.value
+
+    def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
+        """The decoded size of a HEADERLESS body, counted on the GPU without decoding (alz_aplib_measure_batch)."""
+        data = bytes(data)
+        st = (A.Stream * 1)(A.Stream(0, 0, len(data), limit, 0, 0, 0, 0))
+        r = _context().aplib_measure_batch(st, np.frombuffer(data + bytes(64), dtype=np.uint8))[0]
+        _raise_for_outcome(A.E_STREAM if r.status else 0, r.status, r.dst_len)
+        return r.dst_len
+
+    def Decompress(self, data, capacity=None):
+        """aPLib.Decompress: an "AP32" file, or -- without the magic -- a headerless body (whose size is measured first when no capacity is given)."""
+        data = bytes(data)
+        if capacity is None:
+            capacity = self.GetDecompressedSize(data) if data[:4] == b"AP32" and len(data) >= 24 else self.MeasureDecompressedSize(data)
+        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)
+        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
+        rc = load().alz_aplib_decompress(_context().h, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), capacity, C.byref(dl), C.byref(su), C.byref(st))
+        _raise_for_outcome(rc, st.value, dl.value)
+        self.last_src_used = su.value
+        return dst_arr[:dl.value].tobytes()
+
+    def Compress(self, data, settings=None):
+        raise NotImplementedError(APLIB_NO_ENCODER)

@@ -345,6 +345,61 @@ int alz_rlh_encode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size
 int alz_rlh_encode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                 uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
 
+/* ---------------------------------------- aPLib: the last LzWindows user of the reference (decode only)
+ * aPLib (src/AuroraLib.Compression/Formats/Common/aPLib.cs) is no alz_format: its body carries no size, ends at an end marker and looks
+ * back up to W = 0x200000 (2 MiB, WindowsBits 21); it has no body in the CPU oracle.  It has an entry-point family of its own, as measure
+ * and rlh have.  alz_stream and alz_result are reused; decom_len, aux0, aux1 and format of a stream are IGNORED.  The slack rules are
+ * those of alz_rlh_* and the plans (64 readable bytes behind the last stream of both device buffers, never a write outside
+ * [dst_off, dst_off + dst_cap)).  Two kernel families with identical results: alz_ctx_set_exact_kernels(1) selects the exact one (one token
+ * at a time), alz_ctx_set_kernel_variant(1) the token-queue kernel with the lane-parallel byte phase; a context in neither mode gets the one
+ * that was measured faster (docs/EXPERIMENTS.md 13).  alz_last_kernel_ms reports the device time of the call's launch.
+ *
+ * aPLib.DecompressHeaderless (aPLib.cs:105-181): the first byte is a literal; then tokens, each introduced by up to three 1-bits from a
+ * FlagReader(source, Endian.Big) -- 8-bit flag bytes, MSB first, fetched lazily at the current input position when a bit is needed and
+ * none is left, so flag bytes and data bytes interleave: `0` literal byte; `10` gamma-coded match (or, right behind a literal / one-byte
+ * token, gamma 2 = repeat the last distance); `110` byte b: distance b >> 1, length 2 + (b & 1), distance 0 = the END MARKER; `111` four
+ * bits o: one byte from distance o, o == 0 writes 0x00.  The edge rules:
+ *   32-bit arithmetic  ReadGamma and (offset << 8) | byte are C# ints in an unchecked context: computed in uint32_t, read as int32_t; the
+ *                      repeat test `offset == 2` sees the wrapped value.
+ *   distance           negative as int32_t or larger than W: ALZ_ST_BAD_TOKEN (E3).  The length gamma behind it is read first, as the managed
+ *                      code does before BackCopy: src_used is just behind that gamma; input that ends inside it is INPUT_TRUNCATED.
+ *   length             after LengthDelta, as int32_t: <= 0 copies nothing (LzWindows.cs:80; lastOffset and lwm are still updated), anything
+ *                      positive is legal and clipped by dst_cap (E5).
+ *   distance 0         (a repeat before any match; a match with high part 0 and low byte 0) copies from W back (E1); sources in front of
+ *                      the stream start read 0x00 (E2).
+ *   end of input       a missing flag or data byte: INPUT_TRUNCATED, dst_len = what was produced, src_used = src_len.  Empty input:
+ *                      INPUT_TRUNCATED, dst_len 0.
+ *   capacity           a literal or match that does not fit dst_cap is clipped: OUTPUT_CAPACITY, dst_len = dst_cap, src_used unspecified.
+ *   success            OK means the end marker was read; src_used is just behind its byte.
+ * alz_aplib_measure_batch*: results[i] is what alz_aplib_decode_batch would return for streams[i] -- status, dst_len, and src_used wherever
+ *   it is defined (every status but OUTPUT_CAPACITY); dst_off is ignored, dst_cap only bounds the count (0xFFFFFF00 for "the size"),
+ *   nothing is written on the device but the results.
+ * THERE IS NO ENCODER.  aPLib.CompressHeaderless runs the tiered LzChainMatchFinder over seven LzProperties with a 2 MiB window and
+ *   unbounded lengths; the project's bar is bit-identity with the managed bytes, checked against the CPU oracle, and the oracle has no
+ *   aPLib.  alz_brute_force and alz_container_scan keep their 19 decoders / alz_container values and do not try aPLib. */
+int alz_aplib_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                           uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_aplib_decode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                  uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+int alz_aplib_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                            alz_result* results);
+int alz_aplib_measure_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                   alz_result* results);
+/* The aPLib class (aPLib.cs:39-84) on a whole file in host memory.
+ * alz_aplib_is_match: 1 when src_len > 0x10, the magic "AP32" and u32 LE at offset 4 == 24 (IsMatchStatic, :44), else 0.
+ * alz_aplib_decompressed_size: u32 LE at offset 16; ALZ_E_FORMAT without the magic or with fewer than 20 bytes.
+ * alz_aplib_decompress: without the magic at offset 0 (or with fewer than 4 bytes) the whole input is a headerless body (:59-64).
+ *   With it, 24 header bytes are needed (else ALZ_E_FORMAT) and the body starts at 24 + ((headerSize - 24) mod 2^32), computed in 64
+ *   bits as the managed `Position += uint` is: a header size below 24 lands beyond the end -- ALZ_E_STREAM / INPUT_TRUNCATED, *dst_len 0.
+ *   The compressed-size field is only traced by the reference and ignored here.  A decoded size different from the header's:
+ *   ALZ_E_STREAM / OUTPUT_SIZE_MISMATCH with *dst_len the actual size.  *src_used = body start + the body's src_used.  On
+ *   ALZ_E_STREAM, *status holds the alz_status. */
+int alz_aplib_is_match(const uint8_t* src, size_t src_len);
+int alz_aplib_decompressed_size(const uint8_t* src, size_t src_len, uint32_t* size_out);
+int alz_aplib_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
+                         size_t* dst_len, size_t* src_used, int32_t* status);
+
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's
  * [dst_off, dst_off + dst_len) (tests/test_gpu_canary.py); they READ the input in aligned 16-byte granules and, for the 64 KiB

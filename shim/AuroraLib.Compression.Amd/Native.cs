@@ -116,6 +116,21 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib)] internal static extern int alz_rlh_encode_batch_device(IntPtr ctx, uint n,
             byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
 
+        // aPLib (Formats/Common/aPLib.cs), decode only: headerless bodies in batches (format, decomLen, aux0, aux1 of a stream are ignored; the body
+        // ends at its end marker), their sizes without decoding, and the aPLib class on an "AP32" file or a headerless body in host memory
+        [DllImport(Lib)] internal static extern int alz_aplib_decode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_aplib_decode_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_aplib_measure_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_aplib_measure_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_aplib_is_match(byte* src, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_aplib_decompressed_size(byte* src, UIntPtr srcLen, uint* sizeOut);
+        [DllImport(Lib)] internal static extern int alz_aplib_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
+            UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
+
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
             byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);

@@ -14,6 +14,7 @@ FAMILIES = {
     "encode": ["alz_encode.hip", "alz_encode_big.h", "alz_encode_seg.h", "alz_encode_seg_seq.h", "alz_device.h", "alz_internal.h"],
     "measure": ["alz_measure.hip", "alz_measure.h"],   # decoded sizes without decoding: no committed counters
     "rlh": ["alz_rlh.hip", "alz_rlh.h"],               # RLE30 / HUF20, the non-LZ bodies of the GBA / DS family: no committed counters
+    "aplib": ["alz_aplib.hip", "alz_aplib.h"],         # aPLib, the 2 MiB-window LzWindows user (decode + measure): no committed counters
 }
 FILES = ("traffic.json", "insts.json")
 
