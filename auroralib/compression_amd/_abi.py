@@ -104,4 +104,27 @@ APLIB_PROTOTYPES = {
     "alz_aplib_decompress": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)],
 }
 
+# the CRILAYLA / ALLZ entry points (decode only): batches of headerless bodies (streams[i].format is a BITLZ_* value) and the two classes on a file in host memory
+BITLZ_CRILAYLA, BITLZ_ALLZ = range(2)
+BITLZ_COUNT = 2
+BITLZ_NAMES = ["crilayla", "allz"]
+CRILAYLA_HEADER = 0x100                 # plain bytes a CRILAYLA file keeps behind its body; the file layer decodes into size + 0x100
+CRILAYLA_MAX_DISTANCE = 8194
+
+
+def allz_aux0(copy_bits=0, dist_bits=10, len_bits=1):
+    """ALZ_ALLZ_AUX0: flags[1], flags[2], flags[3] of an ALLZ header (the class defaults)."""
+    return copy_bits | dist_bits << 8 | len_bits << 16
+
+
+_BITLZ_DECODE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+_BITLZ_IS_MATCH = [C.c_void_p, C.c_size_t]
+_BITLZ_SIZE = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+_BITLZ_DECOMPRESS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+BITLZ_PROTOTYPES = {
+    "alz_bitlz_decode_batch": _BITLZ_DECODE, "alz_bitlz_decode_batch_device": _BITLZ_DECODE,
+    "alz_crilayla_is_match": _BITLZ_IS_MATCH, "alz_crilayla_decompressed_size": _BITLZ_SIZE, "alz_crilayla_decompress": _BITLZ_DECOMPRESS,
+    "alz_allz_is_match": _BITLZ_IS_MATCH, "alz_allz_decompressed_size": _BITLZ_SIZE, "alz_allz_decompress": _BITLZ_DECOMPRESS,
+}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16

@@ -181,6 +181,26 @@ class Context:
         check(self.lib.alz_aplib_measure_batch_device(self.h, len(streams), d_src, src_bytes, streams, res))
         return res
 
+    # ---- CRILAYLA / ALLZ (decode only): headerless bodies; streams[i].format is an A.BITLZ_* value
+    def bitlz_decode_batch(self, streams, src, dst_bytes, dst=None):
+        """alz_bitlz_decode_batch on host buffers.  A CRILAYLA stream's dst_len bytes end at dst_off + dst_cap (it is written from the top down);
+        an ALLZ stream takes decom_len and aux0 = A.allz_aux0(copy, dist, len).  `dst`: a caller-owned uint8 array of >= dst_bytes (default: a new one)."""
+        n = len(streams)
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if dst is None:
+            dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
+        elif dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.nbytes < dst_bytes:
+            raise ValueError("dst must be a contiguous uint8 array of at least dst_bytes")
+        res = (A.Result * n)()
+        check(self.lib.alz_bitlz_decode_batch(self.h, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def bitlz_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_bitlz_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
+        res = (A.Result * len(streams))()
+        check(self.lib.alz_bitlz_decode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
+        return res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

@@ -21,6 +21,7 @@
 #include "alz_measure.h"
 #include "alz_rlh.h"
 #include "alz_aplib.h"
+#include "alz_bitlz.h"
 
 static thread_local char g_err[512] = "";
 
@@ -1139,6 +1140,81 @@ int alz_aplib_measure_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, siz
     if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
     if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
     return aplib_core(c, true, n, (const uint8_t*)c->d_src, src_bytes, streams, nullptr, 0, results);
+}
+
+// ---------------------------------------------------------------- CRILAYLA / ALLZ: the bit-stream LZ bodies of the .Extended assembly (alz_bitlz.hip)
+// Decode only, shaped like the families above: grouped per alz_bitlz_kind (one launch per kind present, longest streams first), on the
+// context's stream, tables in the context's plan scratch, results to the host.  Each kind has one kernel, so all three context modes run
+// it.
+static int bitlz_validate(uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes) {
+    for (uint32_t i = 0; i < n; i++) {
+        const alz_stream& s = streams[i];
+        if (s.format >= ALZ_BITLZ_COUNT) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: stream %u: unknown alz_bitlz_kind %u", i, s.format);
+        if (!range_ok(s.src_off, s.src_len, src_bytes)) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: stream %u: source range exceeds src_bytes", i);
+        if (!range_ok(s.dst_off, s.dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: stream %u: destination range exceeds dst_bytes", i);
+    }
+    return ALZ_OK;
+}
+
+// (the streams are validated by the caller)
+static int bitlz_core(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, const alz_stream* streams, uint8_t* d_dst_base, alz_result* results) {
+    uint32_t cnt[ALZ_BITLZ_COUNT] = {0}, off[ALZ_BITLZ_COUNT] = {0}, fill[ALZ_BITLZ_COUNT] = {0};
+    for (uint32_t i = 0; i < n; i++) cnt[streams[i].format]++;
+    c->last_kernel_ms = 0.f;
+    if (n == 0) return ALZ_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint32_t> index(n);
+    for (int f = 1; f < ALZ_BITLZ_COUNT; f++) off[f] = off[f - 1] + cnt[f - 1];
+    for (uint32_t i = 0; i < n; i++) { const uint32_t f = streams[i].format; index[off[f] + fill[f]++] = i; }
+    for (int f = 0; f < ALZ_BITLZ_COUNT; f++)   // a stream's cost is its tokens
+        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
+    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
+    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
+    alz_stream* d_streams = (alz_stream*)c->d_plan;
+    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
+    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
+    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    for (int f = 0; f < ALZ_BITLZ_COUNT && e == hipSuccess; f++)
+        if (cnt[f]) e = alz_launch_bitlz_decode(f, c->stream, d_src_base, d_dst_base, d_streams, d_index + off[f], cnt[f], d_results);
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "alz_bitlz_decode_batch failed: %s", hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+
+int alz_bitlz_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                           uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: bad argument");
+    c->last_kernel_ms = 0.f;
+    if (n == 0) return ALZ_OK;
+    int rc;
+    if ((rc = bitlz_validate(n, src_bytes, streams, dst_bytes))) return rc;   // (first: a refused call pays for no upload)
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
+    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
+    if ((rc = bitlz_core(c, n, (const uint8_t*)c->d_src, streams, (uint8_t*)c->d_dst, results))) return rc;
+    std::vector<out_seg> segs;                                          // what each stream produced, whatever its status: CRILAYLA's at the TOP of its span
+    segs.reserve(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!results[i].dst_len) continue;
+        const uint64_t at = streams[i].dst_off + (streams[i].format == ALZ_BITLZ_CRILAYLA ? streams[i].dst_cap - results[i].dst_len : 0u);
+        segs.push_back(out_seg{at, dst_base + at, results[i].dst_len});
+    }
+    return download_segs(c, segs);
+}
+int alz_bitlz_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                  uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch_device: bad argument");
+    if (int rc = bitlz_validate(n, src_bytes, streams, dst_bytes)) return rc;
+    return bitlz_core(c, n, d_src_base, streams, d_dst_base, results);
 }
 
 // Device buffers of one encode call, freed on every exit path

@@ -574,3 +574,56 @@ class APLib:
 
     def Compress(self, data, settings=None):
         raise NotImplementedError(APLIB_NO_ENCODER)
+
+
+BITLZ_NO_ENCODER = ("%s has no encoder here: CompressHeaderless runs the LzChainMatchFinder, the bar is bit-identity with the managed bytes checked against "
+                    "the CPU oracle, and there is no oracle body to hold bit-identity against (include/auroralz.h)")
+
+
+class _BitLzFile:
+    """A class of the .Extended assembly over its alz_<prefix>_* file entry points (alz_bitlz_decode_batch underneath); decode only.
+    No alz_container value backs it, so it stays outside ALL_FORMATS."""
+    provides_size = True
+    prefix = None
+
+    def IsMatch(self, data):
+        data = bytes(data)
+        return bool(getattr(load(), "alz_%s_is_match" % self.prefix)(data, len(data)))
+
+    def GetDecompressedSize(self, data):
+        data = bytes(data)
+        size = C.c_uint32()
+        rc = getattr(load(), "alz_%s_decompressed_size" % self.prefix)(data, len(data), C.byref(size))
+        if rc == A.E_FORMAT:
+            raise InvalidIdentifierException()
+        check(rc)
+        return size.value
+
+    def Decompress(self, data, capacity=None):
+        data = bytes(data)
+        if capacity is None:
+            capacity = self.GetDecompressedSize(data)
+        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)
+        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
+        rc = getattr(load(), "alz_%s_decompress" % self.prefix)(_context().h, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), capacity, C.byref(dl), C.byref(su), C.byref(st))
+        self.last_src_used = su.value
+        _raise_for_outcome(rc, st.value, dl.value)
+        return dst_arr[:dl.value].tobytes()
+
+    def Compress(self, data, settings=None):
+        raise NotImplementedError(BITLZ_NO_ENCODER % type(self).__name__)
+
+
+class CRILAYLA(_BitLzFile):
+    """src/AuroraLib.Compression-Extended/CRI/CRILAYLA.cs -- "CRILAYLA" + size + csize + body + 0x100 plain header bytes (alz_crilayla_*).
+    Decompress returns size + 0x100 bytes: the header bytes first, the body -- decoded from its last byte down -- behind them."""
+    prefix = "crilayla"
+
+
+class ALLZ(_BitLzFile):
+    """src/AuroraLib.Compression-Extended/Specialized/ALLZ.cs -- "ALLZ" + 4 flag bytes + size + body (alz_allz_*).  The three fields are
+    what Compress would write into the header (ALLZ.cs:34-36); Decompress takes them from the file."""
+    prefix = "allz"
+
+    def __init__(self):
+        self.LzCopyBits, self.LzDistanceBits, self.LzLengthBits = 0, 10, 1

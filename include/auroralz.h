@@ -400,6 +400,79 @@ int alz_aplib_decompressed_size(const uint8_t* src, size_t src_len, uint32_t* si
 int alz_aplib_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
                          size_t* dst_len, size_t* src_used, int32_t* status);
 
+/* ---------------------------------------- CRILAYLA and ALLZ: the bit-stream LZ bodies of the .Extended assembly (decode only)
+ * CRILAYLA (src/AuroraLib.Compression-Extended/CRI/CRILAYLA.cs, CRI Middleware's CPK compression) and ALLZ
+ * (src/AuroraLib.Compression-Extended/Specialized/ALLZ.cs, Aqualead LZ) are no alz_format values: neither has a body in the CPU oracle.
+ * They share an entry-point family of their own.  alz_stream and alz_result are reused; streams[i].format is an alz_bitlz_kind, any other
+ * value makes the call return ALZ_E_INVALID; a batch may mix both kinds (one launch per kind present).  The slack rules are those of
+ * alz_aplib_* (64 readable bytes behind the last stream of both device buffers).  Each kind has ONE kernel, the exact one, so
+ * alz_ctx_set_exact_kernels, alz_ctx_set_kernel_variant and a context in neither mode give identical results by construction.
+ * alz_last_kernel_ms reports the device time of the call's launches.  The kernels READ the input in aligned 8- and 16-byte granules: up to
+ * 15 bytes below src_off inside its 16-byte granule (never across a page) and up to 64 bytes behind src_off + src_len; the only other
+ * reads are of the stream's own output.
+ *
+ * CRILAYLA body (DecompressHeaderless, CRILAYLA.cs:123-188).  src_len = the compressed bytes, dst_cap = the length of the destination span
+ * (the file layer passes size + 0x100); decom_len, aux0, aux1 are ignored.  The bit source starts at the LAST input byte and moves towards
+ * the first; within a byte bits are taken MSB first, values are assembled MSB first across bytes.  OUTPUT BYTE q, counted from 0, GOES TO
+ * dst_off + dst_cap - 1 - q.  Tokens, read while unread input bytes remain (bits left in the last loaded byte are padding of either value):
+ * `0` + 8 bits: a literal; `1` + 13 bits + length code: a match of distance field + 3 (3..8194) and length 3 + the sum of fields of
+ * 2, 3, 5, 8, 8, ... bits, where a field of all ones continues (3-5 | 6-12 | 13-43 | 44-298 | 299-553 | ...); out[q] = out[q - distance]
+ * byte by byte, so overlap replicates.
+ *   distance > bytes produced   ALZ_ST_BAD_TOKEN, nothing copied; the length code is read first; src_used = bytes loaded so far.
+ *   does not fit dst_cap        a literal or match is clipped: OUTPUT_CAPACITY, dst_len = dst_cap, src_used unspecified (BAD_TOKEN is checked first).
+ *   input ends inside a token   INPUT_TRUNCATED; the token produces nothing; dst_len = what earlier tokens produced; src_used = src_len.
+ *   empty input                 OK, 0 bytes.
+ *   success                     OK, src_used = src_len; the dst_len bytes occupy [dst_off + dst_cap - dst_len, dst_off + dst_cap) and nothing
+ *                               below that is written (whatever the status); the match length is summed in 64 bits.
+ * ALLZ body (DecompressHeaderless, ALLZ.cs:90-127).  decom_len = the destination span, dst_cap = what may be written,
+ * aux0 = ALZ_ALLZ_AUX0(flags[1], flags[2], flags[3]): the start bits of match length / distance / run length (class defaults 0 / 10 / 1).
+ * FlagReader(source, Endian.Little): 8-bit flag bytes, LSB first, fetched at the CURRENT input position when a bit is needed and none is
+ * left, so flag bytes and raw run bytes interleave and bits left in a flag byte stay valid across a run.  ReadALFlag(s): bits = s, plus one
+ * per 1-bit up to the first 0-bit; then `bits` bits, least significant first; then + ((1 << (bits - s)) - 1) << s -- all in C# int
+ * arithmetic (32-bit wrap, shift counts mod 32, `1 << i` in ReadInt too), read as int32_t.  While produced < decom_len: one bit, `0`: a run of
+ * ReadALFlag(len) + 1 raw bytes from the input, `1`: no run; then, if still produced < decom_len, distance = ReadALFlag(dist) + 1,
+ * length = ReadALFlag(copy) + 3 and a byte-wise copy from produced - distance (the window is the whole output so far).
+ *   run < 0                     BAD_TOKEN.  run == 0 copies nothing.
+ *   match length <= 0           copies nothing and is no error, whatever the distance.
+ *   length > 0 and distance <= 0 or > produced    BAD_TOKEN, src_used just behind the length field (a match as the first token too).
+ *   passes min(decom_len, dst_cap)   a run or match is clipped there: OUTPUT_CAPACITY when dst_cap < decom_len, else OUTPUT_SIZE_MISMATCH;
+ *                               src_used unspecified for both.
+ *   a needed flag byte is missing, or the input holds fewer bytes than a run (after clipping) needs: INPUT_TRUNCATED, src_used = src_len;
+ *                               the run bytes that exist are copied.
+ *   decom_len 0                 OK, nothing read.       success: OK, dst_len == decom_len, src_used = the input position.
+ * THERE IS NO ENCODER for either: the project's bar is bit-identity with the managed bytes checked against the CPU oracle, and the oracle
+ *   has neither body.  alz_brute_force and alz_container_scan do not try them. */
+typedef enum alz_bitlz_kind { ALZ_BITLZ_CRILAYLA = 0, ALZ_BITLZ_ALLZ = 1, ALZ_BITLZ_COUNT = 2 } alz_bitlz_kind;
+#define ALZ_ALLZ_AUX0(copy_bits, dist_bits, len_bits)  ((copy_bits) | (dist_bits) << 8 | (len_bits) << 16)   /* flags[1], flags[2], flags[3] */
+int alz_bitlz_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                           uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_bitlz_decode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                  uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+/* The CRILAYLA class (CRILAYLA.cs:34-99) on a whole file in host memory: "CRILAYLA", u32 LE size at 8, u32 LE csize at 12, the body of csize
+ * bytes at 16, then 0x100 plain header bytes.
+ * alz_crilayla_is_match: 1 when src_len > 0x10 and the magic, else 0.
+ * alz_crilayla_decompressed_size: size + 0x100 computed in uint32_t; ALZ_E_FORMAT without the magic or with fewer than 12 bytes.
+ * alz_crilayla_decompress: fewer than 16 bytes or no magic: ALZ_E_FORMAT.  size + 0x100 >= 2^31: ALZ_E_UNSUPPORTED (the managed (int) cast).
+ *   csize reaches beyond the input: ALZ_E_STREAM / INPUT_TRUNCATED, *dst_len 0.  dst_cap < size + 0x100: ALZ_E_STREAM / OUTPUT_CAPACITY,
+ *   *dst_len 0, nothing decoded.  Otherwise the output is size + 0x100 bytes: [0, 0x100) are the plain header bytes behind the body (missing
+ *   ones 0x00), the body is decoded over the top of the span and wins where it reaches into the header region (:81), bytes that neither
+ *   wrote are 0x00.  A body that produced fewer than `size` bytes: ALZ_E_STREAM / OUTPUT_SIZE_MISMATCH with *dst_len = size + 0x100 and the
+ *   bytes delivered (the managed code writes before it throws, :86-92).  Body errors pass through as ALZ_E_STREAM with their status.
+ *   *src_used = 16 + csize + min(0x100, what is left). */
+int alz_crilayla_is_match(const uint8_t* src, size_t src_len);
+int alz_crilayla_decompressed_size(const uint8_t* src, size_t src_len, uint32_t* size_out);
+int alz_crilayla_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
+                            size_t* dst_len, size_t* src_used, int32_t* status);
+/* The ALLZ class (ALLZ.cs:39-75): "ALLZ", 4 flag bytes (byte 0 unused), u32 LE size at 8, the body at 12.
+ * alz_allz_is_match: 1 when src_len > 0x10 and the magic.  alz_allz_decompressed_size: the u32 at 8; ALZ_E_FORMAT without the magic or with
+ * fewer than 12 bytes.  alz_allz_decompress: the body with decom_len = size (fewer than 12 bytes or no magic: ALZ_E_FORMAT; a size the
+ * managed (int) cast makes negative: ALZ_E_UNSUPPORTED); *src_used = 12 + the body's; on ALZ_E_STREAM, *status holds the alz_status. */
+int alz_allz_is_match(const uint8_t* src, size_t src_len);
+int alz_allz_decompressed_size(const uint8_t* src, size_t src_len, uint32_t* size_out);
+int alz_allz_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
+                        size_t* dst_len, size_t* src_used, int32_t* status);
+
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's
  * [dst_off, dst_off + dst_len) (tests/test_gpu_canary.py); they READ the input in aligned 16-byte granules and, for the 64 KiB

@@ -131,6 +131,22 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib)] internal static extern int alz_aplib_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
             UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
 
+        // CRILAYLA (CRI/CRILAYLA.cs) and ALLZ (Specialized/ALLZ.cs), decode only: headerless bodies in batches (AlzStream.format is an alz_bitlz_kind:
+        // 0 CRILAYLA -- written from dstOff + dstCap down --, 1 ALLZ -- decomLen and aux0 = copy | dist << 8 | len << 16 start bits), and the two
+        // classes on a whole file in host memory
+        [DllImport(Lib)] internal static extern int alz_bitlz_decode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_bitlz_decode_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_crilayla_is_match(byte* src, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_crilayla_decompressed_size(byte* src, UIntPtr srcLen, uint* sizeOut);
+        [DllImport(Lib)] internal static extern int alz_crilayla_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
+            UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
+        [DllImport(Lib)] internal static extern int alz_allz_is_match(byte* src, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_allz_decompressed_size(byte* src, UIntPtr srcLen, uint* sizeOut);
+        [DllImport(Lib)] internal static extern int alz_allz_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
+            UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
+
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
             byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
