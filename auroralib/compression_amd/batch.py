@@ -16,6 +16,19 @@ def _vp(a):
     return a
 
 
+def _ref(lz):
+    return C.byref(lz) if lz is not None else None
+
+
+def _dst_array(dst, dst_bytes):
+    """the destination of a host-buffer call: a new zeroed array, or the caller's own after a check of its shape"""
+    if dst is None:
+        return np.zeros(max(dst_bytes, 1), dtype=np.uint8)
+    if dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.nbytes < dst_bytes:
+        raise ValueError("dst must be a contiguous uint8 array of at least dst_bytes")
+    return dst
+
+
 def device_count():
     """alz_device_count: HIP devices visible to this process (0 without a GPU)."""
     _libmod.GPU_TOUCHED = True
@@ -81,125 +94,92 @@ class Context:
         check(self.lib.alz_last_kernel_ms(self.h, C.byref(v)))
         return v.value
 
+    # ---- the three shapes of a batch call; `lead`: what the C function takes between the context and n (alz_lz_properties or nothing)
+    def _host_decode(self, fn, lead, streams, src, dst_bytes, dst=None):
+        """fn(ctx, *lead, n, src, src_bytes, streams, dst, dst_bytes, results) on host buffers -> (dst, results)"""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.Result * len(streams))()
+        check(fn(self.h, *lead, len(streams), _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def _host_measure(self, fn, lead, streams, src):
+        """fn(ctx, *lead, n, src, src_bytes, streams, results) on a host buffer -> results"""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        return self._device(fn, lead, streams, _vp(src), src.nbytes)
+
+    def _device(self, fn, lead, streams, d_src, src_bytes, *dst):
+        """fn(ctx, *lead, n, d_src, src_bytes, streams, [d_dst, dst_bytes,] results) -> results"""
+        res = (A.Result * len(streams))()
+        check(fn(self.h, *lead, len(streams), d_src, src_bytes, streams, *dst, res))
+        return res
+
     # ---- host-buffer decode (upload, decode on GPU, download)
     def decode_batch(self, streams, src, dst_bytes, lz=None, dst=None):
         """alz_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        if dst is None:
-            dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
-        elif dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.nbytes < dst_bytes:
-            raise ValueError("dst must be a contiguous uint8 array of at least dst_bytes")
-        res = (A.Result * n)()
-        check(self.lib.alz_decode_batch(self.h, C.byref(lz) if lz is not None else None, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_decode_batch, (_ref(lz),), streams, src, dst_bytes, dst)
 
     def decode(self, fmt, src, decom_len=0, cap=None, aux0=0, aux1=0, lz=None):
         src = bytes(src)
         cap = decom_len if cap is None else cap
         dst = np.empty(max(cap, 1), dtype=np.uint8)          # (untouched memory: a ctypes buffer would be written full of zeros first)
         r = A.Result()
-        check(self.lib.alz_decode(self.h, fmt, C.byref(lz) if lz is not None else None, src, len(src), decom_len, aux0, aux1, _vp(dst), cap, C.byref(r)))
+        check(self.lib.alz_decode(self.h, fmt, _ref(lz), src, len(src), decom_len, aux0, aux1, _vp(dst), cap, C.byref(r)))
         return dst[:r.dst_len].tobytes(), r
 
     # ---- decoded sizes without decoding
     def measure_batch(self, streams, src, lz=None):
         """alz_measure_batch on a host buffer: the results alz_decode_batch would return for `streams` (status, dst_len, src_used), nothing decoded.
         dst_off is ignored and dst_cap only bounds the count (A.MEASURE_NO_BOUND: the true size)."""
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        res = (A.Result * n)()
-        check(self.lib.alz_measure_batch(self.h, C.byref(lz) if lz is not None else None, n, _vp(src), src.nbytes, streams, res))
-        return res
+        return self._host_measure(self.lib.alz_measure_batch, (_ref(lz),), streams, src)
 
     def measure_batch_device(self, streams, d_src, src_bytes, lz=None):
         """alz_measure_batch_device: the same with the source already in HBM at d_src; last_kernel_ms() is the device time of the launches."""
-        n = len(streams)
-        res = (A.Result * n)()
-        check(self.lib.alz_measure_batch_device(self.h, C.byref(lz) if lz is not None else None, n, d_src, src_bytes, streams, res))
-        return res
+        return self._device(self.lib.alz_measure_batch_device, (_ref(lz),), streams, d_src, src_bytes)
 
     # ---- RLE30 / HUF20: the non-LZ bodies of the GBA / DS family (streams[i].format is an A.RLH_* value)
-    def _rlh_host(self, fn, streams, src, dst_bytes):
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
-        res = (A.Result * n)()
-        check(fn(self.h, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
-        return dst, res
-
     def rlh_decode_batch(self, streams, src, dst_bytes):
         """alz_rlh_decode_batch on host buffers: RLE30 / HUF20 bodies; aux0 of a HUF20_4 stream is the nibble order (1 = big, Level5)."""
-        return self._rlh_host(self.lib.alz_rlh_decode_batch, streams, src, dst_bytes)
+        return self._host_decode(self.lib.alz_rlh_decode_batch, (), streams, src, dst_bytes)
 
     def rlh_encode_batch(self, streams, src, dst_bytes):
         """alz_rlh_encode_batch: RLE30.CompressHeaderless of raw buffers (a HUF format raises AlzError E_UNSUPPORTED: there is no encoder)."""
-        return self._rlh_host(self.lib.alz_rlh_encode_batch, streams, src, dst_bytes)
+        return self._host_decode(self.lib.alz_rlh_encode_batch, (), streams, src, dst_bytes)
 
     def rlh_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
         """alz_rlh_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
-        res = (A.Result * len(streams))()
-        check(self.lib.alz_rlh_decode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
-        return res
+        return self._device(self.lib.alz_rlh_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
     def rlh_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
         """alz_rlh_encode_batch_device: raw buffers in HBM at d_src, RLE30 streams left at d_dst."""
-        res = (A.Result * len(streams))()
-        check(self.lib.alz_rlh_encode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
-        return res
+        return self._device(self.lib.alz_rlh_encode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
     # ---- aPLib (decode only): headerless bodies; format, decom_len, aux0 and aux1 of a stream are ignored
     def aplib_decode_batch(self, streams, src, dst_bytes, dst=None):
         """alz_aplib_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        if dst is None:
-            dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
-        elif dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.nbytes < dst_bytes:
-            raise ValueError("dst must be a contiguous uint8 array of at least dst_bytes")
-        res = (A.Result * n)()
-        check(self.lib.alz_aplib_decode_batch(self.h, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_aplib_decode_batch, (), streams, src, dst_bytes, dst)
 
     def aplib_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
         """alz_aplib_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launch."""
-        res = (A.Result * len(streams))()
-        check(self.lib.alz_aplib_decode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
-        return res
+        return self._device(self.lib.alz_aplib_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
     def aplib_measure_batch(self, streams, src):
         """alz_aplib_measure_batch on a host buffer: the results aplib_decode_batch would return, nothing decoded; dst_cap only bounds the count."""
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        res = (A.Result * n)()
-        check(self.lib.alz_aplib_measure_batch(self.h, n, _vp(src), src.nbytes, streams, res))
-        return res
+        return self._host_measure(self.lib.alz_aplib_measure_batch, (), streams, src)
 
     def aplib_measure_batch_device(self, streams, d_src, src_bytes):
         """alz_aplib_measure_batch_device: the same with the source already in HBM at d_src."""
-        res = (A.Result * len(streams))()
-        check(self.lib.alz_aplib_measure_batch_device(self.h, len(streams), d_src, src_bytes, streams, res))
-        return res
+        return self._device(self.lib.alz_aplib_measure_batch_device, (), streams, d_src, src_bytes)
 
     # ---- CRILAYLA / ALLZ (decode only): headerless bodies; streams[i].format is an A.BITLZ_* value
     def bitlz_decode_batch(self, streams, src, dst_bytes, dst=None):
         """alz_bitlz_decode_batch on host buffers.  A CRILAYLA stream's dst_len bytes end at dst_off + dst_cap (it is written from the top down);
         an ALLZ stream takes decom_len and aux0 = A.allz_aux0(copy, dist, len).  `dst`: a caller-owned uint8 array of >= dst_bytes (default: a new one)."""
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        if dst is None:
-            dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
-        elif dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.nbytes < dst_bytes:
-            raise ValueError("dst must be a contiguous uint8 array of at least dst_bytes")
-        res = (A.Result * n)()
-        check(self.lib.alz_bitlz_decode_batch(self.h, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_bitlz_decode_batch, (), streams, src, dst_bytes, dst)
 
     def bitlz_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
         """alz_bitlz_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
-        res = (A.Result * len(streams))()
-        check(self.lib.alz_bitlz_decode_batch_device(self.h, len(streams), d_src, src_bytes, streams, d_dst, dst_bytes, res))
-        return res
+        return self._device(self.lib.alz_bitlz_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):

@@ -363,6 +363,15 @@ void alz_plan_destroy(alz_ctx* c, alz_plan* p) {
 }
 
 static int grow(alz_ctx* c, void** buf, size_t* cap, size_t need);
+// The three device tables of a batch of n streams -- streams | results | index, the first two rounded up to 256 bytes -- out of the context's
+// grow-only plan scratch, which one batch at a time uses
+struct plan_tables { alz_stream* streams; alz_result* results; uint32_t* index; };
+static int carve_plan_scratch(alz_ctx* c, size_t n, plan_tables* t) {
+    const size_t a = (n * sizeof(alz_stream) + 255) & ~(size_t)255, b = (n * sizeof(alz_result) + 255) & ~(size_t)255;
+    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + n * sizeof(uint32_t))) return rc;
+    t->streams = (alz_stream*)c->d_plan; t->results = (alz_result*)((uint8_t*)c->d_plan + a); t->index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
+    return ALZ_OK;
+}
 // `scratch`: the plan's device arrays come out of the context's grow-only plan scratch (one plan at a time: the host-buffer
 // entry points, which create, run and drop a plan inside one call -- a hipMalloc / hipFree trio per call cost more than the
 // kernel of a small batch)
@@ -399,10 +408,10 @@ static int plan_create(alz_ctx* c, const alz_lz_properties* props, uint32_t n, c
     size_t nn = n ? n : 1;
     hipError_t e = hipSuccess;
     if (scratch) {
-        const size_t a = (nn * sizeof(alz_stream) + 255) & ~(size_t)255, b = (nn * sizeof(alz_result) + 255) & ~(size_t)255;
-        if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + nn * sizeof(uint32_t))) { delete p; return rc; }
+        plan_tables t;
+        if (int rc = carve_plan_scratch(c, nn, &t)) { delete p; return rc; }
         p->borrowed = true;
-        p->d_streams = (alz_stream*)c->d_plan; p->d_results = (alz_result*)((uint8_t*)c->d_plan + a); p->d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
+        p->d_streams = t.streams; p->d_results = t.results; p->d_index = t.index;
     } else {
         e = hipMalloc((void**)&p->d_streams, nn * sizeof(alz_stream));
         if (e == hipSuccess) e = hipMalloc((void**)&p->d_results, nn * sizeof(alz_result));
@@ -851,12 +860,14 @@ static int download_segs(alz_ctx* c, std::vector<out_seg>& segs) {
     return download_windows(c, c->d_dst, segs);
 }
 
-static int download_outputs(alz_ctx* c, uint32_t n, const alz_stream* streams, const alz_result* results, uint8_t* dst_base, bool only_ok) {
+// crilayla_top: the batch is one of alz_bitlz_kind, and a CRILAYLA stream's bytes lie at the TOP of its span
+static int download_outputs(alz_ctx* c, uint32_t n, const alz_stream* streams, const alz_result* results, uint8_t* dst_base, bool only_ok, bool crilayla_top = false) {
     std::vector<out_seg> segs;
     segs.reserve(n);
     for (uint32_t i = 0; i < n; i++) {
         if (!results[i].dst_len || (only_ok && results[i].status != ALZ_ST_OK)) continue;
-        segs.push_back(out_seg{streams[i].dst_off, dst_base + streams[i].dst_off, results[i].dst_len});
+        const uint64_t at = streams[i].dst_off + (crilayla_top && streams[i].format == ALZ_BITLZ_CRILAYLA ? streams[i].dst_cap - results[i].dst_len : 0u);
+        segs.push_back(out_seg{at, dst_base + at, results[i].dst_len});
     }
     return download_segs(c, segs);
 }
@@ -915,113 +926,59 @@ int alz_decode(alz_ctx* c, uint32_t format, const alz_lz_properties* props, cons
     return alz_decode_batch(c, props, 1, src, src_len, &s, dst, dst_cap, result);
 }
 
-// ---------------------------------------------------------------- measure: decoded sizes without decoding (alz_measure.hip)
-// Grouped per format like a plan (one launch per format present, longest streams first inside a launch), on the context's stream; the
-// three tables live in the context's plan scratch.  No destination: dst_off is not looked at, dst_cap bounds the count.
-int alz_measure_batch_device(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
-                             const alz_stream* streams, alz_result* results) {
-    if (!c || (n && (!streams || !results || !d_src_base))) return fail(ALZ_E_INVALID, "alz_measure_batch: bad argument");
-    const alz_lz_properties lz = effective_lz(props);
-    uint32_t cnt[ALZ_FMT_COUNT] = {0}, off[ALZ_FMT_COUNT] = {0}, fill[ALZ_FMT_COUNT] = {0};
-    for (uint32_t i = 0; i < n; i++) {
-        if (streams[i].format >= ALZ_FMT_COUNT) return fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, streams[i].format);
-        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
-        cnt[streams[i].format]++;
-    }
-    if (cnt[ALZ_FMT_LZSS] && (lz.window_bits < 8 || lz.window_bits > 16 || lz.length_bits < 1 || lz.length_bits > 8))
-        return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path (window_bits 8..16, length_bits 1..8)");
-    c->last_kernel_ms = 0.f;
-    if (n == 0) return ALZ_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint32_t> index(n);
-    for (int f = 1; f < ALZ_FMT_COUNT; f++) off[f] = off[f - 1] + cnt[f - 1];
-    for (uint32_t i = 0; i < n; i++) { const uint32_t f = streams[i].format; index[off[f] + fill[f]++] = i; }
-    for (int f = 0; f < ALZ_FMT_COUNT; f++)     // a stream's cost is its tokens: the compressed bytes
-        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
-    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
-    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
-    alz_stream* d_streams = (alz_stream*)c->d_plan;
-    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
-    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
-    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    for (int f = 0; f < ALZ_FMT_COUNT && e == hipSuccess; f++)
-        if (cnt[f]) e = alz_launch_measure(f, c->stream, d_src_base, d_streams, d_index + off[f], cnt[f], d_results, &lz, c->exact);
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ALZ_E_HIP, "alz_measure_batch failed: %s", hipGetErrorString(e));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
-    return ALZ_OK;
-}
+// ---------------------------------------------------------------- the batch core of the entry-point families that have no plan object
+// measure (alz_measure.hip), RLE30 / HUF20 (alz_rlh.hip), aPLib (alz_aplib.hip) and CRILAYLA / ALLZ (alz_bitlz.hip).  One call is one batch,
+// grouped per kind like a plan (one launch per kind present, longest streams first inside a launch), on the context's stream; the three
+// tables live in the context's plan scratch and the results come back to the host.  A family supplies its name, the number of kinds its
+// `format` field selects among (1: the field is ignored), which bytes its host form downloads, the refusals only it has, and its launch.
+extern "C++" {   // (templates)
+enum batch_download {
+    DL_NO_DST,            // a measure family: no destination, dst_off is not looked at and dst_cap only bounds the count
+    DL_PRODUCED,          // [dst_off, dst_off + dst_len) of every stream, whatever its status (as alz_decode_batch)
+    DL_ONLY_OK,           // ... of the streams that are ALZ_ST_OK (an encoder: as alz_encode_batch)
+    DL_CRILAYLA_TOP       // DL_PRODUCED, but a CRILAYLA stream's bytes END at dst_off + dst_cap (it is written from the top down)
+};
+// the arguments every one of these entry points takes; src / dst are device pointers in a device form (dst NULL where there is none)
+struct batch_args { uint32_t n; const uint8_t* src; size_t src_bytes; const alz_stream* streams; uint8_t* dst; size_t dst_bytes; alz_result* results; };
+static const uint32_t kMaxKinds = ALZ_FMT_COUNT;
+static_assert(ALZ_RLH_COUNT <= kMaxKinds && ALZ_BITLZ_COUNT <= kMaxKinds, "the per-kind counters of grouped_core");
 
-int alz_measure_batch(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* src_base, size_t src_bytes,
-                      const alz_stream* streams, alz_result* results) {
-    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base)) return fail(ALZ_E_INVALID, "alz_measure_batch: bad argument");
-    for (uint32_t i = 0; i < n; i++)
-        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
-    return alz_measure_batch_device(c, props, n, (const uint8_t*)c->d_src, src_bytes, streams, results);
-}
-
-// ---------------------------------------------------------------- RLE30 / HUF20: the non-LZ bodies of the GBA / DS family (alz_rlh.hip)
-// An entry-point family of its own, shaped like measure: grouped per alz_rlh_format (one launch per format present, longest
-// streams first), on the context's stream, tables in the context's plan scratch, results to the host.
-// what a call is refused for, before anything is allocated or copied
-static int rlh_validate(bool encode, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes) {
-    const char* what = encode ? "alz_rlh_encode_batch" : "alz_rlh_decode_batch";
-    for (uint32_t i = 0; i < n; i++) {
-        const alz_stream& s = streams[i];
-        if (s.format >= ALZ_RLH_COUNT) return fail(ALZ_E_INVALID, "%s: stream %u: unknown alz_rlh_format %u", what, i, s.format);
-        if (!range_ok(s.src_off, s.src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: source range exceeds src_bytes", what, i);
-        if (!range_ok(s.dst_off, s.dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: destination range exceeds dst_bytes", what, i);
-        if (s.format != ALZ_RLH_RLE30) {
-            // HuffmanTree.CreateTree sorts equal frequencies with the unstable List.Sort(): the managed bytes are not a function of the input
-            if (encode) return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: HUF20 has no encoder (the managed output is not a function of its input)", what, i);
-            if (s.decom_len >= 0x10000000u)   // symbolsToDecompress = destination.Length * 8 / bitDepth overflows the managed int  HUF20.cs:117
-                return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: HUF20 decom_len >= 0x10000000", what, i);
-        }
+// what every family refuses a call for: an unknown kind, a source or (where there is one) a destination range outside the stated sizes
+static int validate_streams(const char* what, uint32_t kinds, bool has_dst, const batch_args& a) {
+    for (uint32_t i = 0; i < a.n; i++) {
+        const alz_stream& s = a.streams[i];
+        if (kinds > 1 && s.format >= kinds) return fail(ALZ_E_INVALID, "%s: stream %u: unknown format / kind %u", what, i, s.format);
+        if (!range_ok(s.src_off, s.src_len, a.src_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: source range exceeds src_bytes", what, i);
+        if (has_dst && !range_ok(s.dst_off, s.dst_cap, a.dst_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: destination range exceeds dst_bytes", what, i);
     }
     return ALZ_OK;
 }
+static int no_refusals() { return ALZ_OK; }
 
-static int rlh_core(alz_ctx* c, bool encode, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
-                    uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
-    const char* what = encode ? "alz_rlh_encode_batch" : "alz_rlh_decode_batch";
-    uint32_t cnt[ALZ_RLH_COUNT] = {0}, off[ALZ_RLH_COUNT] = {0}, fill[ALZ_RLH_COUNT] = {0};
-    if (int rc = rlh_validate(encode, n, src_bytes, streams, dst_bytes)) return rc;
-    for (uint32_t i = 0; i < n; i++) cnt[streams[i].format]++;
+// n > 0 validated streams: group, sort, upload the tables, one launch(kind, d_streams, d_index of the kind, count, d_results) -> hipError_t per
+// kind present between the two events, results to the host, wait.
+template <class Launch>
+static int grouped_core(alz_ctx* c, const char* what, uint32_t kinds, uint32_t n, const alz_stream* streams, alz_result* results, Launch launch) {
+    uint32_t cnt[kMaxKinds] = {0}, off[kMaxKinds] = {0}, fill[kMaxKinds] = {0};
+    auto kind_of = [&](uint32_t i) { return kinds > 1 ? streams[i].format : 0u; };
+    for (uint32_t i = 0; i < n; i++) cnt[kind_of(i)]++;
     c->last_kernel_ms = 0.f;
-    if (n == 0) return ALZ_OK;
     HIP_TRY(hipSetDevice(c->device));
     std::vector<uint32_t> index(n);
-    for (int f = 1; f < ALZ_RLH_COUNT; f++) off[f] = off[f - 1] + cnt[f - 1];
-    for (uint32_t i = 0; i < n; i++) { const uint32_t f = streams[i].format; index[off[f] + fill[f]++] = i; }
-    for (int f = 0; f < ALZ_RLH_COUNT; f++)
+    for (uint32_t f = 1; f < kinds; f++) off[f] = off[f - 1] + cnt[f - 1];
+    for (uint32_t i = 0; i < n; i++) { const uint32_t f = kind_of(i); index[off[f] + fill[f]++] = i; }
+    for (uint32_t f = 0; f < kinds; f++)     // a stream's cost is its tokens: the compressed bytes
         if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
-    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
-    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
-    alz_stream* d_streams = (alz_stream*)c->d_plan;
-    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
-    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
-    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+    plan_tables t;
+    if (int rc = carve_plan_scratch(c, n, &t)) return rc;
+    hipError_t e = hipMemcpyAsync(t.streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t.index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t.results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
     if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    for (int f = 0; f < ALZ_RLH_COUNT && e == hipSuccess; f++) {
-        if (!cnt[f]) continue;
-        e = encode ? alz_launch_rlh_encode(f, c->stream, d_src_base, d_dst_base, d_streams, d_index + off[f], cnt[f], d_results, c->exact)
-                   : alz_launch_rlh_decode(f, c->stream, d_src_base, d_dst_base, d_streams, d_index + off[f], cnt[f], d_results, c->exact);
-    }
+    for (uint32_t f = 0; f < kinds && e == hipSuccess; f++)
+        if (cnt[f]) e = launch(f, t.streams, t.index + off[f], cnt[f], t.results);
     if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, t.results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
@@ -1030,191 +987,136 @@ static int rlh_core(alz_ctx* c, bool encode, uint32_t n, const uint8_t* d_src_ba
     return ALZ_OK;
 }
 
-static int rlh_host(alz_ctx* c, bool encode, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
-                    uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return fail(ALZ_E_INVALID, "alz_rlh_%s_batch: bad argument", encode ? "encode" : "decode");
-    if (n == 0) return ALZ_OK;
+// One entry point, host or device form: the argument check, the empty batch, validation (once, before anything is allocated or copied: a
+// refused call pays for no upload), the host form's staging of the source, the core, the host form's download.
+// refuse() -> int: the family's own refusals; launch(kind, d_src, d_dst, d_streams, d_index, count, d_results) -> hipError_t.
+template <class Refuse, class Launch>
+static int batch_call(alz_ctx* c, const char* what, uint32_t kinds, batch_download rule, bool device, const batch_args& a, Refuse refuse, Launch launch) {
+    const bool has_dst = rule != DL_NO_DST;
+    const bool missing = device ? a.n && (!a.streams || !a.results || !a.src || (has_dst && !a.dst))
+                                : (a.n && (!a.streams || !a.results)) || (a.src_bytes && !a.src) || (has_dst && a.dst_bytes && !a.dst);
+    if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
+    if (a.n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
     int rc;
-    if ((rc = rlh_validate(encode, n, src_bytes, streams, dst_bytes))) return rc;   // (first, as alz_decode_batch: a refused call pays for no upload)
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
-    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
-    if ((rc = rlh_core(c, encode, n, (const uint8_t*)c->d_src, src_bytes, streams, (uint8_t*)c->d_dst, dst_bytes, results))) return rc;
-    return download_outputs(c, n, streams, results, dst_base, encode);   // decode: what each stream produced, whatever its status (as alz_decode_batch)
+    if ((rc = validate_streams(what, kinds, has_dst, a))) return rc;
+    if ((rc = refuse())) return rc;
+    const uint8_t* d_src = a.src;
+    uint8_t* d_dst = a.dst;
+    if (!device) {
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = grow(c, &c->d_src, &c->d_src_cap, a.src_bytes + 64))) return rc;
+        if (has_dst && (rc = grow(c, &c->d_dst, &c->d_dst_cap, a.dst_bytes + 64))) return rc;
+        if ((rc = staged_h2d(c, c->d_src, a.src, a.src_bytes))) return rc;
+        d_src = (const uint8_t*)c->d_src;
+        d_dst = has_dst ? (uint8_t*)c->d_dst : nullptr;
+    }
+    rc = grouped_core(c, what, kinds, a.n, a.streams, a.results, [&](uint32_t kind, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+        return launch(kind, d_src, d_dst, d_streams, d_index, count, d_results);
+    });
+    if (rc || device || !has_dst) return rc;
+    return download_outputs(c, a.n, a.streams, a.results, a.dst, rule == DL_ONLY_OK, rule == DL_CRILAYLA_TOP);
+}
+}   // extern "C++"
+
+// ---------------------------------------------------------------- measure: decoded sizes without decoding (alz_measure.hip); kinds: alz_format
+static int measure_batch(alz_ctx* c, bool device, const alz_lz_properties* props, const batch_args& a) {
+    const alz_lz_properties lz = effective_lz(props);
+    return batch_call(c, "alz_measure_batch", ALZ_FMT_COUNT, DL_NO_DST, device, a,
+        [&]() -> int {
+            if (lz.window_bits >= 8 && lz.window_bits <= 16 && lz.length_bits >= 1 && lz.length_bits <= 8) return ALZ_OK;
+            for (uint32_t i = 0; i < a.n; i++)
+                if (a.streams[i].format == ALZ_FMT_LZSS) return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path (window_bits 8..16, length_bits 1..8)");
+            return ALZ_OK;
+        },
+        [&](uint32_t f, const uint8_t* d_src, uint8_t*, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+            return alz_launch_measure((int)f, c->stream, d_src, d_streams, d_index, count, d_results, &lz, c->exact);
+        });
+}
+int alz_measure_batch(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                      const alz_stream* streams, alz_result* results) {
+    return measure_batch(c, false, props, {n, src_base, src_bytes, streams, nullptr, 0, results});
+}
+int alz_measure_batch_device(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                             const alz_stream* streams, alz_result* results) {
+    return measure_batch(c, true, props, {n, d_src_base, src_bytes, streams, nullptr, 0, results});
 }
 
+// ---------------------------------------------------------------- RLE30 / HUF20: the non-LZ bodies of the GBA / DS family (alz_rlh.hip); kinds: alz_rlh_format
+static int rlh_batch(alz_ctx* c, bool device, bool encode, const batch_args& a) {
+    const char* what = encode ? "alz_rlh_encode_batch" : "alz_rlh_decode_batch";
+    return batch_call(c, what, ALZ_RLH_COUNT, encode ? DL_ONLY_OK : DL_PRODUCED, device, a,
+        [&]() -> int {
+            for (uint32_t i = 0; i < a.n; i++) {
+                if (a.streams[i].format == ALZ_RLH_RLE30) continue;
+                // HuffmanTree.CreateTree sorts equal frequencies with the unstable List.Sort(): the managed bytes are not a function of the input
+                if (encode) return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: HUF20 has no encoder (the managed output is not a function of its input)", what, i);
+                if (a.streams[i].decom_len >= 0x10000000u)   // symbolsToDecompress = destination.Length * 8 / bitDepth overflows the managed int  HUF20.cs:117
+                    return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: HUF20 decom_len >= 0x10000000", what, i);
+            }
+            return ALZ_OK;
+        },
+        [&](uint32_t f, const uint8_t* d_src, uint8_t* d_dst, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+            return encode ? alz_launch_rlh_encode((int)f, c->stream, d_src, d_dst, d_streams, d_index, count, d_results, c->exact)
+                          : alz_launch_rlh_decode((int)f, c->stream, d_src, d_dst, d_streams, d_index, count, d_results, c->exact);
+        });
+}
 int alz_rlh_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                          uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
-    return rlh_host(c, false, n, src_base, src_bytes, streams, dst_base, dst_bytes, results);
+    return rlh_batch(c, false, false, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
 }
 int alz_rlh_encode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                          uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
-    return rlh_host(c, true, n, src_base, src_bytes, streams, dst_base, dst_bytes, results);
+    return rlh_batch(c, false, true, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
 }
 int alz_rlh_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                 uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_rlh_decode_batch_device: bad argument");
-    return rlh_core(c, false, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
+    return rlh_batch(c, true, false, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
 }
 int alz_rlh_encode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                 uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_rlh_encode_batch_device: bad argument");
-    return rlh_core(c, true, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
+    return rlh_batch(c, true, true, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
 }
 
 // ---------------------------------------------------------------- aPLib: the last LzWindows user (alz_aplib.hip)
-// Decode and measure, shaped like the family above: one launch, longest streams first, on the context's stream, tables in the context's
-// plan scratch, results to the host.  `format`, decom_len, aux0 and aux1 of a stream are ignored.  measure: no destination (d_dst_base NULL).
-static int aplib_validate(bool measure, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes) {
-    const char* what = measure ? "alz_aplib_measure_batch" : "alz_aplib_decode_batch";
-    for (uint32_t i = 0; i < n; i++) {
-        const alz_stream& s = streams[i];
-        if (!range_ok(s.src_off, s.src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: source range exceeds src_bytes", what, i);
-        if (!measure && !range_ok(s.dst_off, s.dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: destination range exceeds dst_bytes", what, i);
-    }
-    return ALZ_OK;
+// Decode and measure.  One kind: `format`, decom_len, aux0 and aux1 of a stream are ignored.
+static int aplib_batch(alz_ctx* c, bool device, bool measure, const batch_args& a) {
+    return batch_call(c, measure ? "alz_aplib_measure_batch" : "alz_aplib_decode_batch", 1, measure ? DL_NO_DST : DL_PRODUCED, device, a, no_refusals,
+        [&](uint32_t, const uint8_t* d_src, uint8_t* d_dst, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+            return measure ? alz_launch_aplib_measure(c->stream, d_src, d_streams, d_index, count, d_results)
+                           : alz_launch_aplib_decode(c->stream, d_src, d_dst, d_streams, d_index, count, d_results,
+                                                     c->exact ? ALZ_APLIB_EXACT : (c->variant != 0 ? ALZ_APLIB_PRODUCTION : ALZ_APLIB_DEFAULT));
+        });
 }
-
-static int aplib_core(alz_ctx* c, bool measure, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
-                      uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
-    const char* what = measure ? "alz_aplib_measure_batch" : "alz_aplib_decode_batch";
-    if (int rc = aplib_validate(measure, n, src_bytes, streams, dst_bytes)) return rc;
-    c->last_kernel_ms = 0.f;
-    if (n == 0) return ALZ_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint32_t> index(n);
-    for (uint32_t i = 0; i < n; i++) index[i] = i;
-    if (n > 1) std::stable_sort(index.begin(), index.end(), [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });   // a stream's cost is its tokens
-    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
-    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
-    alz_stream* d_streams = (alz_stream*)c->d_plan;
-    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
-    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
-    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess)
-        e = measure ? alz_launch_aplib_measure(c->stream, d_src_base, d_streams, d_index, n, d_results)
-                    : alz_launch_aplib_decode(c->stream, d_src_base, d_dst_base, d_streams, d_index, n, d_results,
-                                              c->exact ? ALZ_APLIB_EXACT : (c->variant != 0 ? ALZ_APLIB_PRODUCTION : ALZ_APLIB_DEFAULT));
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
-    return ALZ_OK;
-}
-
 int alz_aplib_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                            uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return fail(ALZ_E_INVALID, "alz_aplib_decode_batch: bad argument");
-    if (n == 0) return ALZ_OK;
-    int rc;
-    if ((rc = aplib_validate(false, n, src_bytes, streams, dst_bytes))) return rc;   // (first: a refused call pays for no upload)
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
-    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
-    if ((rc = aplib_core(c, false, n, (const uint8_t*)c->d_src, src_bytes, streams, (uint8_t*)c->d_dst, dst_bytes, results))) return rc;
-    return download_outputs(c, n, streams, results, dst_base, false);   // what each stream produced, whatever its status (as alz_decode_batch)
+    return aplib_batch(c, false, false, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
 }
 int alz_aplib_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                   uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_aplib_decode_batch_device: bad argument");
-    return aplib_core(c, false, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
-}
-int alz_aplib_measure_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
-    if (!c || (n && (!streams || !results || !d_src_base))) return fail(ALZ_E_INVALID, "alz_aplib_measure_batch_device: bad argument");
-    return aplib_core(c, true, n, d_src_base, src_bytes, streams, nullptr, 0, results);
+    return aplib_batch(c, true, false, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
 }
 int alz_aplib_measure_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
-    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base)) return fail(ALZ_E_INVALID, "alz_aplib_measure_batch: bad argument");
-    if (n == 0) return ALZ_OK;
-    int rc;
-    if ((rc = aplib_validate(true, n, src_bytes, streams, 0))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
-    return aplib_core(c, true, n, (const uint8_t*)c->d_src, src_bytes, streams, nullptr, 0, results);
+    return aplib_batch(c, false, true, {n, src_base, src_bytes, streams, nullptr, 0, results});
+}
+int alz_aplib_measure_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
+    return aplib_batch(c, true, true, {n, d_src_base, src_bytes, streams, nullptr, 0, results});
 }
 
 // ---------------------------------------------------------------- CRILAYLA / ALLZ: the bit-stream LZ bodies of the .Extended assembly (alz_bitlz.hip)
-// Decode only, shaped like the families above: grouped per alz_bitlz_kind (one launch per kind present, longest streams first), on the
-// context's stream, tables in the context's plan scratch, results to the host.  Each kind has one kernel, so all three context modes run
-// it.
-static int bitlz_validate(uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes) {
-    for (uint32_t i = 0; i < n; i++) {
-        const alz_stream& s = streams[i];
-        if (s.format >= ALZ_BITLZ_COUNT) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: stream %u: unknown alz_bitlz_kind %u", i, s.format);
-        if (!range_ok(s.src_off, s.src_len, src_bytes)) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: stream %u: source range exceeds src_bytes", i);
-        if (!range_ok(s.dst_off, s.dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: stream %u: destination range exceeds dst_bytes", i);
-    }
-    return ALZ_OK;
+// Decode only; kinds: alz_bitlz_kind.  Each kind has one kernel, so all three context modes run it.
+static int bitlz_batch(alz_ctx* c, bool device, const batch_args& a) {
+    return batch_call(c, "alz_bitlz_decode_batch", ALZ_BITLZ_COUNT, DL_CRILAYLA_TOP, device, a, no_refusals,
+        [&](uint32_t kind, const uint8_t* d_src, uint8_t* d_dst, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+            return alz_launch_bitlz_decode((int)kind, c->stream, d_src, d_dst, d_streams, d_index, count, d_results);
+        });
 }
-
-// (the streams are validated by the caller)
-static int bitlz_core(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, const alz_stream* streams, uint8_t* d_dst_base, alz_result* results) {
-    uint32_t cnt[ALZ_BITLZ_COUNT] = {0}, off[ALZ_BITLZ_COUNT] = {0}, fill[ALZ_BITLZ_COUNT] = {0};
-    for (uint32_t i = 0; i < n; i++) cnt[streams[i].format]++;
-    c->last_kernel_ms = 0.f;
-    if (n == 0) return ALZ_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint32_t> index(n);
-    for (int f = 1; f < ALZ_BITLZ_COUNT; f++) off[f] = off[f - 1] + cnt[f - 1];
-    for (uint32_t i = 0; i < n; i++) { const uint32_t f = streams[i].format; index[off[f] + fill[f]++] = i; }
-    for (int f = 0; f < ALZ_BITLZ_COUNT; f++)   // a stream's cost is its tokens
-        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
-    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = ((size_t)n * sizeof(alz_result) + 255) & ~(size_t)255;
-    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + (size_t)n * sizeof(uint32_t))) return rc;
-    alz_stream* d_streams = (alz_stream*)c->d_plan;
-    alz_result* d_results = (alz_result*)((uint8_t*)c->d_plan + a);
-    uint32_t* d_index = (uint32_t*)((uint8_t*)c->d_plan + a + b);
-    hipError_t e = hipMemcpyAsync(d_streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    for (int f = 0; f < ALZ_BITLZ_COUNT && e == hipSuccess; f++)
-        if (cnt[f]) e = alz_launch_bitlz_decode(f, c->stream, d_src_base, d_dst_base, d_streams, d_index + off[f], cnt[f], d_results);
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ALZ_E_HIP, "alz_bitlz_decode_batch failed: %s", hipGetErrorString(e));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
-    return ALZ_OK;
-}
-
 int alz_bitlz_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                            uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch: bad argument");
-    c->last_kernel_ms = 0.f;
-    if (n == 0) return ALZ_OK;
-    int rc;
-    if ((rc = bitlz_validate(n, src_bytes, streams, dst_bytes))) return rc;   // (first: a refused call pays for no upload)
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
-    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
-    if ((rc = bitlz_core(c, n, (const uint8_t*)c->d_src, streams, (uint8_t*)c->d_dst, results))) return rc;
-    std::vector<out_seg> segs;                                          // what each stream produced, whatever its status: CRILAYLA's at the TOP of its span
-    segs.reserve(n);
-    for (uint32_t i = 0; i < n; i++) {
-        if (!results[i].dst_len) continue;
-        const uint64_t at = streams[i].dst_off + (streams[i].format == ALZ_BITLZ_CRILAYLA ? streams[i].dst_cap - results[i].dst_len : 0u);
-        segs.push_back(out_seg{at, dst_base + at, results[i].dst_len});
-    }
-    return download_segs(c, segs);
+    return bitlz_batch(c, false, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
 }
 int alz_bitlz_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                   uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
-    if (!c || (n && (!streams || !results || !d_src_base || !d_dst_base))) return fail(ALZ_E_INVALID, "alz_bitlz_decode_batch_device: bad argument");
-    if (int rc = bitlz_validate(n, src_bytes, streams, dst_bytes)) return rc;
-    return bitlz_core(c, n, d_src_base, streams, d_dst_base, results);
+    return bitlz_batch(c, true, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
 }
 
 // Device buffers of one encode call, freed on every exit path
