@@ -127,4 +127,19 @@ BITLZ_PROTOTYPES = {
     "alz_allz_is_match": _BITLZ_IS_MATCH, "alz_allz_decompressed_size": _BITLZ_SIZE, "alz_allz_decompress": _BITLZ_DECOMPRESS,
 }
 
+# the DEFLATE entry points (decode only): batches of raw streams, their sizes without decoding, and the ZLib / GZip classes on a file in host memory
+INFLATE_WINDOW = 0x8000
+_INFLATE_DECODE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+_INFLATE_MEASURE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+_INFLATE_IS_MATCH = [C.c_void_p, C.c_size_t]
+_INFLATE_DECOMPRESS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+_INFLATE_FILE_MEASURE = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+INFLATE_PROTOTYPES = {
+    "alz_inflate_decode_batch": _INFLATE_DECODE, "alz_inflate_decode_batch_device": _INFLATE_DECODE,
+    "alz_inflate_measure_batch": _INFLATE_MEASURE, "alz_inflate_measure_batch_device": _INFLATE_MEASURE,
+    "alz_zlib_is_match": _INFLATE_IS_MATCH, "alz_gzip_is_match": _INFLATE_IS_MATCH,
+    "alz_zlib_decompress": _INFLATE_DECOMPRESS, "alz_gzip_decompress": _INFLATE_DECOMPRESS,
+    "alz_zlib_measure": _INFLATE_FILE_MEASURE, "alz_gzip_measure": _INFLATE_FILE_MEASURE,
+}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16

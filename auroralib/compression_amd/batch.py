@@ -181,6 +181,23 @@ class Context:
         """alz_bitlz_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
         return self._device(self.lib.alz_bitlz_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
+    # ---- DEFLATE (decode only): raw streams as zlib's inflate reads them; format, decom_len, aux0 and aux1 of a stream are ignored
+    def inflate_decode_batch(self, streams, src, dst_bytes, dst=None):
+        """alz_inflate_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
+        return self._host_decode(self.lib.alz_inflate_decode_batch, (), streams, src, dst_bytes, dst)
+
+    def inflate_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_inflate_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launch."""
+        return self._device(self.lib.alz_inflate_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
+
+    def inflate_measure_batch(self, streams, src):
+        """alz_inflate_measure_batch on a host buffer: the results inflate_decode_batch would return, nothing decoded; dst_cap only bounds the count."""
+        return self._host_measure(self.lib.alz_inflate_measure_batch, (), streams, src)
+
+    def inflate_measure_batch_device(self, streams, d_src, src_bytes):
+        """alz_inflate_measure_batch_device: the same with the source already in HBM at d_src."""
+        return self._device(self.lib.alz_inflate_measure_batch_device, (), streams, d_src, src_bytes)
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

@@ -21,6 +21,7 @@
 #include "alz_measure.h"
 #include "alz_rlh.h"
 #include "alz_aplib.h"
+#include "alz_inflate.h"
 #include "alz_bitlz.h"
 
 static thread_local char g_err[512] = "";
@@ -927,7 +928,7 @@ int alz_decode(alz_ctx* c, uint32_t format, const alz_lz_properties* props, cons
 }
 
 // ---------------------------------------------------------------- the batch core of the entry-point families that have no plan object
-// measure (alz_measure.hip), RLE30 / HUF20 (alz_rlh.hip), aPLib (alz_aplib.hip) and CRILAYLA / ALLZ (alz_bitlz.hip).  One call is one batch,
+// measure (alz_measure.hip), RLE30 / HUF20 (alz_rlh.hip), aPLib (alz_aplib.hip), CRILAYLA / ALLZ (alz_bitlz.hip) and DEFLATE (alz_inflate.hip).  One call is one batch,
 // grouped per kind like a plan (one launch per kind present, longest streams first inside a launch), on the context's stream; the three
 // tables live in the context's plan scratch and the results come back to the host.  A family supplies its name, the number of kinds its
 // `format` field selects among (1: the field is ignored), which bytes its host form downloads, the refusals only it has, and its launch.
@@ -1117,6 +1118,30 @@ int alz_bitlz_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size
 int alz_bitlz_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                   uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
     return bitlz_batch(c, true, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
+}
+
+// ---------------------------------------------------------------- DEFLATE: zlib's inflate over raw streams (alz_inflate.hip)
+// Decode and measure.  One kind: `format`, decom_len, aux0 and aux1 of a stream are ignored.  One kernel each, so all three context modes run it.
+static int inflate_batch(alz_ctx* c, bool device, bool measure, const batch_args& a) {
+    return batch_call(c, measure ? "alz_inflate_measure_batch" : "alz_inflate_decode_batch", 1, measure ? DL_NO_DST : DL_PRODUCED, device, a, no_refusals,
+        [&](uint32_t, const uint8_t* d_src, uint8_t* d_dst, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+            return measure ? alz_launch_inflate_measure(c->stream, d_src, d_streams, d_index, count, d_results)
+                           : alz_launch_inflate_decode(c->stream, d_src, d_dst, d_streams, d_index, count, d_results);
+        });
+}
+int alz_inflate_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                             uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return inflate_batch(c, false, false, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
+}
+int alz_inflate_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                    uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    return inflate_batch(c, true, false, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
+}
+int alz_inflate_measure_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
+    return inflate_batch(c, false, true, {n, src_base, src_bytes, streams, nullptr, 0, results});
+}
+int alz_inflate_measure_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
+    return inflate_batch(c, true, true, {n, d_src_base, src_bytes, streams, nullptr, 0, results});
 }
 
 // Device buffers of one encode call, freed on every exit path

@@ -576,6 +576,54 @@ class APLib:
         raise NotImplementedError(APLIB_NO_ENCODER)
 
 
+INFLATE_NO_ENCODER = ("%s has no encoder here: the reference hands Compress to the BCL, whose output depends on the zlib build behind it, "
+                      "so there are no managed bytes to be bit-identical with (include/auroralz.h)")
+
+
+class _InflateFile:
+    """A class of the reference that hands its body to the BCL, over its alz_<prefix>_* file entry points (alz_inflate_decode_batch underneath);
+    decode only.  No alz_container value backs it, so it stays outside ALL_FORMATS.  The format stores no size in front of the data."""
+    provides_size = False
+    prefix = None
+
+    def IsMatch(self, data):
+        data = bytes(data)
+        return bool(getattr(load(), "alz_%s_is_match" % self.prefix)(data, len(data)))
+
+    def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
+        """The decoded size of the file, counted on the GPU without decoding (alz_<prefix>_measure); checksums are taken as correct."""
+        data = bytes(data)
+        n, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
+        rc = getattr(load(), "alz_%s_measure" % self.prefix)(_context().h, data, len(data), limit, C.byref(n), C.byref(su), C.byref(st))
+        _raise_for_outcome(rc, st.value, n.value)
+        return n.value
+
+    def Decompress(self, data, cap=None):
+        """Decompress(Stream, Stream): with no `cap` the size is measured first."""
+        data = bytes(data)
+        if cap is None:
+            cap = self.MeasureDecompressedSize(data)
+        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
+        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
+        rc = getattr(load(), "alz_%s_decompress" % self.prefix)(_context().h, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl), C.byref(su), C.byref(st))
+        self.last_src_used = su.value
+        _raise_for_outcome(rc, st.value, dl.value)
+        return dst_arr[:dl.value].tobytes()
+
+    def Compress(self, data, settings=None):
+        raise NotImplementedError(INFLATE_NO_ENCODER % type(self).__name__)
+
+
+class ZLib(_InflateFile):
+    """src/AuroraLib.Compression/Formats/Common/ZLib.cs -- RFC 1950: CMF, FLG, a DEFLATE body, the Adler-32 of the output (alz_zlib_*)."""
+    prefix = "zlib"
+
+
+class GZip(_InflateFile):
+    """src/AuroraLib.Compression/Formats/Common/GZip.cs -- RFC 1952: members of header, DEFLATE body, CRC-32 and ISIZE (alz_gzip_*)."""
+    prefix = "gzip"
+
+
 BITLZ_NO_ENCODER = ("%s has no encoder here: CompressHeaderless runs the LzChainMatchFinder, the bar is bit-identity with the managed bytes checked against "
                     "the CPU oracle, and there is no oracle body to hold bit-identity against (include/auroralz.h)")
 

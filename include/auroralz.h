@@ -473,6 +473,88 @@ int alz_allz_decompressed_size(const uint8_t* src, size_t src_len, uint32_t* siz
 int alz_allz_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
                         size_t* dst_len, size_t* src_used, int32_t* status);
 
+/* ---------------------------------------- DEFLATE: raw streams, their sizes, ZLib and GZip files (decode only)
+ * The reference hands the bodies of its ZLib and GZip classes (src/AuroraLib.Compression/Formats/Common/ZLib.cs:30-34, GZip.cs:29-34) and
+ * of the zlib wrappers of its .Extended assembly to the BCL, so there is no managed loop to restate: the contract is RFC 1950 / 1951 /
+ * 1952 as zlib implements them.  DEFLATE is no alz_format and no alz_container: it has an entry-point family of its own, as aPLib has.
+ * alz_stream and alz_result are reused; decom_len, aux0, aux1 and format of a stream are IGNORED.  The slack rules are those of
+ * alz_aplib_* (64 readable bytes behind the last stream of both device buffers, never a write outside [dst_off, dst_off + dst_cap)).
+ * One wavefront decodes one stream.  There is ONE decode kernel and ONE measure kernel, so alz_ctx_set_exact_kernels,
+ * alz_ctx_set_kernel_variant and a context in neither mode give identical results by construction.  alz_last_kernel_ms reports the
+ * device time of the call's launch.
+ *
+ * The raw body: zlib's `inflate` with window bits -15 and no dictionary.  Bits are packed LSB first; blocks are read until the one
+ * with BFINAL ends.
+ *   block type 3       ALZ_ST_BAD_TOKEN.
+ *   stored block       the bits up to the byte boundary are dropped, LEN and NLEN are read; NLEN != ~LEN is BAD_TOKEN; LEN bytes are
+ *                      copied (LEN 0 is legal).
+ *   fixed block        literal/length symbols 286 and 287 and distance symbols 30 and 31 decode but are BAD_TOKEN when met.
+ *   dynamic block      each of these is BAD_TOKEN, detected when the block header is parsed, even if the block holds no symbol:
+ *                      HLIT + 257 > 286 or HDIST + 1 > 30; a code-length code that is over-subscribed or incomplete (one with no code at
+ *                      all included); repeat code 16 with no previous length; a repeat that runs past HLIT + HDIST + 258 lengths; length
+ *                      0 for symbol 256; a literal/length set or a distance set that is over-subscribed, or incomplete unless its longest
+ *                      code is 1 bit (a single code).  A distance set with no code at all is legal; a code that a set does not have
+ *                      (the unused code of a single-code set, any distance code of an empty set) is BAD_TOKEN when a stream uses it.  A
+ *                      repeat may run from the literal/length lengths into the distance lengths.
+ *   distance           larger than the bytes produced so far: BAD_TOKEN (nothing lies in front of a stream; the window is 32 KiB, the
+ *                      largest distance a symbol can name).  It is tested before capacity.
+ *   BAD_TOKEN          dst_len = what the symbols before the bad one produced; src_used unspecified.  The bits of a field are needed
+ *                      before the field is judged: a malformed field that the input cuts short is INPUT_TRUNCATED.
+ *   INPUT_TRUNCATED    the input ends before the final end-of-block.  dst_len = what the symbols whose bits are ALL present produced -- a
+ *                      length code, its extra bits, the distance code and its extra bits count as one symbol; of a stored block the
+ *                      bytes that exist are copied.  src_used = src_len.  Empty input: INPUT_TRUNCATED, dst_len 0.
+ *   OUTPUT_CAPACITY    a literal, match or stored run that does not fit dst_cap is clipped: dst_len = dst_cap, src_used unspecified.  It
+ *                      is raised only when a byte that does not fit is to be written (an end-of-block at dst_len == dst_cap is fine).
+ *   OK                 the final end-of-block was read; src_used is just behind the byte that holds its last bit (the rest of that byte
+ *                      is padding of either value).
+ * alz_inflate_measure_batch*: results[i] is what alz_inflate_decode_batch would return for streams[i] -- status, dst_len, and src_used
+ *   wherever it is defined; dst_off is ignored, dst_cap only bounds the count (0xFFFFFF00 for "the size"), nothing is written on the
+ *   device but the results.
+ * THERE IS NO ENCODER: the BCL's output depends on the zlib build behind it, so there are no managed bytes to be identical with.  Preset
+ *   dictionaries are not supported.  alz_brute_force and alz_container_scan do not try DEFLATE. */
+int alz_inflate_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                             uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_inflate_decode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                    uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+int alz_inflate_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                              alz_result* results);
+int alz_inflate_measure_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                     alz_result* results);
+/* The ZLib and GZip classes on a whole file in host memory.  Checksums are computed on the host over the downloaded output.  The header
+ * walks need no context (a NULL ctx is ALZ_E_INVALID only once a body has to be decoded).
+ * alz_zlib_is_match: ZLib.IsMatchStatic (ZLib.cs:26-27, :52-76) statement for statement: src_len > 4, CM == 8, CINFO <= 7,
+ *   (CMF * 256 + FLG) % 31 == 0, the first block's type is not 3, and for type 0 the test as written -- LEN is read from the first two
+ *   data bytes, is compared with its own complement and must not be 0.
+ * alz_gzip_is_match: src_len > 8 and the bytes 1F 8B 08 (GZip.cs:25-26).
+ * alz_zlib_decompress (RFC 1950): fewer than 2 bytes, CM != 8, CINFO > 7 or (CMF * 256 + FLG) % 31 != 0: ALZ_E_FORMAT; FDICT set:
+ *   ALZ_E_UNSUPPORTED.  CINFO does not limit distances (zlib opened with 15 window bits behaves this way).  The body decodes as one
+ *   stream; its errors pass through as ALZ_E_STREAM with their status and *src_used = 2 + the body's.  Fewer than 4 trailer bytes:
+ *   ALZ_E_STREAM / INPUT_TRUNCATED with the output delivered, *src_used = src_len.  The trailer is the big-endian Adler-32 of the
+ *   output: a mismatch is ALZ_E_CHECKSUM (the output is delivered).  *src_used = 2 + body + 4; bytes behind the trailer are not looked at.
+ * alz_gzip_decompress (RFC 1952): magic or CM wrong, or a reserved FLG bit set: ALZ_E_FORMAT; a header that runs past the input:
+ *   ALZ_E_STREAM / INPUT_TRUNCATED; FEXTRA, FNAME, FCOMMENT and FHCRC are skipped with bounds checks, FHCRC is verified against the low
+ *   16 bits of the CRC-32 of the header (ALZ_E_CHECKSUM).  The trailer is the CRC-32 of the member's output and ISIZE, its length mod
+ *   2^32: fewer than 8 bytes are ALZ_E_STREAM / INPUT_TRUNCATED with the output delivered, a mismatch of either is ALZ_E_CHECKSUM.
+ *   Members follow one another while the next two bytes are 1F 8B: each is decoded by a call of its own and the outputs are
+ *   concatenated (*dst_len counts all of them, also when a later member fails); any other trailing bytes end decoding without error.
+ *   On success *src_used = src_len (the reference sets source.Position = source.Length, GZip.cs:33).
+ * alz_zlib_measure / alz_gzip_measure: the alz_container_measure contract for these two classes -- rc, *status, *size_out (what
+ *   *dst_len would be) and *src_used of reading the file into size_limit bytes, the bodies measured on the GPU, with the Adler-32 /
+ *   CRC-32 taken as correct (they need the bytes; FHCRC and ISIZE are verified).  A size_limit below the true size gives
+ *   ALZ_E_STREAM / ALZ_ST_OUTPUT_CAPACITY.
+ * On ALZ_E_STREAM, *status holds the alz_status. */
+int alz_zlib_is_match(const uint8_t* src, size_t src_len);
+int alz_gzip_is_match(const uint8_t* src, size_t src_len);
+int alz_zlib_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
+                        size_t* dst_len, size_t* src_used, int32_t* status);
+int alz_gzip_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
+                        size_t* dst_len, size_t* src_used, int32_t* status);
+int alz_zlib_measure(alz_ctx* ctx, const uint8_t* src, size_t src_len, size_t size_limit,
+                     size_t* size_out, size_t* src_used, int32_t* status);
+int alz_gzip_measure(alz_ctx* ctx, const uint8_t* src, size_t src_len, size_t size_limit,
+                     size_t* size_out, size_t* src_used, int32_t* status);
+
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's
  * [dst_off, dst_off + dst_len) (tests/test_gpu_canary.py); they READ the input in aligned 16-byte granules and, for the 64 KiB

@@ -147,6 +147,28 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib)] internal static extern int alz_allz_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
             UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
 
+        // DEFLATE as zlib's inflate reads it (the body of ZLib / GZip, which the managed classes hand to the BCL), decode only: raw streams in
+        // batches (format, decomLen, aux0, aux1 of a stream are ignored), their sizes without decoding, and the two classes on a whole file in
+        // host memory (checksums verified on the host; *_measure takes them as correct)
+        [DllImport(Lib)] internal static extern int alz_inflate_decode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_inflate_decode_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_inflate_measure_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_inflate_measure_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_zlib_is_match(byte* src, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_gzip_is_match(byte* src, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_zlib_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
+            UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
+        [DllImport(Lib)] internal static extern int alz_gzip_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
+            UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
+        [DllImport(Lib)] internal static extern int alz_zlib_measure(IntPtr ctx, byte* src, UIntPtr srcLen, UIntPtr sizeLimit,
+            UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
+        [DllImport(Lib)] internal static extern int alz_gzip_measure(IntPtr ctx, byte* src, UIntPtr srcLen, UIntPtr sizeLimit,
+            UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
+
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
             byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);

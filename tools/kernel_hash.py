@@ -16,6 +16,7 @@ FAMILIES = {
     "rlh": ["alz_rlh.hip", "alz_rlh.h"],               # RLE30 / HUF20, the non-LZ bodies of the GBA / DS family: no committed counters
     "aplib": ["alz_aplib.hip", "alz_aplib.h"],         # aPLib, the 2 MiB-window LzWindows user (decode + measure): no committed counters
     "bitlz": ["alz_bitlz.hip", "alz_bitlz.h"],         # CRILAYLA / ALLZ, the bit-stream LZ bodies of the .Extended assembly (decode): no committed counters
+    "inflate": ["alz_inflate.hip", "alz_inflate.h"],   # DEFLATE as zlib's inflate reads it (decode + measure): no committed counters
 }
 FILES = ("traffic.json", "insts.json")
 
