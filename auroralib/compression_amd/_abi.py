@@ -142,4 +142,29 @@ INFLATE_PROTOTYPES = {
     "alz_zlib_measure": _INFLATE_FILE_MEASURE, "alz_gzip_measure": _INFLATE_FILE_MEASURE,
 }
 
-assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16
+# checksums of byte ranges on the GPU (a range is src_off / src_len of a Stream) and the host arithmetic that joins two of them
+CK_ADLER32 = 0
+CK_CRC32 = 1
+_CHECKSUM_BATCH = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+CHECKSUM_PROTOTYPES = {
+    "alz_checksum_batch": _CHECKSUM_BATCH, "alz_checksum_batch_device": _CHECKSUM_BATCH,
+    "alz_checksum_combine": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64],      # returns uint32_t (CHECKSUM_RESTYPES)
+}
+CHECKSUM_RESTYPES = {"alz_checksum_combine": C.c_uint32}
+
+# ZLib and GZip files in batches: Stream.format selects the class, one FileResult per file
+ZFILE_ZLIB = 0
+ZFILE_GZIP = 1
+
+
+class FileResult(C.Structure):
+    """alz_file_result: what the single-file call returns for the file -- its rc, the alz_status, bytes delivered, source bytes used"""
+    _fields_ = [("rc", C.c_int32), ("status", C.c_int32), ("dst_len", C.c_uint32), ("src_used", C.c_uint32)]
+
+
+ZFILE_PROTOTYPES = {
+    "alz_zfile_decode_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "alz_zfile_measure_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+}
+
+assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16 and C.sizeof(FileResult) == 16

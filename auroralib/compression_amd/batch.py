@@ -198,6 +198,38 @@ class Context:
         """alz_inflate_measure_batch_device: the same with the source already in HBM at d_src."""
         return self._device(self.lib.alz_inflate_measure_batch_device, (), streams, d_src, src_bytes)
 
+    # ---- checksums of byte ranges: kind is A.CK_ADLER32 or A.CK_CRC32; a range is src_off / src_len of its Stream
+    def _checksum(self, fn, kind, ranges, src, src_bytes):
+        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
+        check(fn(self.h, kind, len(ranges), src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:len(ranges)]
+
+    def checksum_batch(self, kind, ranges, src):
+        """alz_checksum_batch on a host buffer -> a uint32 array, one checksum per range."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        return self._checksum(self.lib.alz_checksum_batch, kind, ranges, _vp(src), src.nbytes)
+
+    def checksum_batch_device(self, kind, ranges, d_src, src_bytes):
+        """alz_checksum_batch_device: the same with the bytes already in HBM at d_src; last_kernel_ms() is the device time of the two launches."""
+        return self._checksum(self.lib.alz_checksum_batch_device, kind, ranges, d_src, src_bytes)
+
+    # ---- ZLib and GZip files in batches: Stream.format is A.ZFILE_ZLIB or A.ZFILE_GZIP, src_off / src_len the whole file
+    def zfile_decode_batch(self, files, src, dst_bytes, dst=None):
+        """alz_zfile_decode_batch on host buffers -> (dst, results): per file what alz_zlib_decompress / alz_gzip_decompress return for it alone.
+        `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        check(self.lib.alz_zfile_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def zfile_measure_batch(self, files, src):
+        """alz_zfile_measure_batch on a host buffer -> results: per file what alz_zlib_measure / alz_gzip_measure return; dst_cap is the size limit."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        res = (A.FileResult * len(files))()
+        check(self.lib.alz_zfile_measure_batch(self.h, len(files), _vp(src), src.nbytes, files, res))
+        return res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

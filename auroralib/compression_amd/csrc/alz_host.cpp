@@ -22,6 +22,7 @@
 #include "alz_rlh.h"
 #include "alz_aplib.h"
 #include "alz_inflate.h"
+#include "alz_checksum.h"
 #include "alz_bitlz.h"
 
 static thread_local char g_err[512] = "";
@@ -1142,6 +1143,69 @@ int alz_inflate_measure_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, s
 }
 int alz_inflate_measure_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
     return inflate_batch(c, true, true, {n, d_src_base, src_bytes, streams, nullptr, 0, results});
+}
+
+// ---------------------------------------------------------------- checksums: Adler-32 and CRC-32 of byte ranges (alz_checksum.hip); kinds: alz_checksum_kind
+// A range is src_off / src_len of its alz_stream, nothing else.  The tables (ranges, chunk prefix, chunk sums, results) live in the context's plan
+// scratch; the device writes nothing but them.
+static uint32_t g_checksum_chunk = ALZ_CHECKSUM_CHUNK;
+int alz_debug_checksum_chunk(uint32_t bytes) {   // bytes of a range one wavefront sums, for every context: 0 asks, a multiple of 1024 up to 1 MiB sets; returns the value in force
+    if (bytes && bytes % 1024u == 0 && bytes <= ALZ_CHECKSUM_CHUNK_MAX) g_checksum_chunk = bytes;
+    return (int)g_checksum_chunk;
+}
+static int checksum_batch(alz_ctx* c, bool device, uint32_t kind, uint32_t n, const uint8_t* src, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+    const char* what = device ? "alz_checksum_batch_device" : "alz_checksum_batch";
+    const bool missing = device ? n && (!ranges || !out || !src) : (n && (!ranges || !out)) || (src_bytes && !src);
+    if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
+    if (kind > ALZ_CK_CRC32) return fail(ALZ_E_INVALID, "%s: unknown kind %u", what, kind);
+    if (n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
+    const uint32_t chunk = g_checksum_chunk;
+    std::vector<uint32_t> first((size_t)n + 1);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!range_ok(ranges[i].src_off, ranges[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: range %u exceeds src_bytes", what, i);
+        first[i] = (uint32_t)total;
+        total += ((uint64_t)ranges[i].src_len + chunk - 1) / chunk;
+        if (total > 0x7FFFFFFFull) return fail(ALZ_E_UNSUPPORTED, "%s: more than 2^31 chunks of %u bytes", what, chunk);
+    }
+    first[n] = (uint32_t)total;
+    c->last_kernel_ms = 0.f;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    const uint8_t* d_src = src;
+    if (!device) {
+        if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+        if ((rc = staged_h2d(c, c->d_src, src, src_bytes))) return rc;
+        d_src = (const uint8_t*)c->d_src;
+    }
+    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = (((size_t)n + 1) * sizeof(uint32_t) + 255) & ~(size_t)255,
+                 p = ((size_t)total * sizeof(uint32_t) + 255) & ~(size_t)255;
+    if ((rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + p + (size_t)n * sizeof(uint32_t)))) return rc;
+    alz_stream* d_ranges = (alz_stream*)c->d_plan;
+    uint32_t* d_first = (uint32_t*)((uint8_t*)c->d_plan + a), *d_partial = (uint32_t*)((uint8_t*)c->d_plan + a + b), *d_out = (uint32_t*)((uint8_t*)c->d_plan + a + b + p);
+    hipError_t e = hipMemcpyAsync(d_ranges, ranges, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_first, first.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) e = alz_launch_checksum(kind, c->stream, d_src, d_ranges, n, d_first, (uint32_t)total, chunk, d_partial, d_out);
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's table and `first`)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+int alz_checksum_batch(alz_ctx* c, uint32_t kind, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+    return checksum_batch(c, false, kind, n, src_base, src_bytes, ranges, out);
+}
+int alz_checksum_batch_device(alz_ctx* c, uint32_t kind, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+    return checksum_batch(c, true, kind, n, d_src_base, src_bytes, ranges, out);
+}
+// the checksum of A || B from those of A and of B: pure host code, the arithmetic of the fold kernel (alz_checksum.h).  An unknown kind gives 0.
+uint32_t alz_checksum_combine(uint32_t kind, uint32_t a, uint32_t b, uint64_t len_b) {
+    if (kind > ALZ_CK_CRC32) return 0;
+    return alz_checksum_join(kind, a, b, len_b, kind == ALZ_CK_CRC32 ? alz_crc_xpow_bytes(len_b) : 0u);
 }
 
 // Device buffers of one encode call, freed on every exit path

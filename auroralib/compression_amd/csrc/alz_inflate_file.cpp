@@ -5,41 +5,11 @@
 #include <cstring>
 
 #include "auroralz.h"
+#include "alz_zfile.h"
 
 namespace {
 
-const uint32_t kMaxCap = 0xFFFFFF00u;                                          // the largest dst_cap of a stream
-
-uint32_t adler32(const uint8_t* p, size_t n) {
-    uint32_t a = 1, b = 0;
-    while (n) {
-        size_t k = n < 5552 ? n : 5552;                                         // the longest run whose sums stay below 2^32
-        n -= k;
-        while (k--) { a += *p++; b += a; }
-        a %= 65521u; b %= 65521u;
-    }
-    return (b << 16) | a;
-}
-
-struct Crc32 {
-    uint32_t t[256];
-    Crc32() {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-            t[i] = c;
-        }
-    }
-    uint32_t of(const uint8_t* p, size_t n) const {
-        uint32_t c = 0xFFFFFFFFu;
-        while (n--) c = t[(c ^ *p++) & 0xFFu] ^ (c >> 8);
-        return ~c;
-    }
-};
-const Crc32 kCrc;
-
-inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline uint32_t be32(const uint8_t* p) { return (uint32_t)p[3] | ((uint32_t)p[2] << 8) | ((uint32_t)p[1] << 16) | ((uint32_t)p[0] << 24); }
+using namespace alz_zframe;                                                    // header walks, trailer fields and the host checksums: shared with alz_zfile.cpp
 
 // what one call reports; `out` counts the bytes delivered (decode) or counted (measure)
 struct Outcome {
@@ -69,57 +39,21 @@ int body(alz_ctx* ctx, const uint8_t* src, size_t len, size_t pos, uint8_t* dst,
 
 // RFC 1950: CMF, FLG, the body, the big-endian Adler-32 of the output
 int zlib_file(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, const Outcome& o) {
-    if (len < 2) return ALZ_E_FORMAT;
-    const uint32_t cmf = src[0], flg = src[1];
-    if ((cmf & 0x0Fu) != 8u) return ALZ_E_FORMAT;                               // CM
-    if ((cmf >> 4) > 7u) return ALZ_E_FORMAT;                                   // CINFO (it does not limit distances: inflate with 15 window bits)
-    if ((cmf * 256u + flg) % 31u != 0u) return ALZ_E_FORMAT;                    // FCHECK
-    if (flg & 0x20u) return ALZ_E_UNSUPPORTED;                                  // FDICT: no preset dictionaries
+    if (int rc = zlib_header(src, len)) return rc;
     alz_result r;
     if (int rc = body(ctx, src, len, 2, dst, cap, 0, o.measure, &r)) return rc;
     if (r.status != ALZ_ST_OK) return o.stream(r.status, r.dst_len, 2 + (size_t)r.src_used);
     const size_t pos = 2 + (size_t)r.src_used;
     if (len - pos < 4) return o.stream(ALZ_ST_INPUT_TRUNCATED, r.dst_len, len);
-    if (!o.measure && be32(src + pos) != adler32(dst, r.dst_len)) return o.end(ALZ_E_CHECKSUM, ALZ_ST_OK, r.dst_len, pos + 4);
+    if (!o.measure && !zlib_trailer_ok(src + pos, adler32(dst, r.dst_len))) return o.end(ALZ_E_CHECKSUM, ALZ_ST_OK, r.dst_len, pos + 4);
     return o.end(ALZ_OK, ALZ_ST_OK, r.dst_len, pos + 4);
-}
-
-// the header of one gzip member at src[pos..len): ALZ_OK and pos behind it, ALZ_E_FORMAT, ALZ_E_CHECKSUM, or ALZ_E_STREAM (it runs past the input)
-int gzip_header(const uint8_t* src, size_t len, size_t& pos) {
-    const size_t start = pos, n = len - pos;
-    if (n < 2 || src[pos] != 0x1F || src[pos + 1] != 0x8B) return ALZ_E_FORMAT;
-    if (n >= 3 && src[pos + 2] != 8) return ALZ_E_FORMAT;                       // CM
-    if (n >= 4 && (src[pos + 3] & 0xE0u)) return ALZ_E_FORMAT;                  // reserved FLG bits
-    if (n < 10) return ALZ_E_STREAM;
-    const uint32_t flg = src[pos + 3];
-    pos += 10;                                                                  // MTIME, XFL, OS are not looked at
-    if (flg & 4u) {                                                             // FEXTRA: XLEN, then XLEN bytes
-        if (len - pos < 2) return ALZ_E_STREAM;
-        const size_t xlen = (size_t)src[pos] | ((size_t)src[pos + 1] << 8);
-        pos += 2;
-        if (len - pos < xlen) return ALZ_E_STREAM;
-        pos += xlen;
-    }
-    for (uint32_t bit = 8u; bit <= 16u; bit <<= 1) {                            // FNAME, FCOMMENT: zero-terminated
-        if (!(flg & bit)) continue;
-        const void* z = memchr(src + pos, 0, len - pos);
-        if (!z) return ALZ_E_STREAM;
-        pos = (size_t)((const uint8_t*)z - src) + 1;
-    }
-    if (flg & 2u) {                                                             // FHCRC: the low 16 bits of the CRC-32 of the header so far
-        if (len - pos < 2) return ALZ_E_STREAM;
-        const uint32_t want = (uint32_t)src[pos] | ((uint32_t)src[pos + 1] << 8);
-        if ((kCrc.of(src + start, pos - start) & 0xFFFFu) != want) return ALZ_E_CHECKSUM;
-        pos += 2;
-    }
-    return ALZ_OK;
 }
 
 // RFC 1952: members (header, body, CRC-32 and ISIZE of the member's output) while the next two bytes are 1F 8B
 int gzip_file(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, const Outcome& o) {
     size_t pos = 0, out = 0;
     for (bool first = true;; first = false) {
-        if (!first && !(len - pos >= 2 && src[pos] == 0x1F && src[pos + 1] == 0x8B)) break;   // anything else behind a member ends decoding
+        if (!first && !gzip_member_follows(src, len, pos)) break;                              // anything else behind a member ends decoding
         const int hrc = gzip_header(src, len, pos);
         if (hrc == ALZ_E_STREAM) return o.stream(ALZ_ST_INPUT_TRUNCATED, out, len);
         if (hrc) return o.end(hrc, ALZ_ST_OK, out, pos);
@@ -130,8 +64,8 @@ int gzip_file(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* dst, size_t
         if (r.status != ALZ_ST_OK) return o.stream(r.status, out, pos + (size_t)r.src_used);
         pos += (size_t)r.src_used;
         if (len - pos < 8) return o.stream(ALZ_ST_INPUT_TRUNCATED, out, len);
-        const bool crc_ok = o.measure || le32(src + pos) == kCrc.of(dst + mstart, r.dst_len);
-        if (!crc_ok || le32(src + pos + 4) != r.dst_len) return o.end(ALZ_E_CHECKSUM, ALZ_ST_OK, out, pos + 8);   // (a stream holds fewer than 2^32 bytes: ISIZE is its length)
+        const uint32_t crc = o.measure ? 0u : crc32().of(dst + mstart, r.dst_len);
+        if (!gzip_trailer_ok(src + pos, o.measure ? nullptr : &crc, r.dst_len)) return o.end(ALZ_E_CHECKSUM, ALZ_ST_OK, out, pos + 8);   // (a stream holds fewer than 2^32 bytes: ISIZE is its length)
         pos += 8;
     }
     return o.end(ALZ_OK, ALZ_ST_OK, out, len);                                  // source.Position = source.Length  GZip.cs:33

@@ -610,6 +610,39 @@ class _InflateFile:
         _raise_for_outcome(rc, st.value, dl.value)
         return dst_arr[:dl.value].tobytes()
 
+    def DecompressMany(self, files, limit=A.MEASURE_NO_BOUND):
+        """Decompress for a whole set of files in two GPU batches: one alz_zfile_measure_batch (sizes up to `limit`), a destination of exactly
+        the measured sizes, one alz_zfile_decode_batch.  Returns a list with, per file, its bytes -- or the exception instance Decompress would
+        have raised for it."""
+        files = [bytes(f) for f in files]
+        kind = A.ZFILE_ZLIB if self.prefix == "zlib" else A.ZFILE_GZIP
+        src = np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8)
+        table, so = (A.Stream * len(files))(), 0
+        for i, f in enumerate(files):
+            table[i] = A.Stream(so, 0, len(f), limit, 0, 0, 0, kind)
+            so += len(f)
+
+        def outcome(r):
+            try:
+                _raise_for_outcome(r.rc, r.status, r.dst_len)
+            except Exception as e:              # the instance is the result
+                return e
+            return None
+        ctx = _context()
+        measured = ctx.zfile_measure_batch(table, src) if files else []
+        out = [outcome(r) for r in measured]
+        good, do = [i for i, e in enumerate(out) if e is None], 0
+        if good:
+            sub = (A.Stream * len(good))()
+            for k, i in enumerate(good):
+                sub[k] = A.Stream(table[i].src_off, do, table[i].src_len, measured[i].dst_len, 0, 0, 0, kind)
+                do += measured[i].dst_len
+            dst, res = ctx.zfile_decode_batch(sub, src, do)
+            for k, i in enumerate(good):
+                e = outcome(res[k])
+                out[i] = e if e is not None else dst[int(sub[k].dst_off):int(sub[k].dst_off) + res[k].dst_len].tobytes()
+        return out
+
     def Compress(self, data, settings=None):
         raise NotImplementedError(INFLATE_NO_ENCODER % type(self).__name__)
 

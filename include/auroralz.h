@@ -555,6 +555,58 @@ int alz_zlib_measure(alz_ctx* ctx, const uint8_t* src, size_t src_len, size_t si
 int alz_gzip_measure(alz_ctx* ctx, const uint8_t* src, size_t src_len, size_t size_limit,
                      size_t* size_out, size_t* src_used, int32_t* status);
 
+/* ---------------------------------------- checksums of byte ranges: Adler-32 and CRC-32 on the GPU
+ * out[i] is the checksum of the n ranges[i]: ALZ_CK_ADLER32 is RFC 1950's (zlib.adler32), ALZ_CK_CRC32 the CRC-32 with polynomial
+ * 0xEDB88320, start value and final inversion 0xFFFFFFFF (zlib.crc32).  A range is src_off / src_len of its alz_stream; EVERY OTHER
+ * FIELD IS IGNORED.  Ranges may overlap, be empty (Adler-32 1, CRC-32 0) and start at any byte.  The device writes nothing but the n
+ * results (and the library's own scratch).  The kernels READ a range in aligned 16-byte granules -- never a granule that holds no byte
+ * of a range -- so the slack rule of alz_aplib_* (64 readable bytes behind the buffer) covers them.
+ * Every range is cut into chunks of 32 KiB; one wavefront sums one chunk, the grid runs over all chunks of all ranges, and a second,
+ * small launch joins each range's chunk sums: many small ranges and one huge range fill the GPU alike.  alz_last_kernel_ms reports the
+ * device time of the two launches.  n == 0 is ALZ_OK; a NULL ctx, an unknown kind, a range outside src_bytes, or NULL ranges / out with
+ * n > 0 are ALZ_E_INVALID (checked before anything is uploaded); more than 2^31 chunks in one call are ALZ_E_UNSUPPORTED.
+ * alz_checksum_combine: the checksum of A || B from the checksum `a` of A, the checksum `b` of B and the length of B (zlib's
+ *   adler32_combine / crc32_combine): pure host code, no context, the very arithmetic the second launch runs.  len_b == 0 returns a.
+ *   An unknown kind returns 0.
+ * NOT BUILT: CRC-32C and xxHash32 (the checksums of the Snappy and LZ4 containers), and a checksum fused into a decode kernel's
+ *   write-back. */
+typedef enum alz_checksum_kind { ALZ_CK_ADLER32 = 0, ALZ_CK_CRC32 = 1 } alz_checksum_kind;
+int alz_checksum_batch(alz_ctx* ctx, uint32_t kind, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                       const alz_stream* ranges, uint32_t* out);
+/* d_src_base is a DEVICE pointer; out is on the host */
+int alz_checksum_batch_device(alz_ctx* ctx, uint32_t kind, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                              const alz_stream* ranges, uint32_t* out);
+uint32_t alz_checksum_combine(uint32_t kind, uint32_t a, uint32_t b, uint64_t len_b);
+
+/* ---------------------------------------- ZLib and GZip files in batches
+ * What alz_zlib_decompress / alz_gzip_decompress (and their _measure twins) do for one file, for n files in one call.  files[i].format is
+ * ALZ_ZFILE_ZLIB or ALZ_ZFILE_GZIP -- a batch may mix them, any other value is ALZ_E_INVALID; src_off / src_len is the whole file;
+ * dst_off / dst_cap is where its output goes (measure: dst_off is ignored, dst_cap is the size limit); decom_len, aux0 and aux1 are
+ * IGNORED.  All buffers are in host memory.
+ * THE CONTRACT IS DIFFERENTIAL: results[i].rc / status / dst_len / src_used are exactly what the single-file call returns for file i
+ * alone with the same capacity, and the bytes at [dst_off, dst_off + dst_len) are the bytes it delivers -- also for a file that fails
+ * (its partial output is delivered).  Nothing outside a file's [dst_off, dst_off + dst_cap) is written.  A file's failure is that
+ * file's rc; the call itself fails only for bad arguments or a HIP error.
+ * One batch: the header walks run on the host (the code of the single-file layer); the source is uploaded once; all bodies decode as ONE
+ * alz_inflate_decode_batch_device (measure: one measure batch); all outputs are summed in HBM by alz_checksum_batch_device, Adler-32 for
+ * the ZLib files and CRC-32 for the GZip members (measure: taken as correct); the trailers are compared on the host; the outputs are
+ * downloaded once.  A GZip member behind the first is found only when the one before it is decoded, so a batch runs in rounds: round r
+ * holds the r-th member of every file that has one, each member with a CRC-32 and ISIZE check of its own.
+ * NOT BUILT: device-resident forms (headers and trailers are read on the host), the zlib wrappers of the .Extended assembly, preset
+ *   dictionaries.  The single-file entry points above are unchanged, host-side checksums included: they are the yardstick. */
+#define ALZ_ZFILE_ZLIB 0u
+#define ALZ_ZFILE_GZIP 1u
+typedef struct alz_file_result {
+    int32_t  rc;         /* ALZ_OK or the ALZ_E_* code of this file */
+    int32_t  status;     /* alz_status (meaningful with ALZ_E_STREAM) */
+    uint32_t dst_len;
+    uint32_t src_used;
+} alz_file_result;
+int alz_zfile_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
+                           uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
+int alz_zfile_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
+                            alz_file_result* results);
+
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's
  * [dst_off, dst_off + dst_len) (tests/test_gpu_canary.py); they READ the input in aligned 16-byte granules and, for the 64 KiB

@@ -62,6 +62,16 @@ namespace AuroraLib.Compression.Amd
         public uint Aux1;
     }
 
+    /// <summary>alz_file_result (16 bytes): what the single-file call returns for one file of an alz_zfile_* batch.</summary>
+    [StructLayout(LayoutKind.Sequential, Size = 16)]
+    public struct AlzFileResult
+    {
+        public int Rc;
+        public int Status;
+        public uint DstLen;
+        public uint SrcUsed;
+    }
+
     /// <summary>alz_format: the headerless bodies (values are ABI constants).</summary>
     public enum AlzFormat : uint
     {
@@ -168,6 +178,19 @@ namespace AuroraLib.Compression.Amd
             UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
         [DllImport(Lib)] internal static extern int alz_gzip_measure(IntPtr ctx, byte* src, UIntPtr srcLen, UIntPtr sizeLimit,
             UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
+
+        // Adler-32 (kind 0) and CRC-32 (kind 1) of byte ranges on the GPU (a range is SrcOff / SrcLen of its AlzStream) ...
+        [DllImport(Lib)] internal static extern int alz_checksum_batch(IntPtr ctx, uint kind, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* ranges, uint* checksums);
+        [DllImport(Lib)] internal static extern int alz_checksum_batch_device(IntPtr ctx, uint kind, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* ranges, uint* checksums);
+        // ... the checksum of A || B from those of A and B (host arithmetic), and ZLib (format 0) / GZip (format 1) files in batches: per
+        // file what alz_zlib_decompress / alz_gzip_decompress return for it alone
+        [DllImport(Lib, ExactSpelling = true)] internal static extern uint alz_checksum_combine(uint kind, uint a, uint b, ulong lenB);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_zfile_decode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_zfile_measure_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, AlzFileResult* results);
 
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,

@@ -1,5 +1,5 @@
 """usage: python tools/kernel_hash.py [--stamp]  -- the hash that ties the committed counter files (profiles/traffic.json, profiles/insts.json) to the kernel sources
-they were measured on.  Two families: "decode" (alz_kernels.hip, alz_big.hip and every header they include) and "encode" (alz_encode.hip and its headers; it shares
+they were measured on.  Two families carry counters: "decode" (alz_kernels.hip, alz_big.hip and every header they include) and "encode" (alz_encode.hip and its headers; it shares
 alz_device.h / alz_internal.h).  sha256 over the files' bytes in name order.  --stamp writes the current hashes into both JSON files (`_kernel_hash`): run it on the
 checkout the counters were collected from (tools/profile_r06.sh does), never to silence bench.py's `counters_stale`."""
 import hashlib
@@ -17,6 +17,8 @@ FAMILIES = {
     "aplib": ["alz_aplib.hip", "alz_aplib.h"],         # aPLib, the 2 MiB-window LzWindows user (decode + measure): no committed counters
     "bitlz": ["alz_bitlz.hip", "alz_bitlz.h"],         # CRILAYLA / ALLZ, the bit-stream LZ bodies of the .Extended assembly (decode): no committed counters
     "inflate": ["alz_inflate.hip", "alz_inflate.h"],   # DEFLATE as zlib's inflate reads it (decode + measure): no committed counters
+    "checksum": ["alz_checksum.hip", "alz_checksum.h"],   # Adler-32 / CRC-32 of byte ranges: no committed counters
+    "zfile": ["alz_zfile.h"],                          # host code: the zlib / gzip framing shared by the two file layers (no kernel)
 }
 FILES = ("traffic.json", "insts.json")
 
