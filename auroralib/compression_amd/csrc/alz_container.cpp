@@ -13,6 +13,7 @@
 #include <cstring>
 #include <vector>
 
+#include "alz_framing.h"
 #include "auroralz.h"
 
 // The RLE30 / HUF20 entry points are referenced WEAKLY from here: the sanitized fuzz binary of these header parsers (oracle/Makefile,
@@ -23,8 +24,9 @@
 
 namespace {
 
+using namespace alz_framing;   // le32, clamp32, xxh32, the LZ4 / Snappy framing readers
+
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-inline uint32_t le32(const uint8_t* p) { return ((uint32_t)p[3] << 24) | ((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | p[0]; }
 inline uint32_t rd32(const uint8_t* p, bool big) { return big ? be32(p) : le32(p); }
 inline uint32_t bswap32(uint32_t v) { return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24); }
 inline void wr32(uint8_t* p, uint32_t v, bool big) {
@@ -109,8 +111,6 @@ int prs_byte_order(const uint8_t* src, size_t len) {
 const uint8_t kAklzMagic[12] = { 'A', 'K', 'L', 'Z', '~', '?', 'Q', 'd', '=', 0xCC, 0xCC, 0xCD };   // "AKLZ~?Qd=\xCC\xCC\xCD"  AKLZ.cs:16
 const uint8_t kLzonMagic[8] = { 'L', 'Z', 'O', 'n', 0x00, 0x2F, 0xF1, 0x71 };                           // LZOn.cs:17
 
-uint32_t clamp32(size_t v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
-
 int run_body(alz_ctx* ctx, uint32_t fmt, const alz_lz_properties* lz, const uint8_t* body, size_t body_len, uint32_t size,
              uint32_t aux0, uint32_t aux1, uint8_t* dst, size_t cap, alz_result* r) {
     return alz_decode(ctx, fmt, lz, body, clamp32(body_len), size, aux0, aux1, dst, clamp32(cap), r);
@@ -138,25 +138,6 @@ int rlh_compress_body(alz_ctx* ctx, const uint8_t* src, size_t n, uint8_t* dst, 
 }
 
 // ---------------------------------------------------------------------------------------------- checksums (host side)
-// XXH32 (the LZ4 frame format's checksum; the reference takes it as LZ4.HashAlgorithm, LZ4.Frame.cs:17-18)
-inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-uint32_t xxh32(const uint8_t* p, size_t len, uint32_t seed) {
-    const uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
-    const uint8_t* end = p + len; uint32_t h;
-    if (len >= 16) {
-        uint32_t v1 = seed + P1 + P2, v2 = seed + P2, v3 = seed, v4 = seed - P1;
-        do {
-            v1 = rotl32(v1 + le32(p) * P2, 13) * P1; v2 = rotl32(v2 + le32(p + 4) * P2, 13) * P1;
-            v3 = rotl32(v3 + le32(p + 8) * P2, 13) * P1; v4 = rotl32(v4 + le32(p + 12) * P2, 13) * P1; p += 16;
-        } while (p + 16 <= end);
-        h = rotl32(v1, 1) + rotl32(v2, 7) + rotl32(v3, 12) + rotl32(v4, 18);
-    } else h = seed + P5;
-    h += (uint32_t)len;
-    while (p + 4 <= end) { h = rotl32(h + le32(p) * P3, 17) * P4; p += 4; }
-    while (p < end) { h = rotl32(h + (*p) * P5, 11) * P1; p++; }
-    h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
-    return h;
-}
 // CRC-32C (Castagnoli, reflected 0x82F63B78); Snappy.cs:87 masks it with CRCMask (:252).  The host's crc32 instruction where it has one (SSE4.2: three
 // independent streams of 8 bytes per step would be faster still; one is ~16 x the table walk already -- 16 MB of Snappy chunks 32 -> 2 ms, which was most of
 // what a framed Compress cost), a byte-wise table otherwise.
@@ -181,10 +162,6 @@ uint32_t crc32c(const uint8_t* p, size_t len) {
     return c ^ 0xFFFFFFFFu;
 }
 inline uint32_t snappy_crc_mask(uint32_t crc) { return ((crc >> 15) | (crc << 17)) + 0xa282ead8u; }
-
-const uint8_t kSnappyId[10] = { 0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59 };                // Snappy.cs:17
-
-inline bool lz4_magic_defined(uint32_t v) { return v == 0x184C2102u || v == 0x184D2204u || (v >= 0x184D2A50u && v <= 0x184D2A5Fu); }   // LZ4.Frame.cs:50-70
 
 // Which branches of the LZ4 file decode ran, process-wide (alz_debug_container_counters): what a test asserts to show that its cases reached each of them.
 enum { CNT_BATCH_BLOCKS, CNT_SPLIT_PLANS, CNT_TIGHT_RETRIES, CNT_FALLBACK_BLOCKS, CNT_LINKED_BLOCKS, CNT_STORED_BLOCKS, CNT_COUNT };
@@ -217,8 +194,6 @@ static bool lz4_block_reaches_back(const uint8_t* b, uint32_t n) {
     }
     return false;
 }
-
-struct Lz4Block { size_t off; uint32_t len; bool raw; };
 
 // A block's destination as the whole-GPU decode path of ONE stream wants it (alz_big_eligible: no more than 32 x the input + 64 KiB -- its launches are sized by the room in the
 // destination): the frame's block maximum is 4 MiB whatever the block holds, and a 1 MB file in one block had 33 x its 126 KB of input to decode into -- 3.7 ms on two wavefronts
@@ -339,83 +314,31 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
         return ALZ_OK;
     };
 
-    while (pos < len && st == ALZ_ST_OK) {
-        if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-        uint32_t magic = le32(src + pos); pos += 4;
-    again:
-        if (magic == 0x184C2102u) {                                                      // legacy  LZ4.cs:96-111
+    // frame after frame (alz_framing.h); a legacy frame that ends in a defined magic hands it to the next read, whatever is left of the file
+    Lz4Frame f; std::vector<Lz4Block> bl; uint32_t magic = 0;
+    while ((magic != 0 || pos < len) && st == ALZ_ST_OK) {
+        bl.clear(); lz4_read_frame(src, len, pos, magic, f, bl);
+        pos = f.end; magic = f.next_magic;
+        const size_t frame_start = out;
+        // The managed reader keeps ONE LzWindows for all blocks of a frame whatever the independence flag says
+        // (LZ4.Frame.cs:120), so a frame that is flagged independent but whose blocks still reach into earlier output decodes
+        // there.  Blocks go out as one batch only when a walk over their sequences (host, input only) shows that none does -- whatever the flag says the other
+        // way round, too: the reference's own writer clears it (LZ4.Frame.cs:184) and compresses every block with a finder of its own (LZ4.cs:205), so the frames it
+        // writes -- 16 MB in 64 KiB blocks: 256 blocks -- were decoded one launch after the other, each with the output so far as its history: 112 ms.  (Legacy blocks have a window each.)
+        bool indep = true;
+        if (f.kind == Lz4Frame::FRAME) for (size_t i = 1; indep && i < bl.size(); i++) if (!bl[i].raw && lz4_block_reaches_back(src + bl[i].off, bl[i].len)) indep = false;
+        if (indep) rc = run_independent(bl, f.nominal); else rc = run_sequential(bl, 0, frame_start, true, false);
+        if (rc != ALZ_OK) return rc;
+        if (st == ALZ_ST_OK && f.fault != ALZ_OK) return f.fault;
+        if (st == ALZ_ST_OK && f.truncated) st = ALZ_ST_INPUT_TRUNCATED;
+        if (st != ALZ_ST_OK || f.ends_file) break;
+        if ((f.flg & 8) && (uint64_t)(out - frame_start) != f.content) { st = ALZ_ST_OUTPUT_SIZE_MISMATCH; break; }   // LZ4.Frame.cs:152-155
+        if (f.flg & 4) {                                                                 // content checksum
             if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            uint32_t bs = le32(src + pos); pos += 4;
-            std::vector<Lz4Block> bl; bool next = false, eof_flag = false, trunc = false;
-            for (;;) {
-                if (bs > len - pos) { trunc = true; break; }
-                bl.push_back(Lz4Block{ pos, bs, false }); pos += bs;
-                if (pos >= len) break;                                                   // ReadByte() == -1
-                if (src[pos] == 0xFF) { pos++; eof_flag = true; break; }                 // (sbyte)0xFF == -1: the EOF flag
-                if (pos + 4 > len) { trunc = true; break; }
-                bs = le32(src + pos); pos += 4;
-                if (lz4_magic_defined(bs)) { next = true; break; }
-            }
-            if ((rc = run_independent(bl, 0x800000u)) != ALZ_OK) return rc;
-            if (st == ALZ_ST_OK && trunc) st = ALZ_ST_INPUT_TRUNCATED;
-            if (st != ALZ_ST_OK) break;
-            if (next) { magic = bs; goto again; }
-            (void)eof_flag;
-            break;                                                                       // blockSize == 0: Decompress returns
-        } else if (magic == 0x184D2204u) {                                               // frame  LZ4.Frame.cs:107-174
-            const size_t frame_start = out;
-            if (pos + 2 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            const uint32_t flg = src[pos], bd = src[pos + 1]; pos += 2;
-            uint32_t bmax;
-            switch ((bd & 0x70) >> 4) { case 4: bmax = 0x10000; break; case 5: bmax = 0x40000; break; case 6: bmax = 0x100000; break; case 7: bmax = 0x400000; break; default: return ALZ_E_FORMAT; }
-            uint64_t content = 0;
-            if (flg & 8) { if (pos + 8 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; } content = (uint64_t)le32(src + pos) | ((uint64_t)le32(src + pos + 4) << 32); pos += 8; }
-            if (flg & 1) { if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; } pos += 4; }
-            if (pos + 1 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            pos += 1;                                                                    // HeaderChecksum: read, not verified
-            if (flg & 1) return ALZ_E_UNSUPPORTED;                                       // external dictionaries  LZ4.Frame.cs:113-114
-            // A block too large for the frame or with a wrong checksum ends the collection; it decides the outcome only if the blocks in
-            // front of it decode cleanly (the managed reader meets it after them).
-            std::vector<Lz4Block> bl; bool trunc = false; int fault = ALZ_OK;
-            for (;;) {
-                if (pos + 4 > len) { trunc = true; break; }
-                const uint32_t bsz = le32(src + pos); pos += 4;
-                if (bsz == 0) break;                                                     // EndMark
-                const bool raw = (bsz & 0x80000000u) != 0; const uint32_t n = bsz & 0x7FFFFFFFu;
-                if (n > bmax) { fault = ALZ_E_FORMAT; break; }
-                if (n > len - pos) { trunc = true; break; }
-                const size_t boff = pos; pos += n;
-                if (flg & 16) {                                                          // block checksum over the stored bytes
-                    if (pos + 4 > len) { trunc = true; break; }
-                    if (le32(src + pos) != xxh32(src + boff, n, 0)) { fault = ALZ_E_CHECKSUM; break; }
-                    pos += 4;
-                }
-                bl.push_back(Lz4Block{ boff, n, raw });
-            }
-            // The managed reader keeps ONE LzWindows for all blocks of a frame whatever the independence flag says
-            // (LZ4.Frame.cs:120), so a frame that is flagged independent but whose blocks still reach into earlier output decodes
-            // there.  Blocks go out as one batch only when a walk over their sequences (host, input only) shows that none does -- whatever the flag says the other
-            // way round, too: the reference's own writer clears it (LZ4.Frame.cs:184) and compresses every block with a finder of its own (LZ4.cs:205), so the frames it
-            // writes -- 16 MB in 64 KiB blocks: 256 blocks -- were decoded one launch after the other, each with the output so far as its history: 112 ms.
-            bool indep = true;
-            for (size_t i = 1; indep && i < bl.size(); i++) if (!bl[i].raw && lz4_block_reaches_back(src + bl[i].off, bl[i].len)) indep = false;
-            if (indep) rc = run_independent(bl, bmax); else rc = run_sequential(bl, 0, frame_start, true, false);
-            if (rc != ALZ_OK) return rc;
-            if (st == ALZ_ST_OK && fault != ALZ_OK) return fault;
-            if (st == ALZ_ST_OK && trunc) st = ALZ_ST_INPUT_TRUNCATED;
-            if (st != ALZ_ST_OK) break;
-            if ((flg & 8) && (uint64_t)(out - frame_start) != content) { st = ALZ_ST_OUTPUT_SIZE_MISMATCH; break; }   // LZ4.Frame.cs:152-155
-            if (flg & 4) {                                                               // content checksum
-                if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-                if (out > frame_start && (rc = alz_memcpy_d2h(ctx, dst + frame_start, (uint8_t*)d_dst.p + frame_start, out - frame_start)) != ALZ_OK) return rc;
-                if (le32(src + pos) != xxh32(dst + frame_start, out - frame_start, 0)) return ALZ_E_CHECKSUM;
-                pos += 4;
-            }
-        } else if (magic >= 0x184D2A50u && magic <= 0x184D2A5Fu) {                        // skippable
-            if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            const uint32_t n = le32(src + pos); pos += 4;
-            pos = (uint64_t)pos + n > len ? len : pos + n;
-        } else { pos -= 4; break; }                                                      // not a frame: stop in front of it
+            if (out > frame_start && (rc = alz_memcpy_d2h(ctx, dst + frame_start, (uint8_t*)d_dst.p + frame_start, out - frame_start)) != ALZ_OK) return rc;
+            if (le32(src + pos) != xxh32(dst + frame_start, out - frame_start, 0)) return ALZ_E_CHECKSUM;
+            pos += 4;
+        }
     }
     if (out && (rc = alz_memcpy_d2h(ctx, dst, d_dst.p, out)) != ALZ_OK) return rc;
     if (dst_len) *dst_len = out;
@@ -456,12 +379,12 @@ int encode_blocks(alz_ctx* ctx, uint32_t fmt, const alz_settings* st, const uint
 int lz4_file_compress(alz_ctx* ctx, bool legacy, uint32_t block_size, const alz_settings* st, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* dst_len) {
     size_t o = 0;
     if (cap < 16) return ALZ_E_NOMEM;
-    if (legacy) { wr32(dst, 0x184C2102u, false); o = 4; block_size = 0x800000u; }       // (int)BlockMaxSizes.Block4MB * 2
+    if (legacy) { wr32(dst, kLz4Legacy, false); o = 4; block_size = 0x800000u; }       // (int)BlockMaxSizes.Block4MB * 2
     else {
         uint8_t bdb;
         switch (block_size) { case 0: block_size = 0x400000; bdb = 0x70; break; case 0x10000: bdb = 0x40; break; case 0x40000: bdb = 0x50; break;
                               case 0x100000: bdb = 0x60; break; case 0x400000: bdb = 0x70; break; default: return ALZ_E_INVALID; }
-        wr32(dst, 0x184D2204u, false); dst[4] = 0x40; dst[5] = bdb; dst[6] = (uint8_t)((xxh32(dst + 4, 2, 0) >> 8) & 0xFF); o = 7;
+        wr32(dst, kLz4Frame, false); dst[4] = 0x40; dst[5] = bdb; dst[6] = (uint8_t)((xxh32(dst + 4, 2, 0) >> 8) & 0xFF); o = 7;
     }
     if (n && n % block_size != 0 && n % block_size < 5) return ALZ_E_INVALID;            // source.Slice(0, Length - 5) throws  LZ4.cs:208
     BlockSlots tmp; std::vector<alz_result> rs; size_t slot = 0;
@@ -484,40 +407,27 @@ int lz4_file_compress(alz_ctx* ctx, bool legacy, uint32_t block_size, const alz_
     return ALZ_OK;
 }
 
-inline uint32_t snappy_varint(const uint8_t* p, size_t len, size_t* used) {            // Snappy.ReadDecompressedSize  Snappy.cs:109-122
-    uint32_t v = 0; int shift = 0; size_t i = 0; int b = 0x80;
-    while ((b & 0x80) && i < len) { b = p[i++]; if (shift < 32) v |= (uint32_t)(b & 0x7F) << shift; shift += 7; }
-    if (used) *used = i;
-    return v;
-}
-
 // Snappy.Decompress  Formats/Common/Snappy.cs:39-69, chunk after chunk from `pos` with `out` bytes produced: the path of a file whose
 // chunk decodes to more than it declares (its last element runs past the size), which moves every later chunk.
 int snappy_in_order(alz_ctx* ctx, const uint8_t* src, size_t len, size_t pos, size_t out, uint8_t* dst, size_t cap, size_t* dst_len, size_t* src_used, int32_t* status) {
     int32_t st = ALZ_ST_OK;
     while (pos < len) {
-        if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-        const uint32_t type = src[pos], cl = (uint32_t)src[pos + 1] | ((uint32_t)src[pos + 2] << 8) | ((uint32_t)src[pos + 3] << 16); pos += 4;
-        if (type == 0) {
-            if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            pos += 4;
+        const SnappyChunk c = snappy_read_chunk(src, len, pos);
+        pos = c.body;
+        if (c.kind == SnappyChunk::TRUNCATED) { st = ALZ_ST_INPUT_TRUNCATED; break; }
+        if (c.kind == SnappyChunk::RESERVED) return ALZ_E_FORMAT;
+        if (c.kind == SnappyChunk::COMPRESSED) {
             alz_result r;
             int rc = run_body(ctx, ALZ_FMT_SNAPPY_RAW, nullptr, src + pos, len - pos, 0, 0, 0, dst + out, out < cap ? cap - out : 0, &r);
             if (rc != ALZ_OK) return rc;
             out += r.dst_len;
             if (r.status != ALZ_ST_OK) { st = r.status; break; }
-            if ((uint64_t)r.src_used + 4 != cl) return ALZ_E_FORMAT;                     // (as below: a body that does not end at the declared length)
+            if ((uint64_t)r.src_used + 4 != c.len) return ALZ_E_FORMAT;                  // (as below: a body that does not end at the declared length)
             pos += r.src_used;
-        } else if (type == 1) {
-            if (pos + 4 > len || cl < 4) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            pos += 4;
-            uint32_t n = cl - 4; if (n > len - pos) n = (uint32_t)(len - pos);
-            if (out + n > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
-            memcpy(dst + out, src + pos, n); out += n; pos += n;
-        } else {
-            if (type >= 0x02 && type <= 0x7F) return ALZ_E_FORMAT;
-            pos = (uint64_t)pos + cl > len ? len : pos + cl;
-        }
+        } else if (c.kind == SnappyChunk::STORED) {
+            if (out + c.stored > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
+            memcpy(dst + out, src + pos, c.stored); out += c.stored; pos = c.next;
+        } else pos = c.next;
     }
     if (dst_len) *dst_len = out;
     if (src_used) *src_used = pos;
@@ -536,24 +446,19 @@ int snappy_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t
     struct Raw { size_t off; uint32_t n; uint64_t out; }; std::vector<Raw> raws;
     std::vector<bool> stored;                                                            // file order: stored (true) or compressed chunk
     while (pos < len) {
-        if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-        const uint32_t type = src[pos], cl = (uint32_t)src[pos + 1] | ((uint32_t)src[pos + 2] << 8) | ((uint32_t)src[pos + 3] << 16); pos += 4;
-        if (type == 0) {
-            if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            const size_t body = pos + 4;
-            const uint32_t size = snappy_varint(src + body, len - body, nullptr);
+        const SnappyChunk c = snappy_read_chunk(src, len, pos);
+        pos = c.next;
+        if (c.kind == SnappyChunk::TRUNCATED) { st = ALZ_ST_INPUT_TRUNCATED; break; }
+        if (c.kind == SnappyChunk::RESERVED) { reserved = true; break; }                 // E_FORMAT once reached
+        if (c.kind == SnappyChunk::COMPRESSED) {
+            const uint32_t size = snappy_varint(src + c.body, len - c.body, nullptr);
             alz_stream s; memset(&s, 0, sizeof(s));
-            s.src_off = body; s.src_len = clamp32(len - body); s.dst_off = out < cap ? out : cap;
+            s.src_off = c.body; s.src_len = clamp32(len - c.body); s.dst_off = out < cap ? out : cap;
             s.dst_cap = clamp32(out < cap ? (cap - out < size ? cap - out : size) : 0); s.format = ALZ_FMT_SNAPPY_RAW;
-            ss.push_back(s); clen.push_back(cl); chdr.push_back(pos - 4); stored.push_back(false);
-            out += size; pos = (uint64_t)pos + cl > len ? len : pos + cl;
-        } else if (type == 1) {
-            if (pos + 4 > len || cl < 4) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-            uint32_t n = cl - 4; if (n > len - pos - 4) n = (uint32_t)(len - pos - 4);    // SubStream.CopyTo copies what is there
-            raws.push_back(Raw{ pos + 4, n, out }); stored.push_back(true); out += n; pos += 4 + n;
-        } else {
-            if (type >= 0x02 && type <= 0x7F) { reserved = true; break; }                 // reserved unskippable chunk  Snappy.cs:61-62: E_FORMAT once reached
-            pos = (uint64_t)pos + cl > len ? len : pos + cl;
+            ss.push_back(s); clen.push_back(c.len); chdr.push_back(c.hdr); stored.push_back(false);
+            out += size;
+        } else if (c.kind == SnappyChunk::STORED) {
+            raws.push_back(Raw{ c.body, c.stored, out }); stored.push_back(true); out += c.stored;
         }
     }
     std::vector<alz_result> rs(ss.size());
@@ -671,7 +576,6 @@ static void lz00_keystream(uint8_t* p, size_t n, uint32_t key) {
 }
 
 // shared with alz_container_measure.cpp (declared in alz_measure.h; not part of the ABI)
-uint32_t alz_host_xxh32(const uint8_t* p, size_t len, uint32_t seed) { return xxh32(p, len, seed); }
 int alz_host_prs_byte_order(const uint8_t* src, size_t len) { return prs_byte_order(src, len); }
 
 extern "C" {
@@ -725,13 +629,13 @@ int alz_container_decompressed_size(uint32_t container, const alz_container_opti
         if (len < 16 || memcmp(src, "ECD", 3)) return ALZ_E_FORMAT;
         *size_out = (uint64_t)be32(src + 8) + 0x10 > len ? 0u : be32(src + 12); return ALZ_OK;
     case ALZ_C_LZ4_FRAME:   // not an IProvidesDecompressedSize in the reference; offered where the descriptor carries ContentSize
-        if (len < 15 || le32(src) != 0x184D2204u || !(src[4] & 8) || le32(src + 10) != 0) return ALZ_E_UNSUPPORTED;
+        if (len < 15 || le32(src) != kLz4Frame || !(src[4] & 8) || le32(src + 10) != 0) return ALZ_E_UNSUPPORTED;
         *size_out = le32(src + 6); return ALZ_OK;
     case ALZ_C_SNAPPY: {    // same: the sum of the chunks' declared sizes
         if (len < 10 || memcmp(src, kSnappyId, 10)) return ALZ_E_FORMAT;
         size_t pos = 10; uint64_t total = 0;
         while (pos + 4 <= len) {
-            const uint32_t type = src[pos], cl = (uint32_t)src[pos + 1] | ((uint32_t)src[pos + 2] << 8) | ((uint32_t)src[pos + 3] << 16); pos += 4;
+            const uint32_t type = src[pos], cl = le24(src + pos + 1); pos += 4;
             if (type == 0) total += pos + 4 <= len ? snappy_varint(src + pos + 4, len - pos - 4, nullptr) : 0;
             else if (type == 1) total += cl >= 4 ? cl - 4 : 0;
             pos += cl;
@@ -761,7 +665,7 @@ int alz_container_is_match(uint32_t container, const uint8_t* src, size_t len) {
     case ALZ_C_MIO0: return len > 0x10 && !memcmp(src, "MIO0", 4);
     case ALZ_C_PRS: return len > 0x4 && prs_byte_order(src, len) != 0;                      // PRS.cs:33-34
     case ALZ_C_LZO: { if (len == 0) return 0; int f = src[0]; return (f > 11 && f < 0x20) || f < 0x10; }   // LZO.cs:33-39 (no extension given)
-    case ALZ_C_LZ4_LEGACY: return len > 0x10 && le32(src) == 0x184C2102u;                   // LZ4Legacy.cs:28-29
+    case ALZ_C_LZ4_LEGACY: return len > 0x10 && le32(src) == kLz4Legacy;                   // LZ4Legacy.cs:28-29
     case ALZ_C_LZ4_FRAME: return len > 0x10 && lz4_magic_defined(le32(src));                // LZ4.cs:38-39
     case ALZ_C_SNAPPY: return len > 0x10 && !memcmp(src, kSnappyId, 10);                    // Snappy.cs:36-37
     case ALZ_C_GCLZ: return len > 0x8 && !memcmp(src, "GCLZ", 4) && alz_container_is_match(ALZ_C_LZ10, src + 4, len - 4);

@@ -14,6 +14,6 @@ hipError_t alz_launch_measure(int fmt, hipStream_t stream, const void* d_src, co
                               uint32_t count, alz_result* d_results, const alz_lz_properties* lz, bool exact = false);
 bool alz_measure_has_bulk(int fmt);
 
-// ---- host side: helpers of alz_container.cpp that alz_container_measure.cpp shares (XXH32 of the LZ4 frame format; PRS.GetByteOrder: 1 little, 2 big, 0 none)
-uint32_t alz_host_xxh32(const uint8_t* p, size_t len, uint32_t seed);
+// ---- host side: the helper of alz_container.cpp that alz_container_measure.cpp shares (PRS.GetByteOrder: 1 little, 2 big, 0 none; the LZ4 / Snappy framing
+// and its XXH32, which both files read, are alz_framing.h)
 int alz_host_prs_byte_order(const uint8_t* src, size_t len);

@@ -19,6 +19,7 @@ FAMILIES = {
     "inflate": ["alz_inflate.hip", "alz_inflate.h"],   # DEFLATE as zlib's inflate reads it (decode + measure): no committed counters
     "checksum": ["alz_checksum.hip", "alz_checksum.h"],   # Adler-32 / CRC-32 of byte ranges: no committed counters
     "zfile": ["alz_zfile.h"],                          # host code: the zlib / gzip framing shared by the two file layers (no kernel)
+    "framing": ["alz_framing.h"],                      # host code: the LZ4 / Snappy framing readers shared by file decode and measure (no kernel)
 }
 FILES = ("traffic.json", "insts.json")
 
