@@ -167,4 +167,15 @@ ZFILE_PROTOTYPES = {
     "alz_zfile_measure_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
 }
 
+# XXH32 of byte ranges on the GPU: the checksum family's argument list with a seed in place of the kind
+_XXH32_BATCH = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+XXH32_PROTOTYPES = {"alz_xxh32_batch": _XXH32_BATCH, "alz_xxh32_batch_device": _XXH32_BATCH}
+
+# LZ4 (frame, legacy) and framed Snappy files in batches: Stream.format is C_LZ4_FRAME, C_LZ4_LEGACY or C_SNAPPY, one FileResult per file
+FRAMED_CONTAINERS = (C_LZ4_FRAME, C_LZ4_LEGACY, C_SNAPPY)
+FRAMED_PROTOTYPES = {
+    "alz_framed_decode_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "alz_framed_measure_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16 and C.sizeof(FileResult) == 16

@@ -230,6 +230,38 @@ class Context:
         check(self.lib.alz_zfile_measure_batch(self.h, len(files), _vp(src), src.nbytes, files, res))
         return res
 
+    # ---- XXH32 of byte ranges (the checksum of the LZ4 frame format); a range is src_off / src_len of its Stream
+    def _xxh32(self, fn, ranges, src, src_bytes, seed):
+        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
+        check(fn(self.h, seed, len(ranges), src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:len(ranges)]
+
+    def xxh32_batch(self, ranges, src, seed=0):
+        """alz_xxh32_batch on a host buffer -> a uint32 array, one XXH32 per range."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        return self._xxh32(self.lib.alz_xxh32_batch, ranges, _vp(src), src.nbytes, seed)
+
+    def xxh32_batch_device(self, ranges, d_src, src_bytes, seed=0):
+        """alz_xxh32_batch_device: the same with the bytes already in HBM at d_src; last_kernel_ms() is the device time of the launch."""
+        return self._xxh32(self.lib.alz_xxh32_batch_device, ranges, d_src, src_bytes, seed)
+
+    # ---- LZ4 and Snappy files in batches: Stream.format is A.C_LZ4_FRAME, A.C_LZ4_LEGACY or A.C_SNAPPY, src_off / src_len the whole file
+    def framed_decode_batch(self, files, src, dst_bytes, dst=None):
+        """alz_framed_decode_batch on host buffers -> (dst, results): per file what alz_container_decompress returns for it alone.
+        `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        check(self.lib.alz_framed_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def framed_measure_batch(self, files, src):
+        """alz_framed_measure_batch on a host buffer -> results: per file what alz_container_measure returns; dst_cap is the size limit."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        res = (A.FileResult * len(files))()
+        check(self.lib.alz_framed_measure_batch(self.h, len(files), _vp(src), src.nbytes, files, res))
+        return res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

@@ -174,27 +174,6 @@ struct DevBuf {   // device allocation released on every exit path
     ~DevBuf() { if (p) alz_device_free(c, p); }
 };
 
-// Does any match of this LZ4 block point in front of the block's own output?  (A walk over the sequences: input only.)  Offset 0 is a
-// distance of 65 536 (E1): it reaches back while the block has produced less than that.
-static bool lz4_block_reaches_back(const uint8_t* b, uint32_t n) {
-    uint64_t produced = 0; uint32_t p = 0;
-    while (p < n) {
-        const uint32_t tok = b[p++];
-        uint64_t lit = tok >> 4;
-        if (lit == 15) { uint32_t x; do { if (p >= n) return false; x = b[p++]; lit += x; } while (x == 255); }
-        if (lit > n - p) return false;                                  // truncated: the decoder reports it
-        p += (uint32_t)lit; produced += lit;
-        if (p >= n) break;
-        if (p + 2 > n) return false;
-        const uint32_t dist = b[p] | (b[p + 1] << 8); p += 2;
-        uint64_t ml = tok & 15;
-        if (ml == 15) { uint32_t x; do { if (p >= n) return false; x = b[p++]; ml += x; } while (x == 255); }
-        if ((dist == 0 ? 65536u : dist) > produced) return true;
-        produced += ml + 4;
-    }
-    return false;
-}
-
 // A block's destination as the whole-GPU decode path of ONE stream wants it (alz_big_eligible: no more than 32 x the input + 64 KiB -- its launches are sized by the room in the
 // destination): the frame's block maximum is 4 MiB whatever the block holds, and a 1 MB file in one block had 33 x its 126 KB of input to decode into -- 3.7 ms on two wavefronts
 // instead of 0.28.  A block that does not fit the tighter room (it compressed better than 32 : 1) reports OUTPUT_CAPACITY and is decoded again with all of it.

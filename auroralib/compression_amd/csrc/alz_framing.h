@@ -123,6 +123,27 @@ inline void lz4_read_frame(const uint8_t* src, size_t len, size_t pos, uint32_t 
     } else { p -= 4; f.ends_file = true; }                                               // not a frame: stop in front of it
 }
 
+// Does any match of this LZ4 block point in front of the block's own output?  (A walk over the sequences: input only.)  Offset 0 is a
+// distance of 65 536 (E1): it reaches back while the block has produced less than that.
+inline bool lz4_block_reaches_back(const uint8_t* b, uint32_t n) {
+    uint64_t produced = 0; uint32_t p = 0;
+    while (p < n) {
+        const uint32_t tok = b[p++];
+        uint64_t lit = tok >> 4;
+        if (lit == 15) { uint32_t x; do { if (p >= n) return false; x = b[p++]; lit += x; } while (x == 255); }
+        if (lit > n - p) return false;                                  // truncated: the decoder reports it
+        p += (uint32_t)lit; produced += lit;
+        if (p >= n) break;
+        if (p + 2 > n) return false;
+        const uint32_t dist = b[p] | (b[p + 1] << 8); p += 2;
+        uint64_t ml = tok & 15;
+        if (ml == 15) { uint32_t x; do { if (p >= n) return false; x = b[p++]; ml += x; } while (x == 255); }
+        if ((dist == 0 ? 65536u : dist) > produced) return true;
+        produced += ml + 4;
+    }
+    return false;
+}
+
 // ---------------------------------------------------------------------------------------------- framed Snappy: one chunk header per call
 const uint8_t kSnappyId[10] = { 0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59 };                // Snappy.cs:17
 

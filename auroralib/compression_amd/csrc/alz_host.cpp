@@ -23,6 +23,7 @@
 #include "alz_aplib.h"
 #include "alz_inflate.h"
 #include "alz_checksum.h"
+#include "alz_xxh32.h"
 #include "alz_bitlz.h"
 
 static thread_local char g_err[512] = "";
@@ -1206,6 +1207,68 @@ int alz_checksum_batch_device(alz_ctx* c, uint32_t kind, uint32_t n, const uint8
 uint32_t alz_checksum_combine(uint32_t kind, uint32_t a, uint32_t b, uint64_t len_b) {
     if (kind > ALZ_CK_CRC32) return 0;
     return alz_checksum_join(kind, a, b, len_b, kind == ALZ_CK_CRC32 ? alz_crc_xpow_bytes(len_b) : 0u);
+}
+
+// ---------------------------------------------------------------- XXH32 of byte ranges (alz_xxh32.hip): the argument rules of the checksum family
+// One launch, four lanes per range.  The tables (ranges, results) live in the context's plan scratch; the device writes nothing but them.
+static int xxh32_batch(alz_ctx* c, bool device, uint32_t seed, uint32_t n, const uint8_t* src, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+    const char* what = device ? "alz_xxh32_batch_device" : "alz_xxh32_batch";
+    const bool missing = device ? n && (!ranges || !out || !src) : (n && (!ranges || !out)) || (src_bytes && !src);
+    if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
+    if (n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
+    for (uint32_t i = 0; i < n; i++)
+        if (!range_ok(ranges[i].src_off, ranges[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: range %u exceeds src_bytes", what, i);
+    c->last_kernel_ms = 0.f;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    const uint8_t* d_src = src;
+    if (!device) {
+        if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+        if ((rc = staged_h2d(c, c->d_src, src, src_bytes))) return rc;
+        d_src = (const uint8_t*)c->d_src;
+    }
+    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255;
+    if ((rc = grow(c, &c->d_plan, &c->d_plan_cap, a + (size_t)n * sizeof(uint32_t)))) return rc;
+    alz_stream* d_ranges = (alz_stream*)c->d_plan;
+    uint32_t* d_out = (uint32_t*)((uint8_t*)c->d_plan + a);
+    hipError_t e = hipMemcpyAsync(d_ranges, ranges, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) e = alz_launch_xxh32(c->stream, seed, d_src, d_ranges, n, d_out);
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the upload reads the caller's table)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+int alz_xxh32_batch(alz_ctx* c, uint32_t seed, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+    return xxh32_batch(c, false, seed, n, src_base, src_bytes, ranges, out);
+}
+int alz_xxh32_batch_device(alz_ctx* c, uint32_t seed, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+    return xxh32_batch(c, true, seed, n, d_src_base, src_bytes, ranges, out);
+}
+// The range copy of the batched LZ4 / Snappy file layer (alz_xxh32.h): HBM to HBM, one launch for the whole list
+int alz_host_range_copy(alz_ctx* c, uint32_t n, alz_copy_range* ranges, const uint8_t* d_src, size_t src_bytes, uint8_t* d_dst, size_t dst_bytes) {
+    if (!c || (n && (!ranges || !d_src || !d_dst))) return fail(ALZ_E_INVALID, "alz_host_range_copy: bad argument");
+    uint64_t pieces = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!range_ok(ranges[i].src_off, ranges[i].n, src_bytes) || !range_ok(ranges[i].dst_off, ranges[i].n, dst_bytes))
+            return fail(ALZ_E_INVALID, "alz_host_range_copy: range %u exceeds its buffer", i);
+        ranges[i].first = (uint32_t)pieces;
+        pieces += ((uint64_t)ranges[i].n + ALZ_COPY_PIECE - 1) / ALZ_COPY_PIECE;
+        if (pieces > 0x7FFFFFFFull) return fail(ALZ_E_UNSUPPORTED, "alz_host_range_copy: more than 2^31 pieces");
+    }
+    if (pieces == 0) return ALZ_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = grow(c, &c->d_plan, &c->d_plan_cap, (size_t)n * sizeof(alz_copy_range))) return rc;
+    hipError_t e = hipMemcpyAsync(c->d_plan, ranges, (size_t)n * sizeof(alz_copy_range), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = alz_launch_range_copy(c->stream, d_src, d_dst, (const alz_copy_range*)c->d_plan, n, (uint32_t)pieces);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "alz_host_range_copy failed: %s", hipGetErrorString(e));
+    return ALZ_OK;
 }
 
 // Device buffers of one encode call, freed on every exit path

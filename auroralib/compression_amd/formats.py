@@ -71,6 +71,40 @@ def _raise_for_outcome(rc, status, dst_len):
     check(rc)
 
 
+def _decompress_many(files, kind, limit, measure_batch, decode_batch, decode_decides=False):
+    """The two GPU batches behind every DecompressMany: measure_batch(table, src) gives the sizes up to `limit`, the destination holds exactly
+    the measured sizes, decode_batch(table, src, dst_bytes) fills it.  `kind` is what Stream.format of the batch family takes for the class.
+    decode_decides: a file whose measure ends in a stream error other than the limit is decoded as well, into the bytes it produces up to
+    there, and the decode's outcome is the file's (Decompress decodes first: a wrong content checksum in front of a truncated frame, a
+    Snappy chunk the decoder refuses).  Returns a list with, per file, its bytes -- or the exception instance Decompress would have raised."""
+    files = [bytes(f) for f in files]
+    src = np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8)
+    table, so = (A.Stream * len(files))(), 0
+    for i, f in enumerate(files):
+        table[i] = A.Stream(so, 0, len(f), limit, 0, 0, 0, kind)
+        so += len(f)
+
+    def outcome(r):
+        try:
+            _raise_for_outcome(r.rc, r.status, r.dst_len)
+        except Exception as e:              # the instance is the result
+            return e
+        return None
+    measured = measure_batch(table, src) if files else []
+    out = [outcome(r) for r in measured]
+    good, do = [i for i, e in enumerate(out) if e is None or (decode_decides and measured[i].rc == A.E_STREAM and measured[i].status != A.ST_OUTPUT_CAPACITY)], 0
+    if good:
+        sub = (A.Stream * len(good))()
+        for k, i in enumerate(good):
+            sub[k] = A.Stream(table[i].src_off, do, table[i].src_len, measured[i].dst_len, 0, 0, 0, kind)
+            do += measured[i].dst_len
+        dst, res = decode_batch(sub, src, do)
+        for k, i in enumerate(good):
+            e = outcome(res[k])
+            out[i] = e if e is not None else dst[int(sub[k].dst_off):int(sub[k].dst_off) + res[k].dst_len].tobytes()
+    return out
+
+
 class _Format:
     container = None
     provides_size = True
@@ -352,7 +386,18 @@ class LZOn(_Format):
     container = A.C_LZON
 
 
-class LZ4(_Format):
+class _FramedMany:
+    """DecompressMany of the classes whose files decode in batches (alz_framed_*): LZ4, LZ4Legacy, Snappy"""
+
+    def DecompressMany(self, files, limit=A.MEASURE_NO_BOUND):
+        """Decompress for a whole set of files in two GPU batches: one alz_framed_measure_batch (sizes up to `limit`), a destination of exactly
+        the measured sizes, one alz_framed_decode_batch.  Returns a list with, per file, its bytes -- or the exception instance Decompress would
+        have raised for it."""
+        ctx = _context()
+        return _decompress_many(files, self.container, limit, ctx.framed_measure_batch, ctx.framed_decode_batch, decode_decides=True)
+
+
+class LZ4(_FramedMany, _Format):
     """src/AuroraLib.Compression/Formats/Common/LZ4.cs + LZ4.Frame.cs: frame (default), legacy and skippable frames.
     BlockSize: 0x10000 / 0x40000 / 0x100000 / 0x400000 (default).  As in the reference, Compress writes a descriptor with
     only the version flag (`Flags &= IsVersion1`, LZ4.Frame.cs:184)."""
@@ -409,7 +454,7 @@ def _lz4_clamp_hint(total, n):
         return total if total < (1 << 31) else None
 
 
-class LZ4Legacy(_Format):
+class LZ4Legacy(_FramedMany, _Format):
     """src/AuroraLib.Compression/Formats/Common/LZ4Legacy.cs"""
     container = A.C_LZ4_LEGACY
     provides_size = False
@@ -418,7 +463,7 @@ class LZ4Legacy(_Format):
         return _lz4_capacity_hint(data)
 
 
-class Snappy(_Format):
+class Snappy(_FramedMany, _Format):
     """src/AuroraLib.Compression/Formats/Common/Snappy.cs (framing format, 64 KiB chunks)."""
     container = A.C_SNAPPY
     provides_size = False
@@ -614,34 +659,8 @@ class _InflateFile:
         """Decompress for a whole set of files in two GPU batches: one alz_zfile_measure_batch (sizes up to `limit`), a destination of exactly
         the measured sizes, one alz_zfile_decode_batch.  Returns a list with, per file, its bytes -- or the exception instance Decompress would
         have raised for it."""
-        files = [bytes(f) for f in files]
-        kind = A.ZFILE_ZLIB if self.prefix == "zlib" else A.ZFILE_GZIP
-        src = np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8)
-        table, so = (A.Stream * len(files))(), 0
-        for i, f in enumerate(files):
-            table[i] = A.Stream(so, 0, len(f), limit, 0, 0, 0, kind)
-            so += len(f)
-
-        def outcome(r):
-            try:
-                _raise_for_outcome(r.rc, r.status, r.dst_len)
-            except Exception as e:              # the instance is the result
-                return e
-            return None
         ctx = _context()
-        measured = ctx.zfile_measure_batch(table, src) if files else []
-        out = [outcome(r) for r in measured]
-        good, do = [i for i, e in enumerate(out) if e is None], 0
-        if good:
-            sub = (A.Stream * len(good))()
-            for k, i in enumerate(good):
-                sub[k] = A.Stream(table[i].src_off, do, table[i].src_len, measured[i].dst_len, 0, 0, 0, kind)
-                do += measured[i].dst_len
-            dst, res = ctx.zfile_decode_batch(sub, src, do)
-            for k, i in enumerate(good):
-                e = outcome(res[k])
-                out[i] = e if e is not None else dst[int(sub[k].dst_off):int(sub[k].dst_off) + res[k].dst_len].tobytes()
-        return out
+        return _decompress_many(files, A.ZFILE_ZLIB if self.prefix == "zlib" else A.ZFILE_GZIP, limit, ctx.zfile_measure_batch, ctx.zfile_decode_batch)
 
     def Compress(self, data, settings=None):
         raise NotImplementedError(INFLATE_NO_ENCODER % type(self).__name__)

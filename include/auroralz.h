@@ -568,8 +568,8 @@ int alz_gzip_measure(alz_ctx* ctx, const uint8_t* src, size_t src_len, size_t si
  * alz_checksum_combine: the checksum of A || B from the checksum `a` of A, the checksum `b` of B and the length of B (zlib's
  *   adler32_combine / crc32_combine): pure host code, no context, the very arithmetic the second launch runs.  len_b == 0 returns a.
  *   An unknown kind returns 0.
- * NOT BUILT: CRC-32C and xxHash32 (the checksums of the Snappy and LZ4 containers), and a checksum fused into a decode kernel's
- *   write-back. */
+ * NOT BUILT: CRC-32C (the checksum of the Snappy container, which the reference does not verify), and a checksum fused into a decode
+ *   kernel's write-back.  XXH32, the checksum of the LZ4 frame format, has entry points of its own below (alz_xxh32_batch*). */
 typedef enum alz_checksum_kind { ALZ_CK_ADLER32 = 0, ALZ_CK_CRC32 = 1 } alz_checksum_kind;
 int alz_checksum_batch(alz_ctx* ctx, uint32_t kind, uint32_t n, const uint8_t* src_base, size_t src_bytes,
                        const alz_stream* ranges, uint32_t* out);
@@ -606,6 +606,53 @@ int alz_zfile_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, si
                            uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
 int alz_zfile_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
                             alz_file_result* results);
+
+/* ---------------------------------------- XXH32 of byte ranges on the GPU
+ * out[i] is XXH32 (xxHash, 32 bits: the block and content checksum of the LZ4 frame format, LZ4.Frame.cs:17-18) of the n ranges[i] with
+ * `seed` (the frame format uses 0).  The argument rules are those of alz_checksum_batch*: a range is src_off / src_len of its alz_stream,
+ * EVERY OTHER FIELD IS IGNORED; ranges may overlap, be empty (0x02CC5D05 with seed 0) and start at any byte; n == 0 is ALZ_OK; a NULL
+ * ctx, a range outside src_bytes, or NULL ranges / out with n > 0 are ALZ_E_INVALID (checked before anything is uploaded).  The device
+ * writes nothing but the n results (and the library's own scratch).  The kernel READS a range in aligned dwords, each of which holds a
+ * byte of the range, so the slack rule of alz_aplib_* (64 readable bytes behind the buffer) covers it.
+ * XXH32 is not linear -- the partial results of two pieces cannot be joined -- so one range is a serial chain over its 16-byte stripes:
+ * four lanes work on a range (one per accumulator), 16 ranges share a wavefront, one launch.  The parallelism is the NUMBER of ranges:
+ * thousands of frames of some KiB each are what this is for; one range of many MiB runs on four lanes and is better hashed on the host
+ * (MI355X, docs/EXPERIMENTS.md 18: 10 000 ranges of 256 KiB at 742 GB/s; ONE range of 64 MiB at 0.33 GB/s, 42 x slower than one host
+ * thread).  alz_last_kernel_ms reports the device time of the launch. */
+int alz_xxh32_batch(alz_ctx* ctx, uint32_t seed, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                    const alz_stream* ranges, uint32_t* out);
+/* d_src_base is a DEVICE pointer; out is on the host */
+int alz_xxh32_batch_device(alz_ctx* ctx, uint32_t seed, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                           const alz_stream* ranges, uint32_t* out);
+
+/* ---------------------------------------- LZ4 and Snappy files in batches
+ * What alz_container_decompress / alz_container_measure do for one file of ALZ_C_LZ4_FRAME, ALZ_C_LZ4_LEGACY or ALZ_C_SNAPPY, for n files
+ * in one call.  files[i].format is one of these three alz_container values -- a batch may mix them, any other value is ALZ_E_INVALID;
+ * src_off / src_len is the whole file; dst_off / dst_cap is where its output goes (measure: dst_off is ignored, dst_cap is the size
+ * limit); decom_len, aux0 and aux1 are IGNORED.  All buffers are in host memory.  alz_file_result is the one of alz_zfile_*.
+ * THE CONTRACT IS DIFFERENTIAL, against the single-file call on file i alone with the same capacity (measure: the same limit):
+ *   that call returns ALZ_OK or ALZ_E_STREAM:  results[i].rc / status / dst_len / src_used are what it returns, and the bytes at
+ *     [dst_off, dst_off + dst_len) are the bytes it delivers -- also the partial output of a file that fails.
+ *   it returns ALZ_E_FORMAT, ALZ_E_CHECKSUM or ALZ_E_UNSUPPORTED:  results[i].rc is that code, status is ALZ_ST_OK, dst_len and src_used
+ *     are 0 and the bytes of the slot are unspecified (the single-file call leaves its out-parameters unset).
+ * Nothing outside a file's [dst_off, dst_off + dst_cap) is written on the host.  A file's failure is that file's rc; the call itself fails
+ * only for bad arguments or a HIP error.
+ * One decode batch: the framing is read on the host by the readers of the single-file layer (block checksums are verified there, over
+ * source bytes in host memory); the source is uploaded once and one device destination covers all slots.  The compressed LZ4 blocks of ALL
+ * files are measured first (one alz_measure_batch_device), which settles every block's place; then a round is ONE device-resident decode:
+ * the first holds every LZ4 block that reaches into nothing in front of itself -- of whatever frame or file -- and every compressed Snappy
+ * chunk at its declared place; a block of a linked frame that reads earlier output runs one round behind the blocks in front of it, and
+ * a Snappy file with a chunk that decodes to more than it declares is read on in order, one chunk per round.  Stored blocks and chunks
+ * are copied HBM to HBM, one launch per round; the outputs of the frames with a content checksum are hashed where they lie by ONE
+ * alz_xxh32_batch_device; the outputs are downloaded once.  alz_framed_measure_batch is the same walk without the decode, with content
+ * checksums taken as correct and the declared content size checked.  MI355X (docs/EXPERIMENTS.md 18): 2 000 files of 64 KiB in one
+ * call take 30 ms (LZ4 frames with content checksums) and 27 ms (Snappy), 11.7 and 10.4 times less than a loop of the single-file call.
+ * NOT BUILT: device-resident forms, batched compression, CRC-32C.  The single-file entry points are unchanged, host-side XXH32 included:
+ *   they are the yardstick. */
+int alz_framed_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
+                            uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
+int alz_framed_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
+                             alz_file_result* results);
 
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's

@@ -62,7 +62,7 @@ namespace AuroraLib.Compression.Amd
         public uint Aux1;
     }
 
-    /// <summary>alz_file_result (16 bytes): what the single-file call returns for one file of an alz_zfile_* batch.</summary>
+    /// <summary>alz_file_result (16 bytes): what the single-file call returns for one file of an alz_zfile_* or alz_framed_* batch.</summary>
     [StructLayout(LayoutKind.Sequential, Size = 16)]
     public struct AlzFileResult
     {
@@ -190,6 +190,18 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_zfile_decode_batch(IntPtr ctx, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
         [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_zfile_measure_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, AlzFileResult* results);
+
+        // XXH32 (the checksum of the LZ4 frame format) of byte ranges on the GPU: the argument rules of alz_checksum_batch, a seed in place of the kind ...
+        [DllImport(Lib)] internal static extern int alz_xxh32_batch(IntPtr ctx, uint seed, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* ranges, uint* hashes);
+        [DllImport(Lib)] internal static extern int alz_xxh32_batch_device(IntPtr ctx, uint seed, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* ranges, uint* hashes);
+        // ... and LZ4 (frame 22, legacy 7) / framed Snappy (9) files in batches: AlzStream.Format is the alz_container value; per file what
+        // alz_container_decompress / alz_container_measure return for it alone
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_framed_decode_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_framed_measure_batch(IntPtr ctx, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* files, AlzFileResult* results);
 
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU

@@ -20,6 +20,8 @@ FAMILIES = {
     "checksum": ["alz_checksum.hip", "alz_checksum.h"],   # Adler-32 / CRC-32 of byte ranges: no committed counters
     "zfile": ["alz_zfile.h"],                          # host code: the zlib / gzip framing shared by the two file layers (no kernel)
     "framing": ["alz_framing.h"],                      # host code: the LZ4 / Snappy framing readers shared by file decode and measure (no kernel)
+    "xxh32": ["alz_xxh32.hip", "alz_xxh32.h"],         # XXH32 of byte ranges and the range copy of the batched LZ4 / Snappy file layer: no committed counters
+    "filebatch": ["alz_file_batch.h"],                 # host code: what the two batched file layers share (no kernel)
 }
 FILES = ("traffic.json", "insts.json")
 
