@@ -178,4 +178,17 @@ FRAMED_PROTOTYPES = {
     "alz_framed_measure_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
 }
 
+# CRC-32C of byte ranges on the GPU (the checksum of a framed Snappy chunk, before its mask): the checksum family's argument list without a kind
+_CRC32C_BATCH = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+CRC32C_PROTOTYPES = {
+    "alz_crc32c_batch": _CRC32C_BATCH, "alz_crc32c_batch_device": _CRC32C_BATCH,
+    "alz_crc32c_combine": [C.c_uint32, C.c_uint32, C.c_uint64],                    # returns uint32_t (CRC32C_RESTYPES)
+}
+CRC32C_RESTYPES = {"alz_crc32c_combine": C.c_uint32}
+
+# LZ4 (frame, legacy) and framed Snappy files WRITTEN in batches: Stream.format is one of FRAMED_CONTAINERS, aux0 an LZ4 frame's block size
+FRAMING_COMPRESS_PROTOTYPES = {
+    "alz_framing_compress_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16 and C.sizeof(FileResult) == 16

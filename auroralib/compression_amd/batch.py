@@ -262,6 +262,32 @@ class Context:
         check(self.lib.alz_framed_measure_batch(self.h, len(files), _vp(src), src.nbytes, files, res))
         return res
 
+    # ---- CRC-32C of byte ranges (the checksum of a framed Snappy chunk, before its mask); a range is src_off / src_len of its Stream
+    def _crc32c(self, fn, ranges, src, src_bytes):
+        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
+        check(fn(self.h, len(ranges), src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:len(ranges)]
+
+    def crc32c_batch(self, ranges, src):
+        """alz_crc32c_batch on a host buffer -> a uint32 array, one CRC-32C per range."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        return self._crc32c(self.lib.alz_crc32c_batch, ranges, _vp(src), src.nbytes)
+
+    def crc32c_batch_device(self, ranges, d_src, src_bytes):
+        """alz_crc32c_batch_device: the same with the bytes already in HBM at d_src; last_kernel_ms() is the device time of the two launches."""
+        return self._crc32c(self.lib.alz_crc32c_batch_device, ranges, d_src, src_bytes)
+
+    # ---- LZ4 and Snappy files written in batches: Stream.format is A.C_LZ4_FRAME, A.C_LZ4_LEGACY or A.C_SNAPPY, src_off / src_len the raw input
+    def framing_compress_batch(self, files, src, dst_bytes, dst=None, quality=8, strategy=0, min_distance=0, max_window_bits=0):
+        """alz_framing_compress_batch on host buffers -> (dst, results): per file what alz_container_compress writes and returns for it alone
+        (aux0: the block size of an LZ4 frame).  `dst`: a caller-owned uint8 array of >= dst_bytes to write into (default: a new one)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        st = A.Settings(quality, max_window_bits, strategy, min_distance)
+        check(self.lib.alz_framing_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

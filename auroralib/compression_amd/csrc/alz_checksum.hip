@@ -1,4 +1,4 @@
-// alz_checksum.hip -- Adler-32 and CRC-32 of byte ranges in HBM (alz_checksum_batch*).  Two launches per batch:
+// alz_checksum.hip -- Adler-32, CRC-32 and CRC-32C of byte ranges in HBM (alz_checksum_batch*, alz_crc32c_batch*).  Two launches per batch:
 //
 //   chunk kernel  every range is cut into chunks of `chunk` bytes; ONE WAVEFRONT sums one chunk, four wavefronts to a workgroup, the grid
 //                 over all chunks of all ranges -- 10 000 ranges of 256 KiB and one range of 1 GiB fill the GPU alike.  A chunk is read in
@@ -11,7 +11,7 @@
 // granules (the bytes of a granule, the bytes weighted by their place in the granule, the byte sums weighted by the round) and reduces them
 // once, behind the chunk: with at most ALZ_CHECKSUM_CHUNK_MAX = 1 MiB to a chunk (1 025 rounds) the largest is 4 080 * 1 025 * 1 026 / 2 <
 // 2^32.  The places count from the first granule; the head h of that granule in front of the chunk is taken out at the end.
-// CRC-32 is linear over GF(2): a lane carries the raw CRC (start value 0) of ITS granules, acc = acc x^8192 + g0 x^128 + g1 x^96 + g2 x^64 +
+// A CRC (CRC-32 and CRC-32C differ in the polynomial P alone: alz_checksum_poly) is linear over GF(2): a lane carries the raw CRC (start value 0) of ITS granules, acc = acc x^8192 + g0 x^128 + g1 x^96 + g2 x^64 +
 // g3 x^32 mod P per round (its next granule lies 1 KiB = 8 192 bits on).  The five multipliers are constants, so each product is 32 steps of
 // "coefficient set ? xor a literal" in the vector ALU -- no table, no LDS.  Behind the chunk a lane multiplies by x^(8 e), e the bytes between
 // the end of its last granule and the end of the chunk (-15 .. 1 008: a table of x^(8 i), i = e + 15, and one multiplication by x^-120), and
@@ -26,31 +26,21 @@ namespace {
 
 constexpr u32 kM = ALZ_ADLER_BASE;
 
-constexpr u32 xpow_c(u64 n) {                                                   // x^n mod P at compile time
-    u32 p = ALZ_CRC_ONE, s = ALZ_CRC_ONE >> 1;
-    while (n) { if (n & 1u) p = alz_crc_mul(p, s); s = alz_crc_mul(s, s); n >>= 1; }
-    return p;
-}
-constexpr u32 kXInv120 = xpow_c(0xFFFFFFFFull - 120u);                          // x^-120: the order of x divides 2^32 - 1
-static_assert(alz_crc_mul(kXInv120, xpow_c(120)) == ALZ_CRC_ONE, "x^(2^32 - 1) is not 1 modulo the CRC-32 polynomial");
+template <u32 P> constexpr bool order_holds() { return alz_crc_mul<P>(alz_crc_xinv120<P>(), alz_crc_xpow_c<P>(120)) == ALZ_CRC_ONE; }
+static_assert(order_holds<ALZ_CRC_POLY>() && order_holds<ALZ_CRC32C_POLY>(), "x^order is not 1 modulo a CRC polynomial (alz_crc_order)");
 
-struct xbyte_table {                                                            // x^(8 i), i < 1024
-    u32 v[1024];
-    constexpr xbyte_table() : v{} {
-        u32 p = ALZ_CRC_ONE;
-        for (int i = 0; i < 1024; i++) { v[i] = p; for (int k = 0; k < 8; k++) p = alz_crc_xtime(p); }
-    }
-};
-__device__ const xbyte_table kXByte{};
+__device__ const alz_crc_xbyte_table<ALZ_CRC_POLY> kXByte{};
+__device__ const alz_crc_xbyte_table<ALZ_CRC32C_POLY> kXByteC{};
+template <u32 P> __device__ __forceinline__ u32 xbyte(int i) { return P == ALZ_CRC32C_POLY ? kXByteC.v[i] : kXByte.v[i]; }
 
 // a K mod P for a constant K: unrolled, the 32 multiples of K fold to literals
-template <u32 K>
+template <u32 P, u32 K>
 __device__ __forceinline__ u32 mul_const(u32 a) {
     u32 p = 0, b = K;
 #pragma unroll
     for (int j = 0; j < 32; j++) {
         p ^= (u32)((int32_t)(a << j) >> 31) & b;
-        b = alz_crc_xtime(b);
+        b = alz_crc_xtime<P>(b);
     }
     return p;
 }
@@ -83,12 +73,11 @@ __device__ __forceinline__ u32 range_of_chunk(const u32* __restrict__ first, u32
     return lo;
 }
 
-}   // namespace
-
-// partial[g]: Adler-32 of chunk g, or its raw CRC (start value 0, no final inversion)
+// partial[g]: Adler-32 of chunk g, or its raw CRC (start value 0, no final inversion).  KIND: an alz_checksum_kind or ALZ_CK_CRC32C.
 template <u32 KIND>
-__global__ __launch_bounds__(256) void alz_checksum_chunk_kernel(const u8* __restrict__ src, const alz_stream* __restrict__ ranges, u32 n,
-                                                                 const u32* __restrict__ first, u32 total, u32 chunk, u32* __restrict__ partial) {
+__device__ __forceinline__ void chunk_body(const u8* __restrict__ src, const alz_stream* __restrict__ ranges, u32 n,
+                                           const u32* __restrict__ first, u32 total, u32 chunk, u32* __restrict__ partial) {
+    constexpr u32 P = alz_checksum_poly(KIND);
     const u32 lane = threadIdx.x & 63u;
     const u32 g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (g >= total) return;
@@ -134,55 +123,82 @@ __global__ __launch_bounds__(256) void alz_checksum_chunk_kernel(const u8* __res
             u32 d[4] = {v.x, v.y, v.z, v.w};
             const int lo = q == 0 ? (int)h : 0, hi = (int)(span - q * 16u);
             if (lo != 0 || hi < 16) mask_granule(d, lo, hi);
-            acc = mul_const<xpow_c(8192)>(acc) ^ mul_const<xpow_c(128)>(d[0]) ^ mul_const<xpow_c(96)>(d[1]) ^ mul_const<xpow_c(64)>(d[2]) ^ mul_const<xpow_c(32)>(d[3]);
+            acc = mul_const<P, alz_crc_xpow_c<P>(8192)>(acc) ^ mul_const<P, alz_crc_xpow_c<P>(128)>(d[0]) ^ mul_const<P, alz_crc_xpow_c<P>(96)>(d[1]) ^
+                  mul_const<P, alz_crc_xpow_c<P>(64)>(d[2]) ^ mul_const<P, alz_crc_xpow_c<P>(32)>(d[3]);
         }
         u32 mine = 0;
         if (q != lane) {                                                        // granule q - 64 was this lane's last: it ends at byte 16 (q - 63)
             const int e = (int)span - (int)(16u * (q - 63u));                   // -15 .. 1 008
-            mine = alz_crc_mul(acc, kXByte.v[e + 15]);
+            mine = alz_crc_mul<P>(acc, xbyte<P>(e + 15));
         }
         const u32 all = wave_xor(mine);
-        if (lane == 0) partial[g] = alz_crc_mul(all, kXInv120);
+        if (lane == 0) partial[g] = alz_crc_mul<P>(all, alz_crc_xinv120<P>());
     }
 }
 
 // out[r]: the checksum of range r from its chunks' partial sums
 template <u32 KIND>
-__global__ __launch_bounds__(64) void alz_checksum_fold_kernel(const alz_stream* __restrict__ ranges, const u32* __restrict__ first, u32 chunk,
-                                                               const u32* __restrict__ partial, u32* __restrict__ out) {
+__device__ __forceinline__ void fold_body(const alz_stream* __restrict__ ranges, const u32* __restrict__ first, u32 chunk,
+                                          const u32* __restrict__ partial, u32* __restrict__ out) {
+    constexpr u32 P = alz_checksum_poly(KIND);
+    constexpr bool CRC = KIND != ALZ_CK_ADLER32;
     const u32 r = blockIdx.x, lane = threadIdx.x;
     const u32 f = first[r], C = first[r + 1] - f, len = ranges[r].src_len;
     const u32 m = (C + 63u) / 64u;                                              // chunks per lane, in order
     const u32 c0 = lane * m < C ? lane * m : C, c1 = c0 + m < C ? c0 + m : C;
-    const u32 xck = KIND == ALZ_CK_CRC32 ? alz_crc_xpow_bytes(chunk) : 0u;
-    u32 v = KIND == ALZ_CK_CRC32 ? 0u : 1u, bytes = 0;
+    const u32 xck = CRC ? alz_crc_xpow_bytes<P>(chunk) : 0u;
+    u32 v = alz_checksum_empty(KIND), bytes = 0;
     for (u32 c = c0; c < c1; c++) {
         const u64 left = (u64)len - (u64)c * chunk;
         const u32 cl = left < chunk ? (u32)left : chunk;
-        v = alz_checksum_join(KIND, v, partial[f + c], cl, KIND != ALZ_CK_CRC32 || cl == chunk ? xck : alz_crc_xpow_bytes(cl));
+        v = alz_checksum_join(KIND, v, partial[f + c], cl, !CRC || cl == chunk ? xck : alz_crc_xpow_bytes<P>(cl));
         bytes += cl;
     }
     const u32 used = m ? (C + m - 1u) / m : 0u;                                 // lanes that hold chunks
     for (u32 o = 1; o < used; o <<= 1) {
         const u32 pv = __shfl_down(v, o, 64), pb = __shfl_down(bytes, o, 64);
-        const u32 j = alz_checksum_join(KIND, v, pv, pb, KIND == ALZ_CK_CRC32 ? alz_crc_xpow_bytes(pb) : 0u);
+        const u32 j = alz_checksum_join(KIND, v, pv, pb, CRC ? alz_crc_xpow_bytes<P>(pb) : 0u);
         if ((lane & (2u * o - 1u)) == 0 && lane + o < 64u) { v = j; bytes += pb; }
     }
-    if (lane == 0) out[r] = KIND == ALZ_CK_CRC32 ? v ^ alz_crc_mul(0xFFFFFFFFu, alz_crc_xpow_bytes(len)) ^ 0xFFFFFFFFu : v;
+    if (lane == 0) out[r] = CRC ? v ^ alz_crc_mul<P>(0xFFFFFFFFu, alz_crc_xpow_bytes<P>(len)) ^ 0xFFFFFFFFu : v;
+}
+
+}   // namespace
+
+template <u32 KIND>
+__global__ __launch_bounds__(256) void alz_checksum_chunk_kernel(const u8* __restrict__ src, const alz_stream* __restrict__ ranges, u32 n,
+                                                                 const u32* __restrict__ first, u32 total, u32 chunk, u32* __restrict__ partial) {
+    chunk_body<KIND>(src, ranges, n, first, total, chunk, partial);
+}
+template <u32 KIND>
+__global__ __launch_bounds__(64) void alz_checksum_fold_kernel(const alz_stream* __restrict__ ranges, const u32* __restrict__ first, u32 chunk,
+                                                               const u32* __restrict__ partial, u32* __restrict__ out) {
+    fold_body<KIND>(ranges, first, chunk, partial, out);
+}
+// CRC-32C: the same two bodies over the Castagnoli polynomial, as kernels with names of their own
+__global__ __launch_bounds__(256) void alz_crc32c_chunk_kernel(const u8* __restrict__ src, const alz_stream* __restrict__ ranges, u32 n,
+                                                               const u32* __restrict__ first, u32 total, u32 chunk, u32* __restrict__ partial) {
+    chunk_body<ALZ_CK_CRC32C>(src, ranges, n, first, total, chunk, partial);
+}
+__global__ __launch_bounds__(64) void alz_crc32c_fold_kernel(const alz_stream* __restrict__ ranges, const u32* __restrict__ first, u32 chunk,
+                                                             const u32* __restrict__ partial, u32* __restrict__ out) {
+    fold_body<ALZ_CK_CRC32C>(ranges, first, chunk, partial, out);
 }
 
 hipError_t alz_launch_checksum(uint32_t kind, hipStream_t stream, const void* d_src, const alz_stream* d_ranges, uint32_t n,
                                const uint32_t* d_first, uint32_t total_chunks, uint32_t chunk, uint32_t* d_partial, uint32_t* d_out) {
-    if (kind > ALZ_CK_CRC32 || chunk == 0 || chunk % 1024u || chunk > ALZ_CHECKSUM_CHUNK_MAX) return hipErrorInvalidValue;
+    if (kind > ALZ_CK_CRC32C || chunk == 0 || chunk % 1024u || chunk > ALZ_CHECKSUM_CHUNK_MAX) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     if (total_chunks) {
         const dim3 grid((total_chunks + 3u) / 4u), block(256);
-        if (kind == ALZ_CK_CRC32) hipLaunchKernelGGL(alz_checksum_chunk_kernel<ALZ_CK_CRC32>, grid, block, 0, stream, (const u8*)d_src, d_ranges, n, d_first, total_chunks, chunk, d_partial);
+        if (kind == ALZ_CK_CRC32C) hipLaunchKernelGGL(alz_crc32c_chunk_kernel, grid, block, 0, stream, (const u8*)d_src, d_ranges, n, d_first, total_chunks, chunk, d_partial);
+        else if (kind == ALZ_CK_CRC32) hipLaunchKernelGGL(alz_checksum_chunk_kernel<ALZ_CK_CRC32>, grid, block, 0, stream, (const u8*)d_src, d_ranges, n, d_first, total_chunks, chunk, d_partial);
         else hipLaunchKernelGGL(alz_checksum_chunk_kernel<ALZ_CK_ADLER32>, grid, block, 0, stream, (const u8*)d_src, d_ranges, n, d_first, total_chunks, chunk, d_partial);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (kind == ALZ_CK_CRC32) hipLaunchKernelGGL(alz_checksum_fold_kernel<ALZ_CK_CRC32>, dim3(n), dim3(64), 0, stream, d_ranges, d_first, chunk, d_partial, d_out);
+    if (kind == ALZ_CK_CRC32C) hipLaunchKernelGGL(alz_crc32c_fold_kernel, dim3(n), dim3(64), 0, stream, d_ranges, d_first, chunk, d_partial, d_out);
+    else if (kind == ALZ_CK_CRC32) hipLaunchKernelGGL(alz_checksum_fold_kernel<ALZ_CK_CRC32>, dim3(n), dim3(64), 0, stream, d_ranges, d_first, chunk, d_partial, d_out);
     else hipLaunchKernelGGL(alz_checksum_fold_kernel<ALZ_CK_ADLER32>, dim3(n), dim3(64), 0, stream, d_ranges, d_first, chunk, d_partial, d_out);
     return hipGetLastError();
 }

@@ -161,7 +161,6 @@ uint32_t crc32c(const uint8_t* p, size_t len) {
     for (size_t i = 0; i < len; i++) c = table[(c ^ p[i]) & 0xFF] ^ (c >> 8);
     return c ^ 0xFFFFFFFFu;
 }
-inline uint32_t snappy_crc_mask(uint32_t crc) { return ((crc >> 15) | (crc << 17)) + 0xa282ead8u; }
 
 // Which branches of the LZ4 file decode ran, process-wide (alz_debug_container_counters): what a test asserts to show that its cases reached each of them.
 enum { CNT_BATCH_BLOCKS, CNT_SPLIT_PLANS, CNT_TIGHT_RETRIES, CNT_FALLBACK_BLOCKS, CNT_LINKED_BLOCKS, CNT_STORED_BLOCKS, CNT_COUNT };
@@ -342,7 +341,7 @@ struct BlockSlots {
 int encode_blocks(alz_ctx* ctx, uint32_t fmt, const alz_settings* st, const uint8_t* src, size_t n, size_t block, BlockSlots& tmp, size_t& slot,
                   std::vector<alz_result>& rs) {
     const size_t nb = (n + block - 1) / block;
-    slot = (block + block / 4 + 64 + 255) & ~(size_t)255;
+    slot = write_slot_bytes(block);
     if (!tmp.resize(nb * slot + 64)) return ALZ_E_NOMEM;
     std::vector<alz_stream> ss(nb); rs.resize(nb);
     for (size_t i = 0; i < nb; i++) {
@@ -352,36 +351,25 @@ int encode_blocks(alz_ctx* ctx, uint32_t fmt, const alz_settings* st, const uint
     }
     return nb ? alz_encode_batch(ctx, nullptr, st, (uint32_t)nb, src, n, ss.data(), tmp.data(), tmp.size(), rs.data(), nullptr) : ALZ_OK;
 }
+// the sink of a single-file writer (alz_framing.h): every piece is copied into the caller's buffer as it is laid out
+struct HostSink {
+    uint8_t* dst; const uint8_t* src; const uint8_t* slots; size_t slot_bytes;
+    void bytes(size_t at, const uint8_t* p, size_t k) { memcpy(dst + at, p, k); }
+    void slot(size_t at, size_t i, size_t k) { memcpy(dst + at, slots + i * slot_bytes, k); }
+    void source(size_t at, size_t off, size_t k) { memcpy(dst + at, src + off, k); }
+};
 
-// LZ4.Compress  LZ4.cs:113-160 (legacy) / CompressLZ4FrameHeader  LZ4.Frame.cs:176-229.  `Flags &= IsVersion1`
-// (LZ4.Frame.cs:184) leaves only the version bit: the frame written never carries a content size or checksums.
+// LZ4.Compress  LZ4.cs:113-160 (legacy) / CompressLZ4FrameHeader  LZ4.Frame.cs:176-229: the rules are lz4_write_open / lz4_write_blocks (alz_framing.h)
 int lz4_file_compress(alz_ctx* ctx, bool legacy, uint32_t block_size, const alz_settings* st, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* dst_len) {
-    size_t o = 0;
-    if (cap < 16) return ALZ_E_NOMEM;
-    if (legacy) { wr32(dst, kLz4Legacy, false); o = 4; block_size = 0x800000u; }       // (int)BlockMaxSizes.Block4MB * 2
-    else {
-        uint8_t bdb;
-        switch (block_size) { case 0: block_size = 0x400000; bdb = 0x70; break; case 0x10000: bdb = 0x40; break; case 0x40000: bdb = 0x50; break;
-                              case 0x100000: bdb = 0x60; break; case 0x400000: bdb = 0x70; break; default: return ALZ_E_INVALID; }
-        wr32(dst, kLz4Frame, false); dst[4] = 0x40; dst[5] = bdb; dst[6] = (uint8_t)((xxh32(dst + 4, 2, 0) >> 8) & 0xFF); o = 7;
-    }
-    if (n && n % block_size != 0 && n % block_size < 5) return ALZ_E_INVALID;            // source.Slice(0, Length - 5) throws  LZ4.cs:208
-    BlockSlots tmp; std::vector<alz_result> rs; size_t slot = 0;
-    int rc = encode_blocks(ctx, ALZ_FMT_LZ4_BLOCK, st, src, n, block_size, tmp, slot, rs);
+    Lz4Writer w;
+    int rc = lz4_write_open(legacy, block_size, n, cap, w);
     if (rc != ALZ_OK) return rc;
-    for (size_t i = 0; i < rs.size(); i++) {
-        const size_t bl = n - i * block_size < block_size ? n - i * block_size : block_size;
-        if (rs[i].status != ALZ_ST_OK) return rs[i].status == ALZ_ST_OUTPUT_CAPACITY ? ALZ_E_NOMEM : ALZ_E_INVALID;
-        if (!legacy && rs[i].dst_len >= block_size) {                                    // buffer.Position >= (int)BlockSize: stored
-            if (o + 4 + bl > cap) return ALZ_E_NOMEM;
-            wr32(dst + o, (uint32_t)bl | 0x80000000u, false); memcpy(dst + o + 4, src + i * block_size, bl); o += 4 + bl;
-        } else {
-            if (o + 4 + rs[i].dst_len > cap) return ALZ_E_NOMEM;
-            wr32(dst + o, rs[i].dst_len, false); memcpy(dst + o + 4, tmp.data() + i * slot, rs[i].dst_len); o += 4 + rs[i].dst_len;
-        }
-    }
-    if (legacy) { if (o + 1 > cap) return ALZ_E_NOMEM; dst[o++] = 0xFF; }                // EOF flag
-    else { if (o + 4 > cap) return ALZ_E_NOMEM; wr32(dst + o, 0, false); o += 4; }       // EndMark
+    BlockSlots tmp; std::vector<alz_result> rs; size_t slot = 0;
+    rc = encode_blocks(ctx, ALZ_FMT_LZ4_BLOCK, st, src, n, w.block, tmp, slot, rs);
+    if (rc != ALZ_OK) return rc;
+    HostSink sink{dst, src, tmp.data(), slot};
+    size_t o = 0;
+    if ((rc = lz4_write_blocks(w, n, rs.data(), cap, sink, &o)) != ALZ_OK) return rc;
     if (dst_len) *dst_len = o;
     return ALZ_OK;
 }
@@ -468,27 +456,20 @@ int snappy_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t
     return fst == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM;
 }
 
-// Snappy.Compress  Formats/Common/Snappy.cs:71-107
+// Snappy.Compress  Formats/Common/Snappy.cs:71-107: the rules are snappy_write_open / snappy_write_chunks (alz_framing.h); the chunks are hashed here, on the host
 int snappy_file_compress(alz_ctx* ctx, const alz_settings* st, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* dst_len) {
-    if (cap < 10) return ALZ_E_NOMEM;
-    memcpy(dst, kSnappyId, 10);
-    size_t o = 10;
-    BlockSlots tmp; std::vector<alz_result> rs; size_t slot = 0;
-    int rc = encode_blocks(ctx, ALZ_FMT_SNAPPY_RAW, st, src, n, 0x10000, tmp, slot, rs);
+    int rc = snappy_write_open(cap);
     if (rc != ALZ_OK) return rc;
-    for (size_t i = 0; i < rs.size(); i++) {
-        const size_t cs = n - i * 0x10000 < 0x10000 ? n - i * 0x10000 : 0x10000;
-        if (rs[i].status != ALZ_ST_OK) return ALZ_E_INVALID;
-        const uint32_t crc = snappy_crc_mask(crc32c(src + i * 0x10000, cs));
-        const bool stored = rs[i].dst_len >= cs;                                         // buffer.Length >= chunkSize
-        const size_t body = stored ? cs : rs[i].dst_len;
-        if (o + 8 + body > cap) return ALZ_E_NOMEM;
-        dst[o] = stored ? 1 : 0;
-        dst[o + 1] = (uint8_t)(body + 4); dst[o + 2] = (uint8_t)((body + 4) >> 8); dst[o + 3] = (uint8_t)((body + 4) >> 16);
-        wr32(dst + o + 4, crc, false);
-        memcpy(dst + o + 8, stored ? src + i * 0x10000 : tmp.data() + i * slot, body);
-        o += 8 + body;
-    }
+    BlockSlots tmp; std::vector<alz_result> rs; size_t slot = 0;
+    rc = encode_blocks(ctx, ALZ_FMT_SNAPPY_RAW, st, src, n, kSnappyChunk, tmp, slot, rs);
+    if (rc != ALZ_OK) return rc;
+    HostSink sink{dst, src, tmp.data(), slot};
+    size_t o = 0;
+    rc = snappy_write_chunks(n, rs.data(), cap, sink, [&](size_t i) {
+        const size_t off = i * (size_t)kSnappyChunk;
+        return crc32c(src + off, n - off < kSnappyChunk ? n - off : kSnappyChunk);
+    }, &o);
+    if (rc != ALZ_OK) return rc;
     if (dst_len) *dst_len = o;
     return ALZ_OK;
 }
@@ -1283,6 +1264,9 @@ int alz_debug_container_counters(uint64_t* out, int n) {
     for (int i = 0; i < n && i < CNT_COUNT; i++) out[i] = g_counters[i].load(std::memory_order_relaxed);
     return CNT_COUNT;
 }
+/* not in the public header: the host CRC-32C the Snappy writer hashes its chunks with (SSE4.2 where the CPU has it): what
+   tools/bench_framing_compress.py times next to the kernels */
+uint32_t alz_debug_host_crc32c(const uint8_t* p, size_t len) { return crc32c(p, len); }
 
 }  // extern "C"
 

@@ -2,6 +2,9 @@
 // alz_container.cpp (decode) and alz_container_measure.cpp (sizes) turn what these two pull parsers return into GPU work, each with its own
 // scheduling.  Pure host code: no HIP, no call into the ABI, nothing allocated but the caller's block list -- so it runs on untrusted bytes under the
 // sanitizers (tests/framing_walk_check.cpp).  Cited per function, paths relative to the reference's src.  Not part of the ABI.
+// Behind the readers: the WRITERS' rules (frame descriptor, block words, end marks, Snappy chunk headers, the error mapping and the order
+// in which a file is laid out and judged against its capacity), written once for alz_container.cpp (one file, pieces copied on the host)
+// and alz_framing_compress.cpp (a batch, pieces copied in HBM).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -178,6 +181,106 @@ inline SnappyChunk snappy_read_chunk(const uint8_t* src, size_t len, size_t pos)
     else c.kind = SnappyChunk::SKIPPED;
     c.next = (uint64_t)pos + 4 + c.len > len ? len : pos + 4 + c.len;
     return c;
+}
+
+// ---------------------------------------------------------------------------------------------- the writers
+// A writer lays a file out as pieces in file order and hands each to a sink, which copies it (one file) or records it (a batch):
+//   sink.bytes(at, p, k)       k <= 8 bytes the writer made up: magic, descriptor, size word, chunk header, end mark
+//   sink.slot(at, i, k)        the first k bytes of block i's compressed output
+//   sink.source(at, off, k)    k raw bytes of the input from `off`: a stored block or chunk
+// `at` is the place in the file.  A writer that returns another code than ALZ_OK may have handed over pieces of the file in front of the
+// failure: the bytes of a failed file are unspecified.
+inline void wr_le32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+
+// the BD byte of a frame for the block size a caller asks for (0: the default, 4 MiB), or 0 for a size the format does not have  LZ4.Frame.cs:29-35
+inline uint8_t lz4_frame_bd(uint32_t option, uint32_t* block) {
+    switch (option) {
+    case 0: case 0x400000: *block = 0x400000; return 0x70;
+    case 0x10000: *block = 0x10000; return 0x40;
+    case 0x40000: *block = 0x40000; return 0x50;
+    case 0x100000: *block = 0x100000; return 0x60;
+    default: return 0;
+    }
+}
+// magic, FLG, BD, HC.  `Flags &= IsVersion1` (LZ4.Frame.cs:184) leaves only the version bit: no content size, no checksums, blocks flagged linked
+inline size_t lz4_frame_descriptor(uint8_t out[7], uint8_t bd) {
+    wr_le32(out, kLz4Frame); out[4] = 0x40; out[5] = bd; out[6] = (uint8_t)((xxh32(out + 4, 2, 0) >> 8) & 0xFF);
+    return 7;
+}
+inline uint32_t lz4_block_word(uint32_t len, bool stored) { return stored ? len | 0x80000000u : len; }
+const uint32_t kLz4EndMark = 0;                                                          // a frame ends with a block word of 0
+const uint8_t kLz4LegacyEof = 0xFF;                                                      // LZ4.cs:157
+const uint32_t kLz4LegacyBlock = 0x800000u;                                              // (int)BlockMaxSizes.Block4MB * 2
+const uint32_t kSnappyChunk = 0x10000u;                                                  // Snappy.cs:74
+// a block the encoder did not finish: only LZ4 tells a slot that was too small apart
+inline int lz4_block_error(int32_t status) { return status == ALZ_ST_OUTPUT_CAPACITY ? ALZ_E_NOMEM : ALZ_E_INVALID; }
+inline int snappy_block_error(int32_t) { return ALZ_E_INVALID; }
+
+inline uint32_t snappy_crc_mask(uint32_t crc) { return ((crc >> 15) | (crc << 17)) + 0xa282ead8u; }   // Snappy.cs:252
+// type, u24 length (the CRC counts), the masked CRC-32C of the chunk's RAW bytes; `crc` is the plain CRC-32C
+inline size_t snappy_chunk_header(uint8_t out[8], bool stored, uint32_t body, uint32_t crc) {
+    const uint32_t len = body + 4;
+    out[0] = stored ? 1 : 0; out[1] = (uint8_t)len; out[2] = (uint8_t)(len >> 8); out[3] = (uint8_t)(len >> 16);
+    wr_le32(out + 4, snappy_crc_mask(crc));
+    return 8;
+}
+// the slot of a block's compressed output in the encode batch of a writer
+inline size_t write_slot_bytes(size_t block) { return (block + block / 4 + 64 + 255) & ~(size_t)255; }
+
+// LZ4.Compress  LZ4.cs:113-160 (legacy) / CompressLZ4FrameHeader  LZ4.Frame.cs:176-229
+struct Lz4Writer { bool legacy; uint32_t block; uint8_t bd; };
+// what the writer refuses before it encodes anything; `option`: the frame's block size as the caller states it
+inline int lz4_write_open(bool legacy, uint32_t option, size_t n, size_t cap, Lz4Writer& w) {
+    w.legacy = legacy; w.block = kLz4LegacyBlock; w.bd = 0;
+    if (cap < 16) return ALZ_E_NOMEM;
+    if (!legacy && !(w.bd = lz4_frame_bd(option, &w.block))) return ALZ_E_INVALID;
+    if (n && n % w.block != 0 && n % w.block < 5) return ALZ_E_INVALID;                  // source.Slice(0, Length - 5) throws  LZ4.cs:208
+    return ALZ_OK;
+}
+// the file from the results `rs` of its blocks (block i: the bytes from i * w.block, at most w.block of them)
+template <class Sink>
+inline int lz4_write_blocks(const Lz4Writer& w, size_t n, const alz_result* rs, size_t cap, Sink& sink, size_t* file_len) {
+    uint8_t h[8]; size_t o = 0;
+    if (w.legacy) { wr_le32(h, kLz4Legacy); sink.bytes(0, h, 4); o = 4; }
+    else { o = lz4_frame_descriptor(h, w.bd); sink.bytes(0, h, o); }
+    const size_t nb = (n + w.block - 1) / w.block;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t bl = n - i * w.block < w.block ? n - i * w.block : w.block;
+        if (rs[i].status != ALZ_ST_OK) return lz4_block_error(rs[i].status);
+        const bool stored = !w.legacy && rs[i].dst_len >= w.block;                       // buffer.Position >= (int)BlockSize: stored
+        const size_t body = stored ? bl : rs[i].dst_len;
+        if (o + 4 + body > cap) return ALZ_E_NOMEM;
+        wr_le32(h, lz4_block_word((uint32_t)body, stored)); sink.bytes(o, h, 4);
+        if (stored) sink.source(o + 4, i * (size_t)w.block, body); else sink.slot(o + 4, i, body);
+        o += 4 + body;
+    }
+    if (w.legacy) { if (o + 1 > cap) return ALZ_E_NOMEM; h[0] = kLz4LegacyEof; sink.bytes(o, h, 1); o += 1; }
+    else { if (o + 4 > cap) return ALZ_E_NOMEM; wr_le32(h, kLz4EndMark); sink.bytes(o, h, 4); o += 4; }
+    *file_len = o;
+    return ALZ_OK;
+}
+
+// Snappy.Compress  Formats/Common/Snappy.cs:71-107
+inline int snappy_write_open(size_t cap) { return cap < 10 ? ALZ_E_NOMEM : ALZ_OK; }
+// crc(i): the plain CRC-32C of the raw bytes of chunk i
+template <class Sink, class Crc>
+inline int snappy_write_chunks(size_t n, const alz_result* rs, size_t cap, Sink& sink, Crc crc, size_t* file_len) {
+    sink.bytes(0, kSnappyId, 10);
+    uint8_t h[8]; size_t o = 10;
+    const size_t nb = (n + kSnappyChunk - 1) / kSnappyChunk;
+    for (size_t i = 0; i < nb; i++) {
+        const size_t cs = n - i * kSnappyChunk < kSnappyChunk ? n - i * kSnappyChunk : kSnappyChunk;
+        if (rs[i].status != ALZ_ST_OK) return snappy_block_error(rs[i].status);
+        const bool stored = rs[i].dst_len >= cs;                                         // buffer.Length >= chunkSize
+        const size_t body = stored ? cs : rs[i].dst_len;
+        snappy_chunk_header(h, stored, (uint32_t)body, crc(i));
+        if (o + 8 + body > cap) return ALZ_E_NOMEM;
+        sink.bytes(o, h, 8);
+        if (stored) sink.source(o + 8, i * (size_t)kSnappyChunk, body); else sink.slot(o + 8, i, body);
+        o += 8 + body;
+    }
+    *file_len = o;
+    return ALZ_OK;
 }
 
 }  // namespace alz_framing

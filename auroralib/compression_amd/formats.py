@@ -396,6 +396,32 @@ class _FramedMany:
         ctx = _context()
         return _decompress_many(files, self.container, limit, ctx.framed_measure_batch, ctx.framed_decode_batch, decode_decides=True)
 
+    def CompressMany(self, datas, settings=None):
+        """Compress for a whole set of inputs in ONE alz_framing_compress_batch: capacities from alz_container_compress_bound, an LZ4 frame's
+        block size from ChunkSize.  Returns a list with, per input, the file's bytes -- or the exception instance Compress would have raised."""
+        datas = [bytes(d) for d in datas]
+        s = settings or CompressionSettings.Balanced
+        lib = load()
+        lib.alz_container_compress_bound.restype = C.c_size_t
+        lib.alz_container_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
+        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
+        table, so, do = (A.Stream * len(datas))(), 0, 0
+        for i, d in enumerate(datas):
+            cap = lib.alz_container_compress_bound(self.container, len(d))
+            table[i] = A.Stream(so, do, len(d), cap, 0, self.ChunkSize, 0, self.container)
+            so += len(d)
+            do += cap
+        if not datas:
+            return []
+        dst, res = _context().framing_compress_batch(table, src, do, quality=s.Quality, strategy=s.Strategy, max_window_bits=s.MaxWindowBits)
+        out = []
+        for i, r in enumerate(res):
+            if r.rc != 0:
+                out.append(AlzError(r.rc, "alz_framing_compress_batch: file %d" % i))
+            else:
+                out.append(dst[int(table[i].dst_off):int(table[i].dst_off) + r.dst_len].tobytes())
+        return out
+
 
 class LZ4(_FramedMany, _Format):
     """src/AuroraLib.Compression/Formats/Common/LZ4.cs + LZ4.Frame.cs: frame (default), legacy and skippable frames.

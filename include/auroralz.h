@@ -568,8 +568,8 @@ int alz_gzip_measure(alz_ctx* ctx, const uint8_t* src, size_t src_len, size_t si
  * alz_checksum_combine: the checksum of A || B from the checksum `a` of A, the checksum `b` of B and the length of B (zlib's
  *   adler32_combine / crc32_combine): pure host code, no context, the very arithmetic the second launch runs.  len_b == 0 returns a.
  *   An unknown kind returns 0.
- * NOT BUILT: CRC-32C (the checksum of the Snappy container, which the reference does not verify), and a checksum fused into a decode
- *   kernel's write-back.  XXH32, the checksum of the LZ4 frame format, has entry points of its own below (alz_xxh32_batch*). */
+ * NOT BUILT: a checksum fused into a decode kernel's write-back.  CRC-32C, the checksum of the Snappy container, and XXH32, the checksum
+ *   of the LZ4 frame format, have entry points of their own below (alz_crc32c_batch*, alz_xxh32_batch*). */
 typedef enum alz_checksum_kind { ALZ_CK_ADLER32 = 0, ALZ_CK_CRC32 = 1 } alz_checksum_kind;
 int alz_checksum_batch(alz_ctx* ctx, uint32_t kind, uint32_t n, const uint8_t* src_base, size_t src_bytes,
                        const alz_stream* ranges, uint32_t* out);
@@ -577,6 +577,22 @@ int alz_checksum_batch(alz_ctx* ctx, uint32_t kind, uint32_t n, const uint8_t* s
 int alz_checksum_batch_device(alz_ctx* ctx, uint32_t kind, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
                               const alz_stream* ranges, uint32_t* out);
 uint32_t alz_checksum_combine(uint32_t kind, uint32_t a, uint32_t b, uint64_t len_b);
+
+/* ---------------------------------------- CRC-32C of byte ranges on the GPU
+ * out[i] is the CRC-32C (Castagnoli: polynomial 0x82F63B78 reflected, start value and final inversion 0xFFFFFFFF; "123456789" gives
+ * 0xE3069283) of the n ranges[i]: the checksum a framed Snappy file carries per chunk, BEFORE Snappy's mask (CRC32c.cs, Snappy.cs:252).
+ * It is not a kind of alz_checksum_batch (whose kinds end at ALZ_CK_CRC32) but the same two launches over the other polynomial, and
+ * everything said there holds: a range is src_off / src_len of its alz_stream, every other field is ignored; ranges may overlap, be
+ * empty (0) and start at any byte; aligned 16-byte granules that each hold a byte of a range, so the 64-byte slack rule covers the
+ * reads; one wavefront per 32 KiB chunk, one fold wavefront per range; alz_last_kernel_ms reports the device time of the two launches;
+ * n == 0 is ALZ_OK; a NULL ctx, a range outside src_bytes, or NULL ranges / out with n > 0 are ALZ_E_INVALID; more than 2^31 chunks
+ * are ALZ_E_UNSUPPORTED.  alz_crc32c_combine: the CRC-32C of A || B from those of A and B and the length of B; pure host code, the
+ * arithmetic of the second launch; len_b == 0 returns a.  MI355X (docs/EXPERIMENTS.md 19): 10 000 ranges of 64 KiB at 952 GB/s, one
+ * range of 64 MiB at 306 GB/s (one host thread with the SSE4.2 instruction: 10 - 13 GB/s). */
+int alz_crc32c_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out);
+/* d_src_base is a DEVICE pointer; out is on the host */
+int alz_crc32c_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out);
+uint32_t alz_crc32c_combine(uint32_t a, uint32_t b, uint64_t len_b);
 
 /* ---------------------------------------- ZLib and GZip files in batches
  * What alz_zlib_decompress / alz_gzip_decompress (and their _measure twins) do for one file, for n files in one call.  files[i].format is
@@ -647,12 +663,41 @@ int alz_xxh32_batch_device(alz_ctx* ctx, uint32_t seed, uint32_t n, const uint8_
  * alz_xxh32_batch_device; the outputs are downloaded once.  alz_framed_measure_batch is the same walk without the decode, with content
  * checksums taken as correct and the declared content size checked.  MI355X (docs/EXPERIMENTS.md 18): 2 000 files of 64 KiB in one
  * call take 30 ms (LZ4 frames with content checksums) and 27 ms (Snappy), 11.7 and 10.4 times less than a loop of the single-file call.
- * NOT BUILT: device-resident forms, batched compression, CRC-32C.  The single-file entry points are unchanged, host-side XXH32 included:
- *   they are the yardstick. */
+ * NOT BUILT: device-resident forms, a second XXH32 layout for few long ranges, checksums fused into the kernels.  The single-file entry
+ *   points are unchanged, host-side XXH32 included: they are the yardstick.  The write direction is alz_framing_compress_batch below. */
 int alz_framed_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
                             uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
 int alz_framed_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
                              alz_file_result* results);
+
+/* ---------------------------------------- LZ4 and Snappy files WRITTEN in batches
+ * What alz_container_compress does for one file of ALZ_C_LZ4_FRAME, ALZ_C_LZ4_LEGACY or ALZ_C_SNAPPY, for n files in one call.
+ * files[i].format is one of these three alz_container values -- a batch may mix them, any other value makes the call ALZ_E_INVALID;
+ * src_off / src_len is the raw input; dst_off / dst_cap is where the file goes; aux0 is the block size of an LZ4 frame (0, 0x10000,
+ * 0x40000, 0x100000 or 0x400000: what alz_container_options.chunk_size is for the single-file call; the other two containers ignore it);
+ * decom_len and aux1 are IGNORED.  One `settings` applies to the whole call; NULL is quality 8.  All buffers are in host memory.
+ * THE CONTRACT IS DIFFERENTIAL, against alz_container_compress on file i alone with the same context, settings, block size and capacity:
+ *   that call returns ALZ_OK:  results[i] is { ALZ_OK, ALZ_ST_OK, dst_len, src_len } and the dst_len bytes at dst_off are the bytes it writes.
+ *   it returns another code:   results[i] is { that code, ALZ_ST_OK, 0, 0 } and the bytes of the slot are unspecified -- ALZ_E_NOMEM for
+ *     a slot that is too small (also below the writers' floors: 16 bytes for LZ4, 10 for Snappy), ALZ_E_INVALID for an LZ4 input whose
+ *     last block would hold 1 to 4 bytes (LZ4.cs:208 throws) and for an aux0 the frame format does not have.
+ * Nothing outside a file's [dst_off, dst_off + dst_cap) is written on the host; one file's failure never changes another file's result.
+ * The call itself fails only for bad arguments (a NULL ctx; n > 0 with NULL pointers; a range outside src_bytes / dst_bytes; settings
+ * the encoder refuses) or a HIP error.  n == 0 is ALZ_OK.
+ * One batch: the host lays out every block of every file the writer does not refuse beforehand (64 KiB chunks for Snappy, aux0 for
+ * frames, 8 MiB for legacy); the source is uploaded once; all blocks of all files are ONE alz_encode_batch_device (LZ4 blocks and raw
+ * Snappy chunks mix: one launch sequence per format), each into a slot of the size the single-file writer gives it; the raw bytes of
+ * all Snappy chunks are hashed where they lie by ONE alz_crc32c_batch_device; the writers of the single-file layer (csrc/alz_framing.h)
+ * then settle per file what is stored and what compressed, the size words and masked CRCs, the length and the verdict against dst_cap;
+ * the file images are assembled in HBM by ONE range copy out of slots, source and a small uploaded table of header bytes, and
+ * downloaded once.  A batch whose source plus slots exceed 2 GiB runs as consecutive groups of whole files (a larger file alone); the
+ * results do not depend on the grouping.  A small legacy file or default-size frame still occupies the slot of a full block.
+ * MI355X (docs/EXPERIMENTS.md 19): 2 000 inputs of 64 KiB in one call take 29 - 44 ms (LZ4 frames and Snappy, quality 0 and 8), 9.5 to
+ * 16 times less than a loop of the single-file call; most of what is left is the download of the slots.
+ * NOT BUILT: device-resident forms, frames with checksums or a content size (the reference's writer clears those flags,
+ *   LZ4.Frame.cs:184), linked blocks.  The single-file entry point is unchanged, host-side CRC-32C included: it is the yardstick. */
+int alz_framing_compress_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                               const alz_stream* files, uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
 
 /* -------------------------------------------- decode: device-resident batches
  * The measured path: payload already in HBM, output left in HBM.  The kernels never WRITE outside a stream's

@@ -204,6 +204,19 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_framed_measure_batch(IntPtr ctx, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* files, AlzFileResult* results);
 
+        // CRC-32C (Castagnoli; a framed Snappy chunk's checksum before its mask) of byte ranges on the GPU: the argument rules of
+        // alz_checksum_batch without a kind, and the join of two neighbouring pieces on the host
+        [DllImport(Lib)] internal static extern int alz_crc32c_batch(IntPtr ctx, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* ranges, uint* sums);
+        [DllImport(Lib)] internal static extern int alz_crc32c_batch_device(IntPtr ctx, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* ranges, uint* sums);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern uint alz_crc32c_combine(uint a, uint b, ulong lenB);
+        // LZ4 (frame 22, legacy 7) / framed Snappy (9) files WRITTEN in batches: the multi-block containers BatchEncoder.CompressMany cannot
+        // serve body by body.  AlzStream.Format is the alz_container value, Aux0 an LZ4 frame's block size; per file what
+        // alz_container_compress writes and returns for it alone
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_framing_compress_batch(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
+
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
             byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
