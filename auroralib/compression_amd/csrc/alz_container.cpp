@@ -13,6 +13,7 @@
 #include <cstring>
 #include <vector>
 
+#include "alz_file_batch.h"
 #include "alz_framing.h"
 #include "auroralz.h"
 
@@ -24,7 +25,11 @@
 
 namespace {
 
-using namespace alz_framing;   // le32, clamp32, xxh32, the LZ4 / Snappy framing readers
+using namespace alz_framing;   // le32, clamp32, xxh32, the LZ4 / Snappy framing readers and what their records make of a file
+// (of alz_file_batch.h only what calls the part of the ABI that tests/fuzz_container.cpp has stand-ins for)
+using alz_file_batch::DeviceBuffer;
+using alz_file_batch::run_plan;
+using alz_file_batch::run_long_and_short;
 
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 inline uint32_t rd32(const uint8_t* p, bool big) { return big ? be32(p) : le32(p); }
@@ -167,12 +172,6 @@ enum { CNT_BATCH_BLOCKS, CNT_SPLIT_PLANS, CNT_TIGHT_RETRIES, CNT_FALLBACK_BLOCKS
 std::atomic<uint64_t> g_counters[CNT_COUNT];
 inline void count(int which, uint64_t n = 1) { g_counters[which].fetch_add(n, std::memory_order_relaxed); }
 
-struct DevBuf {   // device allocation released on every exit path
-    alz_ctx* c; void* p;
-    explicit DevBuf(alz_ctx* ctx) : c(ctx), p(nullptr) {}
-    ~DevBuf() { if (p) alz_device_free(c, p); }
-};
-
 // A block's destination as the whole-GPU decode path of ONE stream wants it (alz_big_eligible: no more than 32 x the input + 64 KiB -- its launches are sized by the room in the
 // destination): the frame's block maximum is 4 MiB whatever the block holds, and a 1 MB file in one block had 33 x its 126 KB of input to decode into -- 3.7 ms on two wavefronts
 // instead of 0.28.  A block that does not fit the tighter room (it compressed better than 32 : 1) reports OUTPUT_CAPACITY and is decoded again with all of it.
@@ -180,8 +179,6 @@ inline uint32_t lz4_tight_cap(uint32_t cap, uint32_t src_len) {
     const uint64_t t = 32ull * src_len + 65536ull;
     return t < cap ? (uint32_t)t : cap;
 }
-// (worth the whole GPU by itself: plan_create's own test, restated for the split below -- a wrong guess costs time, not bytes)
-inline bool lz4_long_block(const alz_stream& s) { return s.src_len >= 8192u && s.dst_cap >= (24u << 10); }
 
 // LZ4.Decompress  Formats/Common/LZ4.cs:50-93 (+ ReadLZ4L :96-111, DecompressLZ4FrameHeader  LZ4.Frame.cs:107-174).
 // The file and the output stay in HBM for the whole call.  Blocks that cannot reference each other (legacy frames:
@@ -189,23 +186,13 @@ inline bool lz4_long_block(const alz_stream& s) { return s.src_len >= 8192u && s
 // nominal offsets; blocks of a linked frame share one window (LZ4.Frame.cs:120) and run in order, each with the
 // frame's earlier output as history (alz_stream.aux0).  Checksums are verified as with LZ4.HashAlgorithm = XXH32.
 int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* dst_len, size_t* src_used, int32_t* status) {
-    DevBuf d_src(ctx), d_dst(ctx);
+    DeviceBuffer d_src(ctx), d_dst(ctx);
     int rc;
-    if ((rc = alz_device_malloc(ctx, len + 64, &d_src.p)) != ALZ_OK) return rc;
-    if ((rc = alz_device_malloc(ctx, cap + 64, &d_dst.p)) != ALZ_OK) return rc;
+    if ((rc = d_src.alloc(len + 64)) != ALZ_OK) return rc;
+    if ((rc = d_dst.alloc(cap + 64)) != ALZ_OK) return rc;
     if (len && (rc = alz_memcpy_h2d(ctx, d_src.p, src, len)) != ALZ_OK) return rc;
     size_t pos = 0, out = 0; int32_t st = ALZ_ST_OK;
 
-    // runs `n` streams and returns their results
-    auto run = [&](std::vector<alz_stream>& ss, std::vector<alz_result>& rs) -> int {
-        alz_plan* pl = nullptr; rs.resize(ss.size());
-        int e = alz_plan_create(ctx, nullptr, (uint32_t)ss.size(), ss.data(), &pl);
-        if (e != ALZ_OK) return e;
-        e = alz_plan_execute(ctx, pl, d_src.p, d_dst.p, nullptr);
-        if (e == ALZ_OK) e = alz_plan_results(ctx, pl, rs.data());
-        alz_plan_destroy(ctx, pl);
-        return e;
-    };
     // blocks in order, each seeing `out - origin` bytes of history when `linked`; `fallback`: the rest of a batch that did not hold
     auto run_sequential = [&](const std::vector<Lz4Block>& bl, size_t first, size_t origin, bool linked, bool fallback) -> int {
         for (size_t i = first; i < bl.size() && st == ALZ_ST_OK; i++) {
@@ -227,10 +214,10 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
             ss[0].aux0 = (uint32_t)hist; ss[0].format = ALZ_FMT_LZ4_BLOCK;
             const uint32_t full = ss[0].dst_cap;
             if (!linked) ss[0].dst_cap = lz4_tight_cap(full, ss[0].src_len);
-            int e = run(ss, rs); if (e != ALZ_OK) return e;
+            int e = run_plan(ctx, ss, rs, d_src.p, d_dst.p); if (e != ALZ_OK) return e;
             if (rs[0].status == ALZ_ST_OUTPUT_CAPACITY && ss[0].dst_cap < full) {                                   // (a block that compressed more than 32 : 1)
                 count(CNT_TIGHT_RETRIES);
-                ss[0].dst_cap = full; e = run(ss, rs); if (e != ALZ_OK) return e;
+                ss[0].dst_cap = full; e = run_plan(ctx, ss, rs, d_src.p, d_dst.p); if (e != ALZ_OK) return e;
             }
             out += rs[0].dst_len;
             if (rs[0].status != ALZ_ST_OK) st = rs[0].status;
@@ -253,23 +240,11 @@ int lz4_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* d
             s.dst_cap = lz4_tight_cap(s.dst_cap, s.src_len);
             ss.push_back(s); idx.push_back(i);
         }
-        // A plan takes its streams one after the other on the whole GPU only when ALL of them are worth it (plan_create), and the last block of a file is usually a
-        // short one: 16 MB in 4 MiB blocks -- four of them and 2 KB -- decoded every block on wavefronts of its own, 14 ms for the 4 MiB ones instead of 0.5 each.
-        // The long blocks and the short ones go out as two plans.
-        std::vector<alz_result> rs(ss.size());
-        {
-            std::vector<alz_stream> sa, sb; std::vector<size_t> ia, ib;
-            for (size_t k = 0; k < ss.size(); k++) { if (lz4_long_block(ss[k])) { sa.push_back(ss[k]); ia.push_back(k); } else { sb.push_back(ss[k]); ib.push_back(k); } }
-            count(CNT_BATCH_BLOCKS, ss.size());
-            if (!sa.empty() && !sb.empty() && sa.size() <= 32) {
-                count(CNT_SPLIT_PLANS);
-                std::vector<alz_result> ra, rb;
-                int e = run(sa, ra); if (e != ALZ_OK) return e;
-                e = run(sb, rb); if (e != ALZ_OK) return e;
-                for (size_t k = 0; k < ia.size(); k++) rs[ia[k]] = ra[k];
-                for (size_t k = 0; k < ib.size(); k++) rs[ib[k]] = rb[k];
-            } else if (!ss.empty()) { int e = run(ss, rs); if (e != ALZ_OK) return e; }
-        }
+        // the long blocks and the short ones go out as two plans (alz_file_batch.h)
+        std::vector<alz_result> rs; bool split = false;
+        count(CNT_BATCH_BLOCKS, ss.size());
+        if (int e = run_long_and_short(ctx, ss, rs, d_src.p, d_dst.p, &split)) return e;
+        if (split) count(CNT_SPLIT_PLANS);
         size_t k = 0;
         for (size_t i = 0; i < bl.size(); i++) {
             const size_t o = origin + i * (size_t)nominal;
@@ -374,86 +349,47 @@ int lz4_file_compress(alz_ctx* ctx, bool legacy, uint32_t block_size, const alz_
     return ALZ_OK;
 }
 
+// the sink of the single-file Snappy decode (alz_framing.h): a stored chunk is copied into the caller's buffer as it is laid out
+struct HostStored {
+    uint8_t* dst; const uint8_t* src;
+    void stored(size_t off, uint64_t out, uint32_t n) { memcpy(dst + out, src + off, n); }
+};
+// an outcome into the out-parameters of a single-file call, which stay unset when the file is refused
+int deliver(const Outcome& o, size_t* dst_len, size_t* src_used, int32_t* status) {
+    if (o.rc != ALZ_OK && o.rc != ALZ_E_STREAM) return o.rc;
+    if (dst_len) *dst_len = (size_t)o.out;
+    if (src_used) *src_used = o.pos;
+    if (status) *status = o.status;
+    return o.rc;
+}
+
 // Snappy.Decompress  Formats/Common/Snappy.cs:39-69, chunk after chunk from `pos` with `out` bytes produced: the path of a file whose
-// chunk decodes to more than it declares (its last element runs past the size), which moves every later chunk.
+// chunk decodes to more than it declares (its last element runs past the size), which moves every later chunk.  The reader is
+// snappy_read_on (alz_framing.h); here each compressed chunk it stops at is decoded, through host buffers.
 int snappy_in_order(alz_ctx* ctx, const uint8_t* src, size_t len, size_t pos, size_t out, uint8_t* dst, size_t cap, size_t* dst_len, size_t* src_used, int32_t* status) {
-    int32_t st = ALZ_ST_OK;
-    while (pos < len) {
-        const SnappyChunk c = snappy_read_chunk(src, len, pos);
-        pos = c.body;
-        if (c.kind == SnappyChunk::TRUNCATED) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-        if (c.kind == SnappyChunk::RESERVED) return ALZ_E_FORMAT;
-        if (c.kind == SnappyChunk::COMPRESSED) {
-            alz_result r;
-            int rc = run_body(ctx, ALZ_FMT_SNAPPY_RAW, nullptr, src + pos, len - pos, 0, 0, 0, dst + out, out < cap ? cap - out : 0, &r);
-            if (rc != ALZ_OK) return rc;
-            out += r.dst_len;
-            if (r.status != ALZ_ST_OK) { st = r.status; break; }
-            if ((uint64_t)r.src_used + 4 != c.len) return ALZ_E_FORMAT;                  // (as below: a body that does not end at the declared length)
-            pos += r.src_used;
-        } else if (c.kind == SnappyChunk::STORED) {
-            if (out + c.stored > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
-            memcpy(dst + out, src + pos, c.stored); out += c.stored; pos = c.next;
-        } else pos = c.next;
+    SnappyReader r = { pos, out, 0 }; HostStored sink{dst, src}; Outcome o; alz_result got; bool have = false;
+    while (!snappy_read_on(src, len, cap, r, have ? &got : nullptr, sink, o)) {
+        const int rc = run_body(ctx, ALZ_FMT_SNAPPY_RAW, nullptr, src + r.pos, len - r.pos, 0, 0, 0, dst + r.out, r.out < cap ? cap - (size_t)r.out : 0, &got);
+        if (rc != ALZ_OK) return rc;
+        have = true;
     }
-    if (dst_len) *dst_len = out;
-    if (src_used) *src_used = pos;
-    if (status) *status = st;
-    return st == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM;
+    return deliver(o, dst_len, src_used, status);
 }
 
 // Snappy.Decompress  Formats/Common/Snappy.cs:39-69.  Every compressed chunk declares its size, so all chunks of a file
-// decode as ONE GPU batch; CRCs are skipped as in the reference.  The managed decoder continues wherever a chunk's body
-// stopped; here a chunk whose body does not end at its declared length is refused (ALZ_E_FORMAT).  Whatever fails first in
-// file order decides, as in the managed decoder.
+// decode as ONE GPU batch at their declared places (snappy_layout, alz_framing.h); CRCs are skipped as in the reference.  What the
+// results make of the file -- whatever fails first in file order decides, as in the managed decoder -- is snappy_judge.
 int snappy_file_decompress(alz_ctx* ctx, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* dst_len, size_t* src_used, int32_t* status) {
-    if (len < 10 || memcmp(src, kSnappyId, 10)) return ALZ_E_FORMAT;
-    size_t pos = 10; uint64_t out = 0; int32_t st = ALZ_ST_OK; bool reserved = false;
-    std::vector<alz_stream> ss; std::vector<uint32_t> clen; std::vector<size_t> chdr;
-    struct Raw { size_t off; uint32_t n; uint64_t out; }; std::vector<Raw> raws;
-    std::vector<bool> stored;                                                            // file order: stored (true) or compressed chunk
-    while (pos < len) {
-        const SnappyChunk c = snappy_read_chunk(src, len, pos);
-        pos = c.next;
-        if (c.kind == SnappyChunk::TRUNCATED) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-        if (c.kind == SnappyChunk::RESERVED) { reserved = true; break; }                 // E_FORMAT once reached
-        if (c.kind == SnappyChunk::COMPRESSED) {
-            const uint32_t size = snappy_varint(src + c.body, len - c.body, nullptr);
-            alz_stream s; memset(&s, 0, sizeof(s));
-            s.src_off = c.body; s.src_len = clamp32(len - c.body); s.dst_off = out < cap ? out : cap;
-            s.dst_cap = clamp32(out < cap ? (cap - out < size ? cap - out : size) : 0); s.format = ALZ_FMT_SNAPPY_RAW;
-            ss.push_back(s); clen.push_back(c.len); chdr.push_back(c.hdr); stored.push_back(false);
-            out += size;
-        } else if (c.kind == SnappyChunk::STORED) {
-            raws.push_back(Raw{ c.body, c.stored, out }); stored.push_back(true); out += c.stored;
-        }
-    }
+    if (!snappy_has_id(src, len)) return ALZ_E_FORMAT;
+    SnappyLayout w; HostStored sink{dst, src};
+    snappy_layout(src, len, cap, w, sink);
+    std::vector<alz_stream> ss;
+    for (const SnappyPiece& p : w.pieces) if (!p.stored) ss.push_back(body(ALZ_FMT_SNAPPY_RAW, p.off, len - p.off, p.at, p.cap, 0));
     std::vector<alz_result> rs(ss.size());
     if (!ss.empty()) { int rc = alz_decode_batch(ctx, nullptr, (uint32_t)ss.size(), src, len, ss.data(), dst, cap, rs.data()); if (rc != ALZ_OK) return rc; }
-    // the first failing chunk in file order, compressed or stored, decides status and length; stored chunks are copied up to it
-    size_t produced = (size_t)(out < cap ? out : cap); int32_t fst = ALZ_ST_OK;
-    for (size_t c = 0, i = 0, k = 0; c < stored.size() && fst == ALZ_ST_OK; c++) {
-        if (stored[c]) {
-            const Raw& r = raws[k++];
-            if (r.out + r.n > cap) { fst = ALZ_ST_OUTPUT_CAPACITY; produced = (size_t)r.out; break; }
-            memcpy(dst + r.out, src + r.off, r.n);
-            continue;
-        }
-        const uint32_t size = snappy_varint(src + ss[i].src_off, len - ss[i].src_off, nullptr);
-        int32_t cs = rs[i].status;
-        if (cs == ALZ_ST_OUTPUT_CAPACITY && ss[i].dst_cap == size && ss[i].dst_off + (uint64_t)size < cap)     // it decodes to more than it declares
-            return snappy_in_order(ctx, src, len, chdr[i], (size_t)ss[i].dst_off, dst, cap, dst_len, src_used, status);
-        if (cs == ALZ_ST_OK && rs[i].dst_len < size) cs = ALZ_ST_OUTPUT_CAPACITY;        // the declared size did not fit dst
-        if (cs == ALZ_ST_OK && (uint64_t)rs[i].src_used + 4 != clen[i]) return ALZ_E_FORMAT;
-        if (cs != ALZ_ST_OK) { fst = cs; produced = (size_t)(ss[i].dst_off + rs[i].dst_len); }
-        i++;
-    }
-    if (fst == ALZ_ST_OK && reserved) return ALZ_E_FORMAT;
-    if (fst == ALZ_ST_OK && st != ALZ_ST_OK) fst = st;
-    if (dst_len) *dst_len = produced;
-    if (src_used) *src_used = pos;
-    if (status) *status = fst;
-    return fst == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM;
+    SnappyReader r; Outcome o;
+    if (!snappy_judge(w, cap, [&](size_t k) -> const alz_result& { return rs[k]; }, r, o)) return snappy_in_order(ctx, src, len, r.pos, (size_t)r.out, dst, cap, dst_len, src_used, status);
+    return deliver(o, dst_len, src_used, status);
 }
 
 // Snappy.Compress  Formats/Common/Snappy.cs:71-107: the rules are snappy_write_open / snappy_write_chunks (alz_framing.h); the chunks are hashed here, on the host
@@ -1337,7 +1273,7 @@ const char* alz_brute_decoder_name(uint32_t i) { return i < ALZ_BRUTE_DECODERS ?
 
 int alz_brute_force(alz_ctx* ctx, const uint8_t* raw, size_t raw_len, uint32_t expected_size, uint8_t* dst, size_t slot, alz_result* results) {
     if (!ctx || (!raw && raw_len) || !dst || !results || slot < expected_size || raw_len > 0xFFFFFFFFull) return ALZ_E_INVALID;
-    DevBuf d_src(ctx), d_dst(ctx);
+    DeviceBuffer d_src(ctx), d_dst(ctx);
     int rc;
     const size_t dslot = (slot + 255) & ~(size_t)255;
     if ((rc = alz_device_malloc(ctx, raw_len + 64, &d_src.p)) != ALZ_OK) return rc;
@@ -1414,7 +1350,7 @@ int alz_container_scan(alz_ctx* ctx, const uint32_t* containers, uint32_t nc, co
         }
     }
     if (cands.empty()) return ALZ_OK;
-    DevBuf d_src(ctx), d_dst(ctx);
+    DeviceBuffer d_src(ctx), d_dst(ctx);
     int rc;
     if ((rc = alz_device_malloc(ctx, len + 64, &d_src.p)) != ALZ_OK) return rc;
     if ((rc = alz_memcpy_h2d(ctx, d_src.p, src, len)) != ALZ_OK) return rc;
@@ -1446,7 +1382,7 @@ int alz_container_scan(alz_ctx* ctx, const uint32_t* containers, uint32_t nc, co
             const Cand& c = cands[who[k]];
             if (c.off < next_free) continue;
             const uint8_t* d_out = (uint8_t*)d_dst.p + ss[k].dst_off;
-            DevBuf d_retry(ctx);
+            DeviceBuffer d_retry(ctx);
             if (rs[k].status != ALZ_ST_OK && !c.swapped && (c.container == ALZ_C_YAZ0 || c.container == ALZ_C_YAZ1)) {
                 // Yaz0.Decompress catches the failure and decodes again with the size field read in the other byte order
                 // (Yaz0.cs:66-78): one more single-stream decode for this candidate

@@ -1,9 +1,9 @@
 // alz_container_measure.cpp -- alz_container_measure: the decompressed size of a file of a container WITHOUT a size field (PRS, LZO, FastLZ, LZ4 frame /
 // legacy, framed Snappy) from its bodies measured on the GPU (alz_measure_batch).  The framing of the LZ4 and Snappy files is read by alz_framing.h, the
-// same code alz_container.cpp's decoders read it with; this file is a translation unit of its own because it calls into the batch half of the library,
-// which the header parsers of alz_container.cpp are built without (their sanitized fuzz binary).
+// same code alz_container.cpp's decoders read it with, and what the measured sizes make of a file is decided there too (lz4_replay,
+// snappy_measure_replay): here the bodies are sent out.  This file is a translation unit of its own because it calls into the batch half of the
+// library, which the header parsers of alz_container.cpp are built without (their sanitized fuzz binary).
 #include <cstdint>
-#include <cstring>
 #include <vector>
 
 #include "alz_framing.h"
@@ -15,109 +15,45 @@ namespace {
 using namespace alz_framing;
 
 // ---------------------------------------------------------------------------------------------- sizes without decoding (alz_container_measure)
-// A body measured with no bound on its count (alz_measure_batch, dst_cap = kNoBound) tells what it does in ANY destination: with `room` bytes left it
-// ends as measured when its bytes fit, and in OUTPUT_CAPACITY with the room used up otherwise (the first token that does not fit stops the decoder, in
-// front of any later error).  So the bodies of a file go out as ONE batch, and the in-order reader is replayed over the results on the host.
-const uint32_t kNoBound = 0xFFFFFF00u;
-inline alz_stream measured_body(uint32_t fmt, size_t off, size_t n) {
-    alz_stream s; memset(&s, 0, sizeof(s));
-    s.src_off = off; s.src_len = clamp32(n); s.dst_cap = kNoBound; s.format = fmt;
-    return s;
-}
-// advances `out` by what the body leaves in a destination of `cap` bytes; returns its status there
-inline int32_t place_body(const alz_result& m, uint64_t& out, uint64_t cap) {
-    const uint64_t room = out < cap ? cap - out : 0;
-    if (m.dst_len > room) { out += room; return ALZ_ST_OUTPUT_CAPACITY; }
-    out += m.dst_len;
-    return m.status;
-}
+// A body measured with no bound on its count tells what it does in ANY destination (place_body, alz_framing.h).  So the bodies of a file go out as
+// ONE batch, and the in-order reader is replayed over the results on the host.
+inline alz_stream measured_body(uint32_t fmt, size_t off, size_t n) { return body(fmt, off, n, 0, kNoBound, 0); }
 
-// LZ4.Decompress  Formats/Common/LZ4.cs:50-93 as the in-order reader sees the file, over measured block sizes.  The frames are read once (alz_framing.h:
-// where a block lies does not depend on what any block decodes to), their compressed blocks go out as ONE measure batch, and the reader is replayed over
-// the results: blocks in file order, then what the frame's read met behind them.  Blocks of a linked frame are measured like independent ones: history
-// only supplies bytes, never sizes.  The content checksum is taken as correct.
-int lz4_file_measure(alz_ctx* ctx, const uint8_t* src, size_t len, size_t cap, size_t* size_out, size_t* src_used, int32_t* status) {
-    std::vector<Lz4Frame> frames; std::vector<Lz4Block> blocks; std::vector<alz_stream> ss; std::vector<alz_result> rs;
-    size_t pos = 0; uint32_t magic = 0;
-    while (magic != 0 || pos < len) {
-        frames.emplace_back(); Lz4Frame& f = frames.back();
-        lz4_read_frame(src, len, pos, magic, f, blocks);
-        pos = f.end; magic = f.next_magic;
-        for (const Lz4Block* b = blocks.data() + f.first, *e = b + f.count; b != e; b++) if (!b->raw) ss.push_back(measured_body(ALZ_FMT_LZ4_BLOCK, b->off, b->len));
-        if (f.fault != ALZ_OK || f.truncated || f.ends_file) break;
-        if (f.flg & 4) { if (pos + 4 > len) break; pos += 4; }                               // content checksum: needs the bytes
-    }
+int measure(alz_ctx* ctx, const uint8_t* src, size_t len, std::vector<alz_stream>& ss, std::vector<alz_result>& rs) {
     rs.resize(ss.size());
-    if (!ss.empty()) { const int e = alz_measure_batch(ctx, nullptr, (uint32_t)ss.size(), src, len, ss.data(), rs.data()); if (e != ALZ_OK) return e; }
-    uint64_t out = 0; int32_t st = ALZ_ST_OK; int rc = ALZ_OK; size_t k = 0; pos = 0;
-    for (const Lz4Frame& f : frames) {
-        const uint64_t frame_start = out;
-        for (const Lz4Block* b = blocks.data() + f.first, *e = b + f.count; b != e; b++) {
-            if (!b->raw) st = place_body(rs[k++], out, cap);
-            else {                                                                           // what fits, as the window writes it
-                const uint64_t room = out < cap ? cap - out : 0;
-                if (b->len > room) { out += room; st = ALZ_ST_OUTPUT_CAPACITY; } else out += b->len;
-            }
-            if (st != ALZ_ST_OK) { pos = f.behind(*b); break; }
-        }
-        if (st != ALZ_ST_OK) break;
-        pos = f.end;
-        if ((rc = f.fault) != ALZ_OK) break;
-        if (f.truncated) { st = ALZ_ST_INPUT_TRUNCATED; break; }
-        if ((f.flg & 8) && out - frame_start != f.content) { st = ALZ_ST_OUTPUT_SIZE_MISMATCH; break; }   // LZ4.Frame.cs:152-155
-        if (f.flg & 4) { if (pos + 4 > len) { st = ALZ_ST_INPUT_TRUNCATED; break; } pos += 4; }
-    }
-    if (size_out) *size_out = (size_t)out;
-    if (src_used) *src_used = pos;
-    if (status) *status = st;
-    if (rc != ALZ_OK) return rc;
-    return st == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM;
+    return ss.empty() ? ALZ_OK : alz_measure_batch(ctx, nullptr, (uint32_t)ss.size(), src, len, ss.data(), rs.data());
 }
 
-// Snappy.Decompress  Formats/Common/Snappy.cs:39-69 over measured chunk sizes.  The managed reader continues wherever a chunk's body stopped, so where
-// the next chunk lies depends on the chunk before it; nearly always that is where the chunk's declared length says.  The chunks are collected on that
-// assumption and measured as one batch (a body is given the rest of the file, as the reader gives it: it stops at its declared size by itself); the
-// replay follows the measured src_used, and where it leaves the assumed positions the rest of the file is collected again from there.
+// LZ4.Decompress  Formats/Common/LZ4.cs:50-93 as the in-order reader sees the file, over measured block sizes: the frames are read once, their
+// compressed blocks go out as ONE measure batch, and the reader is replayed over the results.  The content checksum is taken as correct.
+int lz4_file_measure(alz_ctx* ctx, const uint8_t* src, size_t len, size_t cap, size_t* size_out, size_t* src_used, int32_t* status) {
+    Lz4File w; std::vector<alz_stream> ss; std::vector<alz_result> rs;
+    lz4_collect(src, len, w, [&](const Lz4Block& b) { ss.push_back(measured_body(ALZ_FMT_LZ4_BLOCK, b.off, b.len)); });
+    if (const int e = measure(ctx, src, len, ss, rs)) return e;
+    Lz4Sizes sizes;
+    const Outcome o = lz4_replay(w, len, cap, rs.data(), sizes);
+    if (size_out) *size_out = (size_t)o.out;
+    if (src_used) *src_used = o.pos;
+    if (status) *status = o.status;
+    return o.rc;
+}
+
+// Snappy.Decompress  Formats/Common/Snappy.cs:39-69 over measured chunk sizes: collected at the declared places, measured as one batch, replayed; where
+// the replay leaves the assumed positions the rest of the file is collected again from there.
 int snappy_file_measure(alz_ctx* ctx, const uint8_t* src, size_t len, size_t cap, size_t* size_out, size_t* src_used, int32_t* status) {
-    if (len < 10 || memcmp(src, kSnappyId, 10)) return ALZ_E_FORMAT;
-    size_t pos = 10; uint64_t out = 0; int32_t st = ALZ_ST_OK;
+    if (!snappy_has_id(src, len)) return ALZ_E_FORMAT;
+    SnappyReader r = { 10, 0, 0 }; Outcome o;
     std::vector<alz_stream> ss; std::vector<alz_result> rs;
-    for (bool more = true; more;) {
-        more = false;
+    do {
         ss.clear();
-        for (size_t q = pos; q < len;) {
-            const SnappyChunk c = snappy_read_chunk(src, len, q);
-            if (c.kind == SnappyChunk::TRUNCATED || c.kind == SnappyChunk::RESERVED) break;
-            if (c.kind == SnappyChunk::COMPRESSED) ss.push_back(measured_body(ALZ_FMT_SNAPPY_RAW, c.body, len - c.body));
-            q = c.next;
-        }
-        rs.resize(ss.size());
-        if (!ss.empty()) { const int e = alz_measure_batch(ctx, nullptr, (uint32_t)ss.size(), src, len, ss.data(), rs.data()); if (e != ALZ_OK) return e; }
-        size_t k = 0;
-        while (pos < len) {
-            const SnappyChunk c = snappy_read_chunk(src, len, pos);
-            if (c.kind == SnappyChunk::TRUNCATED) { pos = c.next; st = ALZ_ST_INPUT_TRUNCATED; break; }
-            if (c.kind == SnappyChunk::RESERVED) return ALZ_E_FORMAT;
-            if (c.kind == SnappyChunk::COMPRESSED) {
-                if (k >= ss.size() || ss[k].src_off != c.body) {                             // the chunk before ended elsewhere than it declared
-                    if (k == 0) return ALZ_E_INVALID;                                        // (cannot happen: the first chunk is where the collection started)
-                    more = true; break;
-                }
-                const alz_result& m = rs[k++];
-                const int32_t cs = place_body(m, out, cap);
-                pos = c.body + m.src_used;
-                if (cs != ALZ_ST_OK) { st = cs; break; }
-            } else if (c.kind == SnappyChunk::STORED) {
-                pos = c.body;
-                if (out + c.stored > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
-                out += c.stored; pos = c.next;
-            } else pos = c.next;
-        }
-    }
-    if (size_out) *size_out = (size_t)out;
-    if (src_used) *src_used = pos;
-    if (status) *status = st;
-    return st == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM;
+        snappy_measure_collect(src, len, r.pos, [&](size_t off) { ss.push_back(measured_body(ALZ_FMT_SNAPPY_RAW, off, len - off)); });
+        if (const int e = measure(ctx, src, len, ss, rs)) return e;
+    } while (!snappy_measure_replay(src, len, cap, r, 0, ss.data(), ss.size(), rs.data(), o));
+    if (o.rc != ALZ_OK && o.rc != ALZ_E_STREAM) return o.rc;
+    if (size_out) *size_out = (size_t)o.out;
+    if (src_used) *src_used = o.pos;
+    if (status) *status = o.status;
+    return o.rc;
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
-// alz_file_batch.h -- what the batched file layers (alz_zfile.cpp: ZLib / GZip; alz_framed_batch.cpp: LZ4 / Snappy) share: a device buffer
-// that is freed on every exit path, the range test of their argument checks, and the one download of all outputs.  Pure host code on the
-// public ABI; not part of it.
+// alz_file_batch.h -- what the file layers share.  The batched ones (alz_zfile.cpp: ZLib / GZip; alz_framed_batch.cpp and
+// alz_framing_compress.cpp: LZ4 / Snappy): their argument check and the one download of all outputs.  Those and the single-file layer
+// (alz_container.cpp): a device buffer that is freed on every exit path, the plan runner, and the split of a set of streams into long
+// blocks and short ones.  Pure host code on the public ABI; not part of it.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -18,6 +19,49 @@ struct DeviceBuffer {                                                           
 };
 
 inline bool range_ok(uint64_t off, uint64_t len, uint64_t total) { return off <= total && len <= total - off; }
+
+// the argument check of a batched file call: accepts(format) names the files it reads; has_dst: the call writes outputs
+template <class Accepts>
+inline int check_files(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files, const uint8_t* dst_base, size_t dst_bytes,
+                       const alz_file_result* results, bool has_dst, Accepts accepts) {
+    if (!ctx || (n && (!files || !results)) || (src_bytes && !src_base) || (has_dst && dst_bytes && !dst_base)) return ALZ_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!accepts(files[i].format)) return ALZ_E_INVALID;
+        if (!range_ok(files[i].src_off, files[i].src_len, src_bytes)) return ALZ_E_INVALID;
+        if (has_dst && !range_ok(files[i].dst_off, files[i].dst_cap, dst_bytes)) return ALZ_E_INVALID;
+    }
+    return ALZ_OK;
+}
+
+// runs the streams `ss` as one plan, device-resident, and returns their results
+inline int run_plan(alz_ctx* ctx, std::vector<alz_stream>& ss, std::vector<alz_result>& rs, const void* d_src, void* d_dst) {
+    alz_plan* pl = nullptr; rs.resize(ss.size());
+    int e = alz_plan_create(ctx, nullptr, (uint32_t)ss.size(), ss.data(), &pl);
+    if (e != ALZ_OK) return e;
+    e = alz_plan_execute(ctx, pl, d_src, d_dst, nullptr);
+    if (e == ALZ_OK) e = alz_plan_results(ctx, pl, rs.data());
+    alz_plan_destroy(ctx, pl);
+    return e;
+}
+// (worth the whole GPU by itself: plan_create's own test, restated for the split below -- a wrong guess costs time, not bytes)
+inline bool long_block(const alz_stream& s) { return s.format == ALZ_FMT_LZ4_BLOCK && s.src_len >= 8192u && s.dst_cap >= (24u << 10); }
+// A plan takes its streams one after the other on the whole GPU only when ALL of them are worth it (plan_create), and the last block of a
+// file is usually a short one: 16 MB in 4 MiB blocks -- four of them and 2 KB -- decoded every block on wavefronts of its own, 14 ms for
+// the 4 MiB ones instead of 0.5 each.  So the long blocks and the short ones go out as two plans, unless there are more than 32 long ones;
+// `rs` in the order of `ss`, *split: whether two plans ran.
+inline int run_long_and_short(alz_ctx* ctx, std::vector<alz_stream>& ss, std::vector<alz_result>& rs, const void* d_src, void* d_dst, bool* split) {
+    std::vector<alz_stream> sa, sb; std::vector<size_t> ia, ib;
+    for (size_t k = 0; k < ss.size(); k++) { if (long_block(ss[k])) { sa.push_back(ss[k]); ia.push_back(k); } else { sb.push_back(ss[k]); ib.push_back(k); } }
+    *split = !sa.empty() && !sb.empty() && sa.size() <= 32;
+    rs.resize(ss.size());
+    if (!*split) return ss.empty() ? ALZ_OK : run_plan(ctx, ss, rs, d_src, d_dst);
+    std::vector<alz_result> ra, rb;
+    if (int e = run_plan(ctx, sa, ra, d_src, d_dst)) return e;
+    if (int e = run_plan(ctx, sb, rb, d_src, d_dst)) return e;
+    for (size_t k = 0; k < ia.size(); k++) rs[ia[k]] = ra[k];
+    for (size_t k = 0; k < ib.size(); k++) rs[ib[k]] = rb[k];
+    return ALZ_OK;
+}
 
 // the produced bytes of every file, device -> host: neighbouring outputs travel as one copy (through a bounce buffer, so that nothing
 // between two outputs is written on the host)

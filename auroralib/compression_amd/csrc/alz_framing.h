@@ -2,7 +2,9 @@
 // alz_container.cpp (decode) and alz_container_measure.cpp (sizes) turn what these two pull parsers return into GPU work, each with its own
 // scheduling.  Pure host code: no HIP, no call into the ABI, nothing allocated but the caller's block list -- so it runs on untrusted bytes under the
 // sanitizers (tests/framing_walk_check.cpp).  Cited per function, paths relative to the reference's src.  Not part of the ABI.
-// Behind the readers: the WRITERS' rules (frame descriptor, block words, end marks, Snappy chunk headers, the error mapping and the order
+// Behind the readers: what their records and the results of the bodies make of a file (rc, status, length, how far it was read), written once
+// for the single-file measure and Snappy decode and for the batched measure and decode of alz_framed_batch.cpp (tests/framing_replay_check.cpp).
+// Behind those: the WRITERS' rules (frame descriptor, block words, end marks, Snappy chunk headers, the error mapping and the order
 // in which a file is laid out and judged against its capacity), written once for alz_container.cpp (one file, pieces copied on the host)
 // and alz_framing_compress.cpp (a batch, pieces copied in HBM).
 #pragma once
@@ -181,6 +183,220 @@ inline SnappyChunk snappy_read_chunk(const uint8_t* src, size_t len, size_t pos)
     else c.kind = SnappyChunk::SKIPPED;
     c.next = (uint64_t)pos + 4 + c.len > len ? len : pos + 4 + c.len;
     return c;
+}
+
+inline bool snappy_has_id(const uint8_t* src, size_t len) { return len >= 10 && std::equal(kSnappyId, kSnappyId + 10, src); }
+
+// ---------------------------------------------------------------------------------------------- from records and results to a file's outcome
+// What the readers' records and the results of the bodies make of a file -- rc, status, length, how far it was read -- written once for the
+// four layers that read such files: the single-file measure (alz_container_measure.cpp) and Snappy decode (alz_container.cpp), the batch
+// measure and the batch decode (alz_framed_batch.cpp).  Those keep how bodies reach the GPU and how bytes move; a layer that moves bytes
+// hands in a sink or a visitor.  tests/framing_replay_check.cpp runs these functions on results from the CPU oracle.
+const uint32_t kNoBound = 0xFFFFFF00u;                                                   // the largest dst_cap of a stream
+inline alz_stream body(uint32_t fmt, uint64_t src_off, size_t src_len, uint64_t dst_off, uint32_t dst_cap, uint32_t hist) {
+    alz_stream s = {};
+    s.src_off = src_off; s.src_len = clamp32(src_len); s.dst_off = dst_off; s.dst_cap = dst_cap; s.aux0 = hist; s.format = fmt;
+    return s;
+}
+// A body measured with no bound on its count (dst_cap = kNoBound) tells what it does in ANY destination: with `room` bytes left it ends as
+// measured when its bytes fit, and in OUTPUT_CAPACITY with the room used up otherwise (the first token that does not fit stops the decoder,
+// in front of any later error).  Advances `out` by what the body leaves in a destination of `cap` bytes; returns its status there.
+inline int32_t place_body(const alz_result& m, uint64_t& out, uint64_t cap) {
+    const uint64_t room = out < cap ? cap - out : 0;
+    if (m.dst_len > room) { out += room; return ALZ_ST_OUTPUT_CAPACITY; }
+    out += m.dst_len;
+    return m.status;
+}
+
+// rc is ALZ_OK, ALZ_E_STREAM (then `status` tells why) or the code that refuses the file; out: bytes delivered; pos: how far the file was read
+struct Outcome { int rc; int32_t status; uint64_t out; size_t pos; };
+inline Outcome stream_outcome(int32_t status, uint64_t out, size_t pos) { return Outcome{ status == ALZ_ST_OK ? ALZ_OK : ALZ_E_STREAM, status, out, pos }; }
+inline Outcome refused(int rc) { return Outcome{ rc, ALZ_ST_OK, 0, 0 }; }
+
+// ---- LZ4
+struct Lz4File { std::vector<Lz4Frame> frames; std::vector<Lz4Block> blocks; };
+
+// LZ4.Decompress  Formats/Common/LZ4.cs:50-93: the frames of the file (where a block lies does not depend on what any block decodes to).
+// measure(b): every compressed block, in file order -- the caller appends the body it is measured as.
+template <class Measure>
+inline void lz4_collect(const uint8_t* src, size_t len, Lz4File& w, Measure measure) {
+    size_t pos = 0; uint32_t magic = 0;
+    while (magic != 0 || pos < len) {
+        w.frames.emplace_back(); Lz4Frame& f = w.frames.back();
+        lz4_read_frame(src, len, pos, magic, f, w.blocks);
+        pos = f.end; magic = f.next_magic;
+        for (const Lz4Block* b = w.blocks.data() + f.first, *e = b + f.count; b != e; b++) if (!b->raw) measure(*b);
+        if (f.fault != ALZ_OK || f.truncated || f.ends_file) break;
+        if (f.flg & 4) { if (pos + 4 > len) break; pos += 4; }                           // content checksum: needs the bytes
+    }
+}
+
+// What a size query hands to lz4_replay.  A decoder's visitor does its work in the same three places:
+struct Lz4Sizes {
+    // every block in file order with the output in front of it, the room behind that and (compressed blocks) its measured result; another
+    // code than ALZ_OK refuses the file
+    int block(const Lz4Frame&, const Lz4Block&, uint64_t /*frame_start*/, uint64_t /*out*/, uint64_t /*room*/, const alz_result*) { return ALZ_OK; }
+    // a block ended the file short: where the read stands (a decoder has read the whole frame by then)
+    size_t stopped(const Lz4Frame& f, const Lz4Block& b) { return f.behind(b); }
+    // a frame that ended well carries a content checksum word at `pos` over out - frame_start bytes: taken as correct here
+    void content_checksum(uint64_t /*frame_start*/, uint64_t /*out*/, size_t /*pos*/) {}
+};
+
+// The in-order reader over the measured sizes `m` (one per compressed block, file order; blocks of a linked frame are measured like
+// independent ones: history only supplies bytes, never sizes).  The verdicts in the order Lz4Frame states: blocks in file order, then what
+// the frame's read met behind them.
+template <class Visitor>
+inline Outcome lz4_replay(const Lz4File& w, size_t len, uint64_t cap, const alz_result* m, Visitor& v) {
+    uint64_t out = 0; size_t pos = 0;
+    for (const Lz4Frame& f : w.frames) {
+        const uint64_t frame_start = out;
+        for (const Lz4Block* b = w.blocks.data() + f.first, *e = b + f.count; b != e; b++) {
+            const uint64_t room = cap - out;
+            const alz_result* mb = b->raw ? nullptr : m++;
+            if (const int rc = v.block(f, *b, frame_start, out, room, mb)) return refused(rc);
+            int32_t st = ALZ_ST_OK;
+            if (mb) st = place_body(*mb, out, cap);
+            else if (b->len > room) { out += room; st = ALZ_ST_OUTPUT_CAPACITY; }        // what fits, as the window writes it
+            else out += b->len;
+            if (st != ALZ_ST_OK) return stream_outcome(st, out, v.stopped(f, *b));
+        }
+        pos = f.end;
+        if (f.fault != ALZ_OK) return Outcome{ f.fault, ALZ_ST_OK, out, pos };
+        if (f.truncated) return stream_outcome(ALZ_ST_INPUT_TRUNCATED, out, pos);
+        if ((f.flg & 8) && out - frame_start != f.content) return stream_outcome(ALZ_ST_OUTPUT_SIZE_MISMATCH, out, pos);   // LZ4.Frame.cs:152-155
+        if (f.flg & 4) {
+            if (pos + 4 > len) return stream_outcome(ALZ_ST_INPUT_TRUNCATED, out, pos);
+            v.content_checksum(frame_start, out, pos);
+            pos += 4;
+        }
+    }
+    return stream_outcome(ALZ_ST_OK, out, pos);
+}
+
+// ---- Snappy
+struct SnappyReader { size_t pos; uint64_t out; uint32_t clen; };                        // the in-order reader: where it stands, what it has produced; clen: the declared length of the chunk that is out
+
+// Snappy.Decompress  Formats/Common/Snappy.cs:39-69 over measured chunk sizes.  The managed reader continues wherever a chunk's body stopped, so
+// where the next chunk lies depends on the chunk before it; nearly always that is where the chunk's declared length says.  The chunks are
+// collected on that assumption (measure(body offset): a body is given the rest of the file, as the reader gives it -- it stops at its declared
+// size by itself) ...
+template <class Measure>
+inline void snappy_measure_collect(const uint8_t* src, size_t len, size_t pos, Measure measure) {
+    while (pos < len) {
+        const SnappyChunk c = snappy_read_chunk(src, len, pos);
+        if (c.kind == SnappyChunk::TRUNCATED || c.kind == SnappyChunk::RESERVED) break;
+        if (c.kind == SnappyChunk::COMPRESSED) measure(c.body);
+        pos = c.next;
+    }
+}
+// ... and the reader is replayed over the results `rs` of the `n` bodies `ss` (file_off: where the file lies in their source): it follows
+// the measured src_used.  True: the outcome is in `o`.  False: it has left the assumed places -- collect again from r.pos.
+inline bool snappy_measure_replay(const uint8_t* src, size_t len, uint64_t cap, SnappyReader& r, uint64_t file_off, const alz_stream* ss, size_t n,
+                                  const alz_result* rs, Outcome& o) {
+    int32_t st = ALZ_ST_OK; size_t k = 0;
+    while (r.pos < len) {
+        const SnappyChunk c = snappy_read_chunk(src, len, r.pos);
+        if (c.kind == SnappyChunk::TRUNCATED) { r.pos = c.next; st = ALZ_ST_INPUT_TRUNCATED; break; }
+        if (c.kind == SnappyChunk::RESERVED) { o = refused(ALZ_E_FORMAT); return true; }
+        if (c.kind == SnappyChunk::COMPRESSED) {
+            if (k >= n || ss[k].src_off != file_off + c.body) {                          // the chunk before ended elsewhere than it declared
+                if (k == 0) { o = refused(ALZ_E_INVALID); return true; }                 // (cannot happen: the first chunk is where the collection started)
+                return false;
+            }
+            const alz_result& m = rs[k++];
+            const int32_t cs = place_body(m, r.out, cap);
+            r.pos = c.body + m.src_used;
+            if (cs != ALZ_ST_OK) { st = cs; break; }
+        } else if (c.kind == SnappyChunk::STORED) {
+            r.pos = c.body;
+            if (r.out + c.stored > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
+            r.out += c.stored; r.pos = c.next;
+        } else r.pos = c.next;
+    }
+    o = stream_outcome(st, r.out, r.pos);
+    return true;
+}
+
+// A decoder lays the chunks out at the places they declare: a piece is a compressed or a stored chunk, in file order.  A compressed piece is
+// decoded at `at` into `cap` bytes (its declared size `n`, clipped to the destination); a stored piece is `n` bytes from `off` for `out`.
+struct SnappyPiece { bool stored; size_t hdr, off; uint32_t n, clen; uint64_t out, at; uint32_t cap; };
+struct SnappyLayout {
+    std::vector<SnappyPiece> pieces;
+    bool reserved = false;                                                               // the walk ended at a reserved chunk: E_FORMAT once reached
+    int32_t walk_st = ALZ_ST_OK;
+    size_t pos = 10; uint64_t out = 0;                                                   // where the walk ended; the declared sizes
+};
+// Every layer that copies stored chunks hands in a sink: sink.stored(off, out, n) -- n > 0 bytes of the file from `off` belong at `out` of the
+// output, and fit.  The layout reports the stored pieces at their declared places, the in-order reader those it passes.
+template <class Sink>
+inline void snappy_layout(const uint8_t* src, size_t len, uint64_t cap, SnappyLayout& w, Sink& sink) {
+    while (w.pos < len) {
+        const SnappyChunk c = snappy_read_chunk(src, len, w.pos);
+        w.pos = c.next;
+        if (c.kind == SnappyChunk::TRUNCATED) { w.walk_st = ALZ_ST_INPUT_TRUNCATED; break; }
+        if (c.kind == SnappyChunk::RESERVED) { w.reserved = true; break; }
+        if (c.kind == SnappyChunk::COMPRESSED) {
+            const uint32_t size = snappy_varint(src + c.body, len - c.body, nullptr);
+            const uint64_t out = w.out;
+            w.pieces.push_back(SnappyPiece{ false, c.hdr, c.body, size, c.len, out, out < cap ? out : cap, clamp32((size_t)(out < cap ? (cap - out < size ? cap - out : size) : 0)) });
+            w.out += size;
+        } else if (c.kind == SnappyChunk::STORED) {
+            w.pieces.push_back(SnappyPiece{ true, c.hdr, c.body, c.stored, c.len, w.out, w.out, 0 });
+            if (w.out + c.stored <= cap && c.stored) sink.stored(c.body, w.out, c.stored);
+            w.out += c.stored;
+        }
+    }
+}
+// The first failing piece in file order, compressed or stored, decides status and length; result(k): what the k-th compressed piece
+// returned.  The managed decoder continues wherever a chunk's body stopped; a chunk whose body does not end at its declared length is
+// refused here (ALZ_E_FORMAT).  True: the outcome is in `o`.  False: a chunk decodes to more than it declares (its last element runs past
+// the size), which moves every chunk behind it -- on in order with `r`, which stands at that chunk.
+template <class Results>
+inline bool snappy_judge(const SnappyLayout& w, uint64_t cap, Results result, SnappyReader& r, Outcome& o) {
+    uint64_t produced = w.out < cap ? w.out : cap; int32_t fst = ALZ_ST_OK; size_t k = 0;
+    for (const SnappyPiece& p : w.pieces) {
+        if (p.stored) {
+            if (p.out + p.n > cap) { fst = ALZ_ST_OUTPUT_CAPACITY; produced = p.out; break; }
+            continue;
+        }
+        const alz_result& g = result(k++);
+        int32_t cs = g.status;
+        if (cs == ALZ_ST_OUTPUT_CAPACITY && p.cap == p.n && p.at + (uint64_t)p.n < cap) { r = SnappyReader{ p.hdr, p.at, 0 }; return false; }
+        if (cs == ALZ_ST_OK && g.dst_len < p.n) cs = ALZ_ST_OUTPUT_CAPACITY;             // the declared size did not fit dst
+        if (cs == ALZ_ST_OK && (uint64_t)g.src_used + 4 != p.clen) { o = refused(ALZ_E_FORMAT); return true; }
+        if (cs != ALZ_ST_OK) { fst = cs; produced = p.at + g.dst_len; break; }
+    }
+    if (fst == ALZ_ST_OK && w.reserved) { o = refused(ALZ_E_FORMAT); return true; }
+    if (fst == ALZ_ST_OK && w.walk_st != ALZ_ST_OK) fst = w.walk_st;
+    o = stream_outcome(fst, produced, w.pos);
+    return true;
+}
+// The in-order reader, one compressed chunk per call: takes in what the chunk that was out returned (got; NULL at the start), then reads on.
+// True: the outcome is in `o`.  False: the body at r.pos is to be decoded at r.out, into all the room there is.
+template <class Sink>
+inline bool snappy_read_on(const uint8_t* src, size_t len, uint64_t cap, SnappyReader& r, const alz_result* got, Sink& sink, Outcome& o) {
+    int32_t st = ALZ_ST_OK;
+    if (got) {
+        r.out += got->dst_len;
+        if (got->status != ALZ_ST_OK) st = got->status;
+        else if ((uint64_t)got->src_used + 4 != r.clen) { o = refused(ALZ_E_FORMAT); return true; }   // (as the judge: a body that does not end at the declared length)
+        else r.pos += got->src_used;
+    }
+    while (st == ALZ_ST_OK && r.pos < len) {
+        const SnappyChunk c = snappy_read_chunk(src, len, r.pos);
+        r.pos = c.body;
+        if (c.kind == SnappyChunk::TRUNCATED) { st = ALZ_ST_INPUT_TRUNCATED; break; }
+        if (c.kind == SnappyChunk::RESERVED) { o = refused(ALZ_E_FORMAT); return true; }
+        if (c.kind == SnappyChunk::COMPRESSED) { r.clen = c.len; return false; }
+        if (c.kind == SnappyChunk::STORED) {
+            if (r.out + c.stored > cap) { st = ALZ_ST_OUTPUT_CAPACITY; break; }
+            if (c.stored) sink.stored(c.body, r.out, c.stored);
+            r.out += c.stored;
+        }
+        r.pos = c.next;
+    }
+    o = stream_outcome(st, r.out, r.pos);
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------- the writers

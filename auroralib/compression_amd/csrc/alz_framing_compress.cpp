@@ -163,11 +163,7 @@ extern "C" {
 
 int alz_framing_compress_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
                                const alz_stream* files, uint8_t* dst_base, size_t dst_bytes, alz_file_result* results) {
-    if (!ctx || (n && (!files || !results)) || (src_bytes && !src_base) || (dst_bytes && !dst_base)) return ALZ_E_INVALID;
-    for (uint32_t i = 0; i < n; i++) {
-        if (!lz4_container(files[i].format) && files[i].format != ALZ_C_SNAPPY) return ALZ_E_INVALID;
-        if (!range_ok(files[i].src_off, files[i].src_len, src_bytes) || !range_ok(files[i].dst_off, files[i].dst_cap, dst_bytes)) return ALZ_E_INVALID;
-    }
+    if (int rc = check_files(ctx, n, src_base, src_bytes, files, dst_base, dst_bytes, results, true, [](uint32_t c) { return lz4_container(c) || c == ALZ_C_SNAPPY; })) return rc;
     for (double& ms : g_phase_ms) ms = 0;
     if (n == 0) return ALZ_OK;
     std::vector<Opened> opened(n);

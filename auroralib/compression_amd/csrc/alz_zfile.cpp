@@ -61,13 +61,8 @@ void close_member(const alz_stream& file, const uint8_t* src, FileState& f, alz_
 
 int run(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files, uint8_t* dst_base, size_t dst_bytes,
         alz_file_result* results, bool measure) {
-    if (!ctx || (n && (!files || !results)) || (src_bytes && !src_base) || (!measure && dst_bytes && !dst_base)) return ALZ_E_INVALID;
+    if (int rc = check_files(ctx, n, src_base, src_bytes, files, dst_base, dst_bytes, results, !measure, [](uint32_t format) { return format <= ALZ_ZFILE_GZIP; })) return rc;
     if (n == 0) return ALZ_OK;
-    for (uint32_t i = 0; i < n; i++) {
-        if (files[i].format > ALZ_ZFILE_GZIP) return ALZ_E_INVALID;
-        if (!range_ok(files[i].src_off, files[i].src_len, src_bytes)) return ALZ_E_INVALID;
-        if (!measure && !range_ok(files[i].dst_off, files[i].dst_cap, dst_bytes)) return ALZ_E_INVALID;
-    }
     std::vector<FileState> state(n);
     uint32_t active = 0;
     for (uint32_t i = 0; i < n; i++) {

@@ -81,7 +81,7 @@ def lz4_legacy(blocks, eof_flag=True):
 # ------------------------------------------------------------------------------------------------ generated files + mutations
 # Framed files with their expected output from a byte-wise model of the managed readers (one window per LZ4 frame, offset 0 = distance
 # 65 536 (E1), zeros in front of a window's start (E2), a fresh window per legacy block and per Snappy chunk), and a seeded mutator that
-# works on the structure the generator recorded.  Nothing here calls the C oracle: checksum functions are passed in.
+# works on the structure the generator recorded.  The generator and the mutator do not call the C oracle: checksum functions are passed in.
 import os  # noqa: E402
 
 SEED = int(os.environ.get("ALZ_FUZZ_SEED", "1234"))
@@ -487,3 +487,39 @@ def mutants(case, seed, per_case=12):
                 add("declared size@%d %d->%d" % (o, v, nv), _with(d, o, _snappy_varint(nv), n))
     rng.shuffle(out)
     return out[:per_case] if per_case else out
+
+
+def snappy_refusal_reached(data, cap):
+    """The documented deviation: the library refuses (E_FORMAT) a compressed chunk whose body does not end at its declared length; the
+    oracle reads on from where the body stopped.  True when the oracle's in-order walk reaches such a chunk before any failure."""
+    import oracle_lib as O
+    from auroralib.compression_amd import _abi as A
+    pos, out = 10, 0
+    while pos < len(data):
+        if pos + 4 > len(data):
+            return False
+        typ, cl = data[pos], int.from_bytes(data[pos + 1:pos + 4], "little")
+        pos += 4
+        if typ == 0:
+            if pos + 4 > len(data):
+                return False
+            _, r = O.decode_stream(A.FMT_SNAPPY_RAW, data[pos + 4:], cap=max(cap - out, 0))
+            if r.status != A.ST_OK:
+                return False
+            if r.src_used + 4 != cl:
+                return True
+            out += r.dst_len
+            pos += 4 + r.src_used
+        elif typ == 1:
+            if pos + 4 > len(data) or cl < 4:
+                return False
+            n = min(cl - 4, len(data) - pos - 4)
+            if out + n > cap:
+                return False
+            out += n
+            pos += 4 + n
+        elif typ <= 0x7F:
+            return False
+        else:
+            pos = min(pos + cl, len(data))
+    return False
