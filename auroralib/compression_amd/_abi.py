@@ -191,4 +191,17 @@ FRAMING_COMPRESS_PROTOTYPES = {
     "alz_framing_compress_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
 }
 
+# DEFLATE written on the GPU: raw streams (level 0..9, flags DEFLATE_FIXED) and ZLib / GZip files (kind: ZFILE_ZLIB / ZFILE_GZIP, in a batch Stream.format)
+DEFLATE_FIXED = 1
+_DEFLATE_ENCODE = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+DEFLATE_PROTOTYPES = {
+    "alz_deflate_bound": [C.c_size_t],                                            # returns size_t (DEFLATE_RESTYPES)
+    "alz_deflate_block_bytes": [],
+    "alz_deflate_encode_batch": _DEFLATE_ENCODE, "alz_deflate_encode_batch_device": _DEFLATE_ENCODE,
+    "alz_deflate_file_bound": [C.c_uint32, C.c_size_t],                           # returns size_t
+    "alz_deflate_file_compress": [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "alz_deflate_file_compress_batch": _DEFLATE_ENCODE,
+}
+DEFLATE_RESTYPES = {"alz_deflate_bound": C.c_size_t, "alz_deflate_file_bound": C.c_size_t}
+
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16 and C.sizeof(FileResult) == 16

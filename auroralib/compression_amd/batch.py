@@ -288,6 +288,24 @@ class Context:
         check(self.lib.alz_framing_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
         return dst, res
 
+    # ---- DEFLATE written on the GPU: raw streams (src_* the raw input, dst_* where the stream goes); level 0..9, flags A.DEFLATE_FIXED
+    def deflate_encode_batch(self, streams, src, dst_bytes, level=6, flags=0, dst=None):
+        """alz_deflate_encode_batch on host buffers -> (dst, results).  `dst`: a caller-owned uint8 array of >= dst_bytes to write into (default: a new one)."""
+        return self._host_decode(self.lib.alz_deflate_encode_batch, (level, flags), streams, src, dst_bytes, dst)
+
+    def deflate_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes, level=6, flags=0):
+        """alz_deflate_encode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
+        return self._device(self.lib.alz_deflate_encode_batch_device, (level, flags), streams, d_src, src_bytes, d_dst, dst_bytes)
+
+    def deflate_file_compress_batch(self, files, src, dst_bytes, level=6, flags=0, dst=None):
+        """alz_deflate_file_compress_batch on host buffers -> (dst, results): per file (Stream.format: A.ZFILE_ZLIB or A.ZFILE_GZIP) what
+        alz_deflate_file_compress writes and returns for it alone.  `dst`: a caller-owned uint8 array of >= dst_bytes (default: a new one)."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        check(self.lib.alz_deflate_file_compress_batch(self.h, level, flags, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""

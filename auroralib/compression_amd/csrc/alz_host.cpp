@@ -135,7 +135,7 @@ struct alz_ctx {
     void* d_plan = nullptr; size_t d_plan_cap = 0;   // plan arrays of the host-buffer entry points (no hipMalloc / hipFree per call)
     // encoder scratch (prev links, narrowed links, matches, masks ...: ~45 GB for 10 000 x 256 KiB at quality 8), one grow-only slot
     // per purpose: allocating and freeing it per call cost 1-2 s, four times the kernels.  alz_ctx_release_scratch() returns it.
-    enum { ENC_STREAMS, ENC_RESULTS, ENC_AUX, ENC_INDEX, ENC_POS, ENC_PREV4, ENC_PREVM, ENC_MATCH, ENC_SIDE, ENC_MASK, ENC_TAIL, ENC_BIG, ENC_SEL, ENC_NARROW, ENC_SEG, ENC_SLOTS };
+    enum { ENC_STREAMS, ENC_RESULTS, ENC_AUX, ENC_INDEX, ENC_POS, ENC_PREV4, ENC_PREVM, ENC_MATCH, ENC_SIDE, ENC_MASK, ENC_TAIL, ENC_BIG, ENC_SEL, ENC_NARROW, ENC_SEG, ENC_DEFLATE, ENC_SLOTS };
     void* enc_buf[ENC_SLOTS] = {nullptr}; size_t enc_cap[ENC_SLOTS] = {0};
     copy_pool* pool = nullptr;                 // created with the pinned buffers
     std::vector<copy_job> jobs;                // (scratch of the staging loops)
@@ -1144,6 +1144,59 @@ int alz_inflate_measure_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, s
 }
 int alz_inflate_measure_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams, alz_result* results) {
     return inflate_batch(c, true, true, {n, d_src_base, src_bytes, streams, nullptr, 0, results});
+}
+
+// ---------------------------------------------------------------- DEFLATE, the other direction (alz_inflate.hip, alz_inflate.h): alz_deflate_*
+// One kind; every context mode runs the same kernels.  The host cuts the streams into blocks; the block table, the plans and the tokens
+// (one word per input byte) live in the context's encoder scratch.
+size_t alz_deflate_bound(size_t src_len) {
+    const size_t blocks = src_len ? (src_len + ALZ_DEFLATE_BLOCK - 1) / ALZ_DEFLATE_BLOCK : 1;
+    return src_len + 5 * blocks;                             // every block is at most its stored form
+}
+int alz_deflate_block_bytes(void) { return (int)ALZ_DEFLATE_BLOCK; }
+
+static int deflate_batch(alz_ctx* c, bool device, int level, uint32_t flags, const batch_args& a) {
+    const char* what = device ? "alz_deflate_encode_batch_device" : "alz_deflate_encode_batch";
+    if (level < 0 || level > 9) return fail(ALZ_E_INVALID, "%s: level %d is not 0..9", what, level);
+    if (flags & ~ALZ_DEFLATE_FIXED) return fail(ALZ_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+    std::vector<alz_deflate_blk> blocks;                     // (outlive the launches: grouped_core waits for the stream)
+    std::vector<uint32_t> first;
+    return batch_call(c, what, 1, DL_ONLY_OK, device, a,
+        [&]() -> int {
+            for (uint32_t i = 0; i < a.n; i++)
+                if (a.streams[i].src_len >= 0x7FFFFF00u) return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: 0x7FFFFF00 bytes and more", what, i);
+            return ALZ_OK;
+        },
+        [&](uint32_t, const uint8_t* d_src, uint8_t* d_dst, const alz_stream* d_streams, const uint32_t*, uint32_t, alz_result* d_results) -> hipError_t {
+            uint64_t tok = 0;
+            first.resize((size_t)a.n + 1);
+            for (uint32_t i = 0; i < a.n; i++) {
+                first[i] = (uint32_t)blocks.size();
+                const uint32_t len = a.streams[i].src_len, nb = len ? (len + ALZ_DEFLATE_BLOCK - 1) / ALZ_DEFLATE_BLOCK : 1u;
+                if (blocks.size() + nb > 0x7FFFFFFFull) return hipErrorInvalidValue;
+                for (uint32_t k = 0; k < nb; k++) blocks.push_back(alz_deflate_blk{i, k, tok + (uint64_t)k * ALZ_DEFLATE_BLOCK});
+                tok += len;
+            }
+            first[a.n] = (uint32_t)blocks.size();
+            const size_t nblk = blocks.size();
+            const size_t o_first = (nblk * sizeof(alz_deflate_blk) + 15) & ~(size_t)15, o_plans = (o_first + first.size() * 4 + 15) & ~(size_t)15,
+                         o_tok = (o_plans + nblk * sizeof(alz_deflate_plan) + 15) & ~(size_t)15;
+            if (grow(c, &c->enc_buf[alz_ctx::ENC_DEFLATE], &c->enc_cap[alz_ctx::ENC_DEFLATE], o_tok + (size_t)tok * 4 + 16) != ALZ_OK) return hipErrorOutOfMemory;
+            uint8_t* base = (uint8_t*)c->enc_buf[alz_ctx::ENC_DEFLATE];
+            hipError_t e = hipMemcpyAsync(base, blocks.data(), nblk * sizeof(alz_deflate_blk), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(base + o_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) return e;
+            return alz_launch_deflate_encode(c->stream, d_src, d_dst, d_streams, a.n, (const alz_deflate_blk*)base, (uint32_t)nblk, (const uint32_t*)(base + o_first),
+                                             (uint32_t*)(base + o_tok), (alz_deflate_plan*)(base + o_plans), level, flags, d_results);
+        });
+}
+int alz_deflate_encode_batch(alz_ctx* c, int level, uint32_t flags, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                             uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return deflate_batch(c, false, level, flags, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
+}
+int alz_deflate_encode_batch_device(alz_ctx* c, int level, uint32_t flags, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                    uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    return deflate_batch(c, true, level, flags, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
 }
 
 // ---------------------------------------------------------------- checksums: Adler-32 and CRC-32 of byte ranges (alz_checksum.hip); kinds: alz_checksum_kind

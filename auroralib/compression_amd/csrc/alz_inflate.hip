@@ -389,3 +389,249 @@ hipError_t alz_launch_inflate_measure(hipStream_t stream, const void* d_src, con
     hipLaunchKernelGGL(alz_inflate_measure_kernel, dim3(count), dim3(64), 0, stream, (const u8*)d_src, streams, index, count, results);
     return hipGetLastError();
 }
+
+// ================================================================================================ the encoder (alz_deflate_*)
+// alz_inflate.h describes the launches and holds the code builder (host and device code, tested on the CPU).  Grid mapping: one wavefront
+// (= one 64-thread workgroup) per BLOCK of ALZ_DEFLATE_BLOCK input bytes, so one long stream fills the GPU as a batch of short ones does.
+//
+// find.  The history of a DEFLATE encoder is its input: a block first inserts the 32 KiB in front of it, then itself, 64 positions per
+// step.  LDS holds head[2^14] (the newest position + 1 per hash of three bytes) and prev[32 Ki] (per position mod 32 Ki the distance to the
+// one before it on its chain; 0 ends it).  A step reads the heads, links its 64 positions -- to the nearest EARLIER LANE with the same
+// three bytes if there is one (63 shuffles), else to the head -- and only then publishes them (atomicMax: the newest wins whatever the
+// order).  So the chains, and with them the tokens, are a function of the stream's bytes and the level alone.  Inside the block every lane
+// then walks its chain (level: how many candidates, which length ends the walk), and a wave-uniform loop picks the tokens greedily or, from
+// level 4 on, lazily: a position whose successor has a longer match becomes a literal.  A slot of prev that a position 32 KiB later has
+// overwritten can lead the walk to a position that is no real candidate; every candidate is compared byte by byte, and the walk ends at
+// distance 32 768 and at the stream's start, so such a slot costs a compare.  Matches never leave the block, never exceed 258 bytes.
+// emit.  Each lane turns a token into at most 48 bits, a wave prefix sum places them, and the lanes OR them into a zeroed image of the
+// whole block in LDS (a block is never larger than its stored form: 32 709 bytes); the image is then stored at the block's byte offset.
+#define DFL_HASH_BITS 14u
+#define DFL_WIN 32768u
+#define DFL_STAGE_WORDS ((ALZ_DEFLATE_BLOCK + 64u) / 4u)
+
+__device__ __forceinline__ u32 dfl_ld4(const u8* p) { u32 v; __builtin_memcpy(&v, p, 4); return v; }
+// equal bytes at a and b, at most `maxlen` (both readable that far)
+__device__ __forceinline__ u32 dfl_match_len(const u8* a, const u8* b, u32 maxlen) {
+    u32 i = 0;
+    while (i + 4u <= maxlen) {
+        const u32 x = dfl_ld4(a + i) ^ dfl_ld4(b + i);
+        if (x) return i + ((u32)__builtin_ctz(x) >> 3);
+        i += 4u;
+    }
+    while (i < maxlen && a[i] == b[i]) i++;
+    return i;
+}
+
+__global__ __launch_bounds__(64) void alz_deflate_find_kernel(const u8* __restrict__ src_base, const alz_stream* __restrict__ streams,
+                                                              const alz_deflate_blk* __restrict__ blocks, u32 nblocks, int level, u32 flags,
+                                                              u32* __restrict__ tokens, alz_deflate_plan* __restrict__ plans) {
+    __shared__ u32 head[1u << DFL_HASH_BITS];
+    __shared__ unsigned short prev[DFL_WIN];
+    __shared__ u32 lit_freq[ALZ_DEFLATE_NLIT + 2], dist_freq[ALZ_DEFLATE_NDIST + 2];
+    __shared__ alz_deflate_work work;
+    __shared__ __attribute__((aligned(16))) alz_deflate_plan plan;
+    __shared__ u32 sizes[3];
+    const u32 bid = blockIdx.x;
+    if (bid >= nblocks) return;
+    const u32 lane = threadIdx.x;
+    const alz_deflate_blk blk = blocks[bid];
+    const alz_stream st = streams[blk.sid];
+    const u8* src = src_base + st.src_off;
+    const u32 n = uni(st.src_len);
+    const u32 bs = uni(blk.k) * ALZ_DEFLATE_BLOCK;
+    const u32 blen = n - bs < ALZ_DEFLATE_BLOCK ? n - bs : ALZ_DEFLATE_BLOCK;
+    const u32 bend = bs + blen;
+    const bool final = bend == n;
+    u32* tok = tokens + blk.tok_at;
+
+    for (u32 i = lane; i < sizeof(plan) / 4u; i += 64u) ((u32*)&plan)[i] = 0;
+    for (u32 i = lane; i < ALZ_DEFLATE_NLIT + 2; i += 64u) lit_freq[i] = 0;
+    if (lane < ALZ_DEFLATE_NDIST + 2) dist_freq[lane] = 0;
+    u32 ntok = 0;
+    if (level > 0 && blen > 0) {
+        for (u32 i = lane; i < (1u << DFL_HASH_BITS); i += 64u) head[i] = 0;
+        for (u32 i = lane; i < DFL_WIN; i += 64u) prev[i] = 0;
+        __syncthreads();
+        const u32 chain_max = alz_deflate_level_chain(level), nice = alz_deflate_level_nice(level);
+        const bool lazy = alz_deflate_level_lazy(level);
+        u32 skip = 0;                                        // positions of the coming steps that the last match covers
+        for (u32 gs = bs > DFL_WIN ? bs - DFL_WIN : 0u; gs < bend; gs += 64u) {
+            const u32 p = gs + lane;
+            const bool hashable = p + 3u <= n;
+            u32 tri = 0xFFFFFFFFu, h = 0;
+            if (hashable) {
+                tri = (u32)src[p] | ((u32)src[p + 1] << 8) | ((u32)src[p + 2] << 16);
+                h = (tri * 0x9E3779B1u) >> (32u - DFL_HASH_BITS);
+            }
+            const u32 old = hashable ? head[h] : 0u;
+            u32 delta = 0;
+#pragma unroll 1
+            for (u32 d = 1; d < 64u; d++) {
+                const u32 t = __shfl_up(tri, d);
+                if (lane >= d && t == tri && !delta) delta = d;
+            }
+            if (!hashable) delta = 0;
+            else if (!delta && old) delta = p + 1u - old;
+            if (delta > DFL_WIN) delta = 0;
+            if (hashable) prev[p & (DFL_WIN - 1u)] = (unsigned short)delta;
+            __syncthreads();
+            if (hashable) atomicMax(&head[h], p + 1u);
+            __syncthreads();
+            if (gs < bs) continue;                            // the window in front of the block: inserted only
+            // ---- the best match of every position
+            const u32 maxlen = p < bend ? (bend - p < 258u ? bend - p : 258u) : 0u;
+            u32 best = 0, best_dist = 0;
+            if (maxlen >= 3u && hashable) {
+                u32 cur = p, dl = delta;
+                for (u32 c = chain_max; dl && c; c--) {
+                    if (dl > cur) break;
+                    cur -= dl;
+                    const u32 dist = p - cur;
+                    if (dist > DFL_WIN) break;
+                    if (best < 3u || src[cur + best] == src[p + best]) {
+                        const u32 len = dfl_match_len(src + cur, src + p, maxlen);
+                        if (len > best) { best = len; best_dist = dist; }
+                        if (best >= nice || best >= maxlen) break;
+                    }
+                    dl = prev[cur & (DFL_WIN - 1u)];
+                }
+                if (best < 3u || (best == 3u && best_dist > 4096u)) best = 0;
+            }
+            // ---- the parse of these 64 positions: wave-uniform
+            const u32 nvalid = bend - gs < 64u ? bend - gs : 64u;
+            u64 tmask = 0, lmask = 0;
+            u32 cur = skip;
+            while (cur < nvalid) {
+                u32 L = (u32)__builtin_amdgcn_readlane((int)best, (int)cur);
+                if (lazy && L >= 3u && cur + 1u < nvalid && (u32)__builtin_amdgcn_readlane((int)best, (int)(cur + 1u)) > L) L = 0;
+                tmask |= 1ull << cur;
+                if (L < 3u) { lmask |= 1ull << cur; cur += 1u; } else cur += L;
+            }
+            skip = cur - nvalid;
+            if ((tmask >> lane) & 1ull) {
+                const u32 at = ntok + (u32)__popcll(tmask & ((1ull << lane) - 1ull));
+                if ((lmask >> lane) & 1ull) {
+                    const u32 b = src[p];
+                    tok[at] = b;
+                    atomicAdd(&lit_freq[b], 1u);
+                } else {
+                    u32 eb, ev;
+                    tok[at] = 0x80000000u | ((best - 3u) << 16) | (best_dist - 1u);
+                    atomicAdd(&lit_freq[alz_deflate_len_sym(best, &eb, &ev)], 1u);
+                    atomicAdd(&dist_freq[alz_deflate_dist_sym(best_dist, &eb, &ev)], 1u);
+                }
+            }
+            ntok += (u32)__popcll(tmask);
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        lit_freq[256] = 1;
+        alz_deflate_plan_block(lit_freq, dist_freq, blen, ntok, final, level == 0, (flags & 1u) != 0, &work, &plan, sizes);
+    }
+    __syncthreads();
+    for (u32 i = lane; i < sizeof(plan) / 4u; i += 64u) ((u32*)&plans[bid])[i] = ((const u32*)&plan)[i];
+}
+
+// one lane per stream: where its blocks go, whether they fit, the result
+__global__ __launch_bounds__(64) void alz_deflate_place_kernel(const alz_stream* __restrict__ streams, u32 n, const u32* __restrict__ first,
+                                                               alz_deflate_plan* __restrict__ plans, alz_result* __restrict__ results) {
+    const u32 sid = blockIdx.x * 64u + threadIdx.x;
+    if (sid >= n) return;
+    u64 at = 0;
+    for (u32 b = first[sid]; b < first[sid + 1]; b++) { plans[b].dst_at = (u32)at; at += plans[b].bytes; }
+    const bool fits = at <= (u64)streams[sid].dst_cap;
+    alz_result r;
+    r.dst_len = fits ? (u32)at : 0u; r.src_used = fits ? streams[sid].src_len : 0u; r.status = fits ? ALZ_ST_OK : ALZ_ST_OUTPUT_CAPACITY; r.reserved = 0;
+    results[sid] = r;
+}
+
+// `nb` bits of `v` (at most 48) at bit `pos` of the zeroed image
+__device__ __forceinline__ void dfl_put(u32* stage, u32 pos, u64 v, u32 nb) {
+    if (!nb) return;
+    const u32 w = pos >> 5, sh = pos & 31u;
+    const u32 a0 = (u32)(v << sh);
+    const u64 rest = sh ? v >> (32u - sh) : v >> 32;
+    if (a0) atomicOr(&stage[w], a0);
+    if ((u32)rest) atomicOr(&stage[w + 1], (u32)rest);
+    if ((u32)(rest >> 32)) atomicOr(&stage[w + 2], (u32)(rest >> 32));
+}
+
+__global__ __launch_bounds__(64) void alz_deflate_emit_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
+                                                              const alz_deflate_blk* __restrict__ blocks, u32 nblocks, const u32* __restrict__ tokens,
+                                                              const alz_deflate_plan* __restrict__ plans, const alz_result* __restrict__ results) {
+    __shared__ u32 stage[DFL_STAGE_WORDS];
+    __shared__ unsigned short lit_code[288], dist_code[32], blc[16];
+    __shared__ u8 lit_len[288], dist_len[32];
+    const u32 bid = blockIdx.x;
+    if (bid >= nblocks) return;
+    const u32 lane = threadIdx.x;
+    const alz_deflate_blk blk = blocks[bid];
+    if (results[blk.sid].status != ALZ_ST_OK) return;        // the stream does not fit: nothing of it is written
+    const alz_stream st = streams[blk.sid];
+    const alz_deflate_plan* pl = &plans[bid];
+    const u32 n = uni(st.src_len), bs = uni(blk.k) * ALZ_DEFLATE_BLOCK;
+    const u32 blen = n - bs < ALZ_DEFLATE_BLOCK ? n - bs : ALZ_DEFLATE_BLOCK;
+    const bool final = bs + blen == n;
+    const u32 type = uni(pl->type), bytes = uni(pl->bytes), ntok = uni(pl->ntok);
+    u8* dst = dst_base + st.dst_off + pl->dst_at;
+    if (type == ALZ_DEFLATE_STORED) {
+        if (lane < 5u) dst[lane] = lane == 0 ? (u8)final : (u8)(((lane < 3u ? blen : ~blen) >> (8u * ((lane - 1u) & 1u))) & 0xFFu);
+        const u8* s = src_base + st.src_off + bs;
+        for (u32 i = lane; i < blen; i += 64u) dst[5u + i] = s[i];
+        return;
+    }
+    for (u32 i = lane; i < DFL_STAGE_WORDS; i += 64u) stage[i] = 0;
+    for (u32 i = lane; i < 288u; i += 64u) lit_len[i] = type == ALZ_DEFLATE_DYNAMIC ? pl->lit_len[i] : (u8)alz_deflate_fixed_len(i);
+    if (lane < 32u) dist_len[lane] = type == ALZ_DEFLATE_DYNAMIC ? pl->dist_len[lane] : (u8)5;
+    __syncthreads();
+    if (lane == 0) alz_deflate_codes(lit_len, 288u, lit_code, blc);
+    __syncthreads();
+    if (lane == 0) alz_deflate_codes(dist_len, 32u, dist_code, blc);
+    __syncthreads();
+    u32 pos = 3u;
+    if (lane == 0) dfl_put(stage, 0, (u64)((final ? 1u : 0u) | (type << 1)), 3u);
+    if (type == ALZ_DEFLATE_DYNAMIC) {
+        const u32 hb = uni(pl->hdr_bits);
+        for (u32 i = lane; i * 8u < hb; i += 64u) dfl_put(stage, 3u + i * 8u, (u64)pl->hdr[i], 8u);   // (the bits of the last byte behind hdr_bits are zero)
+        pos += hb;
+    }
+    const u32* tok = tokens + blk.tok_at;
+    for (u32 base = 0; base <= ntok; base += 64u) {
+        const u32 i = base + lane;
+        u64 v = 0; u32 nb = 0;
+        if (i < ntok) {
+            const u32 t = tok[i];
+            if (!(t & 0x80000000u)) { v = lit_code[t]; nb = lit_len[t]; }
+            else {
+                u32 eb, ev;
+                const u32 ls = alz_deflate_len_sym(((t >> 16) & 0xFFu) + 3u, &eb, &ev);
+                v = lit_code[ls]; nb = lit_len[ls];
+                v |= (u64)ev << nb; nb += eb;
+                const u32 ds = alz_deflate_dist_sym((t & 0x7FFFu) + 1u, &eb, &ev);
+                v |= (u64)dist_code[ds] << nb; nb += dist_len[ds];
+                v |= (u64)ev << nb; nb += eb;
+            }
+        } else if (i == ntok) { v = lit_code[256]; nb = lit_len[256]; }
+        u32 incl = nb;
+#pragma unroll
+        for (u32 d = 1; d < 64u; d <<= 1) { const u32 t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+        if (pos + incl <= 8u * bytes) dfl_put(stage, pos + incl - nb, v, nb);   // (always: the plan counted these very bits)
+        pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    // the joining: three zero bits and the padding are already there
+    if (!final && lane == 0) dfl_put(stage, 8u * (bytes - 2u), 0xFFFFull, 16u);
+    __syncthreads();
+    for (u32 i = lane; i < bytes; i += 64u) dst[i] = (u8)(stage[i >> 2] >> (8u * (i & 3u)));
+}
+
+hipError_t alz_launch_deflate_encode(hipStream_t stream, const void* d_src, void* d_dst, const alz_stream* d_streams, u32 n,
+                                     const alz_deflate_blk* d_blocks, u32 nblocks, const u32* d_first, u32* d_tokens,
+                                     alz_deflate_plan* d_plans, int level, u32 flags, alz_result* d_results) {
+    if (n == 0 || nblocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(alz_deflate_find_kernel, dim3(nblocks), dim3(64), 0, stream, (const u8*)d_src, d_streams, d_blocks, nblocks, level, flags, d_tokens, d_plans);
+    hipLaunchKernelGGL(alz_deflate_place_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, d_streams, n, d_first, d_plans, d_results);
+    hipLaunchKernelGGL(alz_deflate_emit_kernel, dim3(nblocks), dim3(64), 0, stream, (const u8*)d_src, (u8*)d_dst, d_streams, d_blocks, nblocks,
+                       (const u32*)d_tokens, (const alz_deflate_plan*)d_plans, (const alz_result*)d_results);
+    return hipGetLastError();
+}

@@ -648,7 +648,8 @@ class APLib:
 
 
 INFLATE_NO_ENCODER = ("%s has no encoder here: the reference hands Compress to the BCL, whose output depends on the zlib build behind it, "
-                      "so there are no managed bytes to be bit-identical with (include/auroralz.h)")
+                      "so there are no managed bytes to be bit-identical with (include/auroralz.h); Deflate / DeflateMany write the file with "
+                      "the library's own DEFLATE encoder")
 
 
 class _InflateFile:
@@ -691,15 +692,66 @@ class _InflateFile:
     def Compress(self, data, settings=None):
         raise NotImplementedError(INFLATE_NO_ENCODER % type(self).__name__)
 
+    # ---- the library's own encoder (alz_deflate_*): valid files of the class, not the bytes a BCL would write
+    def _kind(self):
+        return A.ZFILE_ZLIB if self.prefix == "zlib" else A.ZFILE_GZIP
+
+    def DeflateLevel(self, settings=None):
+        """(level, fixed): what the reference's Compress would hand the BCL for these settings."""
+        raise NotImplementedError
+
+    def Deflate(self, data, level=6, fixed=False):
+        """The file of this class around a DEFLATE body of `level` 0..9 (alz_deflate_file_compress); fixed: fixed Huffman codes only."""
+        data = bytes(data)
+        lib = load()
+        cap = lib.alz_deflate_file_bound(self._kind(), len(data))
+        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
+        dl = C.c_size_t()
+        check(lib.alz_deflate_file_compress(_context().h, self._kind(), level, A.DEFLATE_FIXED if fixed else 0, data, len(data),
+                                            dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
+        return dst_arr[:dl.value].tobytes()
+
+    def DeflateMany(self, datas, level=6, fixed=False):
+        """Deflate for a whole set of inputs in ONE alz_deflate_file_compress_batch.  Returns a list with, per input, the file's bytes -- or the
+        exception instance Deflate would have raised for it."""
+        datas = [bytes(d) for d in datas]
+        lib = load()
+        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
+        table, so, do = (A.Stream * len(datas))(), 0, 0
+        for i, d in enumerate(datas):
+            cap = lib.alz_deflate_file_bound(self._kind(), len(d))
+            table[i] = A.Stream(so, do, len(d), cap, 0, 0, 0, self._kind())
+            so += len(d)
+            do += (cap + 15) & ~15
+        dst, res = _context().deflate_file_compress_batch(table, src, do, level, A.DEFLATE_FIXED if fixed else 0)
+        out = []
+        for i, r in enumerate(res):
+            if r.rc:
+                out.append(AlzError(r.rc, "alz_deflate_file_compress_batch: file %d" % i))
+            else:
+                out.append(dst[table[i].dst_off:table[i].dst_off + r.dst_len].tobytes())
+        return out
+
 
 class ZLib(_InflateFile):
     """src/AuroraLib.Compression/Formats/Common/ZLib.cs -- RFC 1950: CMF, FLG, a DEFLATE body, the Adler-32 of the output (alz_zlib_*)."""
     prefix = "zlib"
 
+    def DeflateLevel(self, settings=None):
+        """ZLib.cs:43-44: level = Quality * 8 / 15 rounded down, CompatibilityMode (Strategy bit 0) asks for fixed codes."""
+        settings = settings or CompressionSettings.Balanced
+        return settings.Quality * 8 // 15, bool(settings.Strategy & 1)
+
 
 class GZip(_InflateFile):
     """src/AuroraLib.Compression/Formats/Common/GZip.cs -- RFC 1952: members of header, DEFLATE body, CRC-32 and ISIZE (alz_gzip_*)."""
     prefix = "gzip"
+
+    def DeflateLevel(self, settings=None):
+        """The explicit CompressionLevel operator (CompressionSettings.cs:65-73): NoCompression, Fastest, Optimal, SmallestSize; never fixed."""
+        settings = settings or CompressionSettings.Balanced
+        q = settings.Quality
+        return (0 if q <= 2 else 1 if q <= 6 else 6 if q <= 9 else 9), False
 
 
 BITLZ_NO_ENCODER = ("%s has no encoder here: CompressHeaderless runs the LzChainMatchFinder, the bar is bit-identity with the managed bytes checked against "

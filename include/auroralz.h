@@ -510,7 +510,8 @@ int alz_allz_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_
  * alz_inflate_measure_batch*: results[i] is what alz_inflate_decode_batch would return for streams[i] -- status, dst_len, and src_used
  *   wherever it is defined; dst_off is ignored, dst_cap only bounds the count (0xFFFFFF00 for "the size"), nothing is written on the
  *   device but the results.
- * THERE IS NO ENCODER: the BCL's output depends on the zlib build behind it, so there are no managed bytes to be identical with.  Preset
+ * THE ENCODER is alz_deflate_* below (behind alz_zfile_*): the BCL's output depends on the zlib build behind it, so there are no managed
+ *   bytes to be identical with, and its contract is the one above read backwards.  Preset
  *   dictionaries are not supported.  alz_brute_force and alz_container_scan do not try DEFLATE. */
 int alz_inflate_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                              uint8_t* dst_base, size_t dst_bytes, alz_result* results);
@@ -622,6 +623,67 @@ int alz_zfile_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, si
                            uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
 int alz_zfile_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
                             alz_file_result* results);
+
+/* ---------------------------------------- DEFLATE written on the GPU: raw streams, ZLib and GZip files
+ * The reference hands ZLib.Compress / GZip.Compress to the BCL (ZLib.cs:36-46, GZip.cs:36-43): its contract is "whatever the zlib behind
+ * the BCL writes", any RFC 1951 stream that inflates back to the input.  BIT-IDENTITY DOES NOT APPLY HERE; the bar is the one of the
+ * decoder read backwards: a stream is right when zlib's `inflate` (window bits -15) reads it to its end, with no byte left over and the
+ * input as output, and alz_inflate_decode_batch reads it the same way.  So no code set is incomplete other than a single 1-bit code,
+ * symbols 286 / 287 / 30 / 31 are never used, no distance exceeds 32 768 or reaches in front of the stream's start, no length exceeds
+ * 258, no stored block holds more than 65 535 bytes.
+ * alz_stream and alz_result are reused: src_off / src_len is the raw input, dst_off / dst_cap where the stream goes; decom_len, aux0, aux1
+ * and format are IGNORED.  The slack rules are those of alz_inflate_*.  The kernels read nothing outside a stream's source range.
+ * level    0..9 with zlib's meaning; 0 writes stored blocks only.  1..9 search harder as they rise -- per position the finder compares at
+ *          most `chain` candidates of its hash chain, stops at a match of `nice` bytes, and from level 4 on parses lazily (a position
+ *          whose successor has a longer match becomes a literal):
+ *            level   1    2    3    4    5    6    7    8     9
+ *            chain   4    8   16   16   32   64  128  256  1024
+ *            nice   32   64  128  128  258  258  258  258   258
+ *            lazy    -    -    -  yes  yes  yes  yes  yes   yes
+ *          A match of 3 bytes further than 4 096 back is dropped (it costs more than its literals), as zlib does.
+ * flags    ALZ_DEFLATE_FIXED: fixed Huffman codes only (what ZLib.cs:43 maps CompatibilityMode to).  Any other level or flag bit is
+ *          ALZ_E_INVALID.
+ * blocks   A stream is cut into blocks of alz_deflate_block_bytes() (32 704) input bytes; every kernel's unit of work is a block, so ONE
+ *          long stream fills the GPU as a batch of short ones does.  A block's matches reach back into earlier blocks of its stream (the
+ *          history is the input: a block first inserts the 32 KiB in front of it into its hash table).  Per block the encoder writes the
+ *          smallest of the stored, the fixed and the dynamic form (with ALZ_DEFLATE_FIXED: of stored and fixed); the tokens of a block do
+ *          not depend on `flags`, so the default is never larger than fixed-only.  Code lengths are limited to 15 (the code-length code:
+ *          7) and every code set is complete, or a single 1-bit code; a block without a match has an empty distance set.
+ *          BLOCKS MEET ON BYTE BOUNDARIES: a block that is neither stored nor the stream's last is followed by an EMPTY STORED BLOCK (3
+ *          header bits, padding, 00 00 FF FF -- zlib's Z_SYNC_FLUSH), 4 to 5 bytes per block; in return no block waits for the
+ *          bits in front of it.
+ * results  OK: { ALZ_ST_OK, dst_len = bytes written, src_used = src_len }.  A stream that does not fit dst_cap: ALZ_ST_OUTPUT_CAPACITY
+ *          with dst_len 0, as alz_rlh_encode_batch; nothing of it is written.  Nothing outside [dst_off, dst_off + dst_cap) is ever
+ *          written.  alz_deflate_bound(n) = n + 5 per block always suffices (<= n + (n >> 10) + 64).  Empty input gives a valid stream of
+ *          one final block.  Inputs of 0x7FFFFF00 bytes and more are ALZ_E_UNSUPPORTED.  n == 0 is ALZ_OK.
+ * The output of a stream is a pure function of (bytes, level, flags): not of the batch around it, its alignment, the host or device form
+ * or the context mode -- there is ONE set of kernels, as for inflate.  alz_last_kernel_ms reports the device time of the call's launches.
+ *
+ * The file layer.  kind is ALZ_ZFILE_ZLIB or ALZ_ZFILE_GZIP (anything else: ALZ_E_INVALID).
+ *   zlib   78 01 / 78 5E / 78 9C / 78 DA for levels 0-1 / 2-5 / 6 / 7-9 (what zlib writes), the body, the big-endian Adler-32 of the input.
+ *   gzip   1F 8B 08 00, MTIME 0, XFL (04 at levels 0-1, 02 at level 9, 00 otherwise), OS 03, the body, CRC-32 and ISIZE (src_len mod
+ *          2^32), little-endian.
+ * alz_deflate_file_compress stages the input once, runs the body as one alz_deflate_encode_batch_device of one stream and takes the
+ *   checksum on the host; a dst_cap that is too small is ALZ_E_NOMEM (*dst_len is then 0); alz_deflate_file_bound(kind, n) suffices.
+ * alz_deflate_file_compress_batch has the contract of alz_framing_compress_batch with files[i].format as the kind: DIFFERENTIAL against
+ *   the single-file call on file i alone -- results[i] is { ALZ_OK, ALZ_ST_OK, dst_len, src_len } and the same bytes, or { that call's
+ *   code, ALZ_ST_OK, 0, 0 }; one file's failure is that file's rc, and nothing outside a file's slot is written.  One batch: one upload,
+ *   ONE alz_deflate_encode_batch_device over all bodies, one alz_checksum_batch_device per kind present over the raw inputs where they
+ *   lie, the images assembled in HBM by one range copy, one download.
+ * NOT BUILT: bit-exact concatenation of blocks, preset dictionaries, device-resident file forms, the .Extended wrappers. */
+#define ALZ_DEFLATE_FIXED 1u
+size_t alz_deflate_bound(size_t src_len);
+int alz_deflate_block_bytes(void);
+int alz_deflate_encode_batch(alz_ctx* ctx, int level, uint32_t flags, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                             const alz_stream* streams, uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_deflate_encode_batch_device(alz_ctx* ctx, int level, uint32_t flags, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                                    const alz_stream* streams, uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+size_t alz_deflate_file_bound(uint32_t kind, size_t src_len);
+int alz_deflate_file_compress(alz_ctx* ctx, uint32_t kind, int level, uint32_t flags, const uint8_t* src, size_t src_len,
+                              uint8_t* dst, size_t dst_cap, size_t* dst_len);
+int alz_deflate_file_compress_batch(alz_ctx* ctx, int level, uint32_t flags, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                                    const alz_stream* files, uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
 
 /* ---------------------------------------- XXH32 of byte ranges on the GPU
  * out[i] is XXH32 (xxHash, 32 bits: the block and content checksum of the LZ4 frame format, LZ4.Frame.cs:17-18) of the n ranges[i] with

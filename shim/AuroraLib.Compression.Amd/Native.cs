@@ -217,6 +217,21 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_framing_compress_batch(IntPtr ctx, AlzSettings* settings, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
 
+        // DEFLATE WRITTEN on the GPU: raw streams (level 0..9 with zlib's meaning, flags bit 0 = fixed Huffman codes only) and ZLib (kind 0) /
+        // GZip (kind 1) files, one or a batch (AlzStream.Format is the kind).  The library's own encoder: valid streams, not the bytes a BCL
+        // would write, so ZLib.Compress / GZip.Compress stay managed
+        [DllImport(Lib)] internal static extern UIntPtr alz_deflate_bound(UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_deflate_block_bytes();
+        [DllImport(Lib)] internal static extern int alz_deflate_encode_batch(IntPtr ctx, int level, uint flags, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_deflate_encode_batch_device(IntPtr ctx, int level, uint flags, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern UIntPtr alz_deflate_file_bound(uint kind, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_deflate_file_compress(IntPtr ctx, uint kind, int level, uint flags,
+            byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap, UIntPtr* dstLen);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_deflate_file_compress_batch(IntPtr ctx, int level, uint flags, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
+
         // decompressed size of a file of a container without a size field (PRS, LZO, FastLZ, LZ4 frame / legacy, framed Snappy), measured on the GPU
         [DllImport(Lib)] internal static extern int alz_container_measure(IntPtr ctx, uint container, void* opt,
             byte* src, UIntPtr srcLen, UIntPtr sizeLimit, UIntPtr* sizeOut, UIntPtr* srcUsed, int* status);
