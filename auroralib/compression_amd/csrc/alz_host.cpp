@@ -188,6 +188,111 @@ static alz_lz_properties effective_lz(const alz_lz_properties* p) {
     return lz;
 }
 
+// ---------------------------------------------------------------- the rules the entry points share, each written once
+// off + len <= total without wrapping (offsets are caller-supplied 64-bit values)
+static inline bool range_ok(uint64_t off, uint64_t len, uint64_t total) { return off <= total && len <= total - off; }
+// the LZSS geometries the GPU kernels take (the encoder asks for max_distance == 1 << window_bits on top)
+static inline bool lzss_on_gpu(const alz_lz_properties& lz) { return lz.window_bits >= 8 && lz.window_bits <= 16 && lz.length_bits >= 1 && lz.length_bits <= 8; }
+// an LZ4 block that continues a frame's window: its history, aux0 bytes in front of dst_off, would begin in front of the destination buffer
+static inline bool lz4_history_outside(const alz_stream& s) { return s.format == ALZ_FMT_LZ4_BLOCK && s.aux0 > s.dst_off; }
+static int refuse_lz4_history(uint32_t i, const alz_stream& s) {   // (the plan's wording: alz_plan_create, alz_decode_batch_multi)
+    return lz4_history_outside(s) ? fail(ALZ_E_INVALID, "stream %u: history %u exceeds dst_off", i, s.aux0) : ALZ_OK;
+}
+static int no_refusal(uint32_t, const alz_stream&) { return ALZ_OK; }
+
+// What a call is refused for, stream by stream, and per stream in this order: an unknown kind (`kinds` > 1: `format` must lie below it), a source
+// range outside *src_bytes, a destination range outside *dst_bytes (NULL: the family has none), then the caller's own extra(i, stream) -> int.  `what`: the entry
+// point's name in front of the batch families' texts, "" for the decoder, the encoder and the multi-GPU calls.  `ranges`: a table of byte ranges (the checksum families), with their wording.
+template <class Extra>
+static int validate_streams(const char* what, uint32_t kinds, uint32_t n, const alz_stream* streams, const size_t* src_bytes, const size_t* dst_bytes, Extra extra, bool ranges = false) {
+    const char* sep = *what ? ": " : "";
+    for (uint32_t i = 0; i < n; i++) {
+        const alz_stream& s = streams[i];
+        if (kinds > 1 && s.format >= kinds) return *what ? fail(ALZ_E_INVALID, "%s: stream %u: unknown format / kind %u", what, i, s.format) : fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, s.format);
+        if (src_bytes && !range_ok(s.src_off, s.src_len, *src_bytes))
+            return ranges ? fail(ALZ_E_INVALID, "%s: range %u exceeds src_bytes", what, i) : fail(ALZ_E_INVALID, "%s%sstream %u: source range exceeds src_bytes", what, sep, i);
+        if (dst_bytes && !range_ok(s.dst_off, s.dst_cap, *dst_bytes)) return fail(ALZ_E_INVALID, "%s%sstream %u: destination range exceeds dst_bytes", what, sep, i);
+        if (int rc = extra(i, s)) return rc;
+    }
+    return ALZ_OK;
+}
+
+// The streams of a batch grouped per kind: `index` lists the stream numbers kind after kind, a kind's streams in input order; off[k] / cnt[k] is
+// where kind k's list starts and how many it holds.  With a cost(i) the costliest streams of a kind come first (equal costs in input order).
+static const uint32_t kMaxKinds = ALZ_FMT_COUNT;
+static_assert(ALZ_RLH_COUNT <= kMaxKinds && ALZ_BITLZ_COUNT <= kMaxKinds, "the per-kind counters of group_streams");
+template <class KindOf>
+static void group_streams(uint32_t n, uint32_t kinds, KindOf kind_of, std::vector<uint32_t>& index, uint32_t* off, uint32_t* cnt) {
+    uint32_t fill[kMaxKinds] = {0};
+    index.assign(n ? n : 1, 0u);
+    for (uint32_t f = 0; f < kinds; f++) cnt[f] = 0;
+    for (uint32_t i = 0; i < n; i++) cnt[kind_of(i)]++;
+    for (uint32_t f = 0, at = 0; f < kinds; f++) { off[f] = at; at += cnt[f]; }
+    for (uint32_t i = 0; i < n; i++) { const uint32_t f = kind_of(i); index[off[f] + fill[f]++] = i; }
+}
+template <class KindOf, class Cost>
+static void group_streams(uint32_t n, uint32_t kinds, KindOf kind_of, Cost cost, std::vector<uint32_t>& index, uint32_t* off, uint32_t* cnt) {
+    group_streams(n, kinds, kind_of, index, off, cnt);
+    for (uint32_t f = 0; f < kinds; f++)
+        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
+}
+
+// One timed run on the context's stream: uploads(), ev0, launches(), ev1, downloads() -- each -> hipError_t, each skipped once one has failed --
+// and ALWAYS a wait for the stream before the return: the copies read and write the caller's tables and the caller's locals.  The first error is
+// reported under `what`; the time between the two events becomes last_kernel_ms.
+template <class Uploads, class Launches, class Downloads>
+static int launch_bracket(alz_ctx* c, const char* what, Uploads uploads, Launches launches, Downloads downloads) {
+    hipError_t e = uploads();
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) e = launches();
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = downloads();
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
+    return ALZ_OK;
+}
+
+// The context list of a multi-GPU call: no NULL, none twice
+static int check_contexts(const char* what, alz_ctx* const* ctxs, uint32_t n_ctx) {
+    for (uint32_t q = 0; q < n_ctx; q++) {
+        if (!ctxs[q]) return fail(ALZ_E_INVALID, "%s: context %u is NULL", what, q);
+        for (uint32_t r = 0; r < q; r++) if (ctxs[r] == ctxs[q]) return fail(ALZ_E_INVALID, "%s: context %u is listed twice (a context is single-threaded)", what, q);
+    }
+    return ALZ_OK;
+}
+// greedy LPT: longest job first onto the least loaded part (equal jobs, as in the metric's batches, are dealt round-robin); load[] starts at zero
+template <class Cost>
+static void lpt_deal(uint32_t n, uint32_t n_parts, Cost cost, uint32_t* part_of, uint64_t* load) {
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
+    for (uint32_t k = 0; k < n; k++) {
+        uint32_t best = 0;
+        for (uint32_t q = 1; q < n_parts; q++) if (load[q] < load[best]) best = q;
+        part_of[order[k]] = best; load[best] += cost(order[k]);
+    }
+}
+// A batch dealt out over contexts, part[i] the context of stream i: work(q, idx) -> int runs context q's share, idx its stream numbers (ascending:
+// source order; an empty share is skipped).  One host thread per context (a context is single-threaded; distinct contexts run concurrently), no collective: the shares are
+// independent.  The first share that failed is reported, with its thread's text.
+template <class Work>
+static int run_shares(alz_ctx* const* ctxs, uint32_t n_ctx, uint32_t n, const uint32_t* part, uint32_t* part_of_out, Work work) {
+    if (part_of_out) for (uint32_t i = 0; i < n; i++) part_of_out[i] = part[i];
+    std::vector<std::vector<uint32_t>> idx(n_ctx);
+    for (uint32_t i = 0; i < n; i++) idx[part[i]].push_back(i);
+    std::vector<int> rcs(n_ctx, ALZ_OK); std::vector<std::string> errs(n_ctx);
+    auto run = [&](uint32_t q) { if (!idx[q].empty() && (rcs[q] = work(q, idx[q]))) errs[q] = g_err; };
+    std::vector<std::thread> th;
+    for (uint32_t q = 1; q < n_ctx; q++) th.emplace_back(run, q);
+    run(0);
+    for (std::thread& t : th) t.join();
+    for (uint32_t q = 0; q < n_ctx; q++) if (rcs[q]) return fail(rcs[q], "context %u (device %d): %s", q, ctxs[q]->device, errs[q].c_str());
+    return ALZ_OK;
+}
+
 extern "C" {
 
 int alz_abi_version(void) { return ALZ_ABI_VERSION; }
@@ -382,32 +487,23 @@ static int plan_create(alz_ctx* c, const alz_lz_properties* props, uint32_t n, c
     if (!c || !out || (n && !streams)) return fail(ALZ_E_INVALID, "alz_plan_create: bad argument");
     HIP_TRY(hipSetDevice(c->device));
     alz_lz_properties lz = effective_lz(props);
-    std::vector<uint32_t> cnt(ALZ_FMT_COUNT, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        if (streams[i].format >= ALZ_FMT_COUNT) return fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, streams[i].format);
-        if (streams[i].format == ALZ_FMT_LZ4_BLOCK && streams[i].aux0) {   // history in front of dst_off
-            if (streams[i].aux0 > streams[i].dst_off) return fail(ALZ_E_INVALID, "stream %u: history %u exceeds dst_off", i, streams[i].aux0);
-            if ((uint64_t)streams[i].aux0 + streams[i].dst_cap > 0xFFFFFF00ull) return fail(ALZ_E_UNSUPPORTED, "stream %u: history + dst_cap exceed 4 GiB", i);
-        }
-        cnt[streams[i].format]++;
-    }
-    if (cnt[ALZ_FMT_LZSS] && (lz.window_bits < 8 || lz.window_bits > 16 || lz.length_bits < 1 || lz.length_bits > 8))
-        return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path (window_bits 8..16, length_bits 1..8)");
-    alz_plan* p = new (std::nothrow) alz_plan();
-    if (!p) return fail(ALZ_E_NOMEM, "out of host memory");
-    p->n = n; p->lz = lz;
-    std::vector<uint32_t> index(n ? n : 1);
-    uint32_t off = 0;
-    for (int f = 0; f < ALZ_FMT_COUNT; f++) { p->fmt_off[f] = off; p->fmt_cnt[f] = cnt[f]; off += cnt[f]; }
-    std::vector<uint32_t> fill(ALZ_FMT_COUNT, 0);
-    for (uint32_t i = 0; i < n; i++) { uint32_t f = streams[i].format; index[p->fmt_off[f] + fill[f]++] = i; }
+    if (int rc = validate_streams("", ALZ_FMT_COUNT, n, streams, nullptr, nullptr, [](uint32_t i, const alz_stream& s) -> int {   // (no buffer sizes here: no ranges)
+            if (int rc = refuse_lz4_history(i, s)) return rc;
+            if (s.format == ALZ_FMT_LZ4_BLOCK && s.aux0 && (uint64_t)s.aux0 + s.dst_cap > 0xFFFFFF00ull) return fail(ALZ_E_UNSUPPORTED, "stream %u: history + dst_cap exceed 4 GiB", i);
+            return ALZ_OK;
+        })) return rc;
     // Longest first inside a format's launch: workgroups are dispatched in index order and a CU holds ~24 of them, so the
     // costly streams start at once and the cheap ones fill the tail.  A stream's cost is its tokens (~ compressed bytes)
     // plus its output bytes: the 256 KiB windows of Test.bmp take 2.8 ms (flat, ratio 0.02) to 9.2 ms (photographic, ratio
     // 0.59) per 10 000; in input order that batch ran 5.8 ms per launch (tools/realistic_windows.py).
-    auto cost = [&](uint32_t i) { return 3ull * streams[i].src_len + (streams[i].decom_len ? streams[i].decom_len : streams[i].dst_cap); };
-    for (int f = 0; f < ALZ_FMT_COUNT; f++)
-        if (cnt[f] > 1) std::stable_sort(index.begin() + p->fmt_off[f], index.begin() + p->fmt_off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
+    uint32_t cnt[ALZ_FMT_COUNT], off[ALZ_FMT_COUNT]; std::vector<uint32_t> index;
+    group_streams(n, ALZ_FMT_COUNT, [&](uint32_t i) { return streams[i].format; },
+                  [&](uint32_t i) { return 3ull * streams[i].src_len + (streams[i].decom_len ? streams[i].decom_len : streams[i].dst_cap); }, index, off, cnt);
+    if (cnt[ALZ_FMT_LZSS] && !lzss_on_gpu(lz)) return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path (window_bits 8..16, length_bits 1..8)");
+    alz_plan* p = new (std::nothrow) alz_plan();
+    if (!p) return fail(ALZ_E_NOMEM, "out of host memory");
+    p->n = n; p->lz = lz;
+    memcpy(p->fmt_off, off, sizeof(off)); memcpy(p->fmt_cnt, cnt, sizeof(cnt));
     size_t nn = n ? n : 1;
     hipError_t e = hipSuccess;
     if (scratch) {
@@ -678,9 +774,6 @@ int alz_plan_results(alz_ctx* c, alz_plan* p, alz_result* results) {
 }
 
 // ---------------------------------------------------------------- host-buffer entry points
-// off + len <= total without wrapping (offsets are caller-supplied 64-bit values)
-static inline bool range_ok(uint64_t off, uint64_t len, uint64_t total) { return off <= total && len <= total - off; }
-
 static int ensure_pinned(alz_ctx* c) {
     if (c->pin_cap) return ALZ_OK;
     for (int i = 0; i < 2; i++) {
@@ -756,6 +849,15 @@ static int grow(alz_ctx* c, void** buf, size_t* cap, size_t need) {
     HIP_TRY(hipMalloc(buf, want));
     *cap = want;
     return ALZ_OK;
+}
+
+// The part every host form shares: the library's own device buffers grown to the batch (64 bytes of read slack behind each), the source staged
+static int stage_source(alz_ctx* c, const uint8_t* src, size_t src_bytes, bool has_dst, size_t dst_bytes) {
+    int rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
+    if (has_dst && (rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
+    return staged_h2d(c, c->d_src, src, src_bytes);
 }
 
 // Sparse outputs (compressed streams in worst-case-sized slots, batches with failed streams): one workgroup per stream packs
@@ -878,17 +980,11 @@ static int download_outputs(alz_ctx* c, uint32_t n, const alz_stream* streams, c
 int alz_decode_batch(alz_ctx* c, const alz_lz_properties* props, uint32_t n, const uint8_t* src_base, size_t src_bytes,
                      const alz_stream* streams, uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
     if (!c || (n && (!streams || !results))) return fail(ALZ_E_INVALID, "alz_decode_batch: bad argument");
-    for (uint32_t i = 0; i < n; i++) {
-        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
-        if (!range_ok(streams[i].dst_off, streams[i].dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "stream %u: destination range exceeds dst_bytes", i);
-        if (streams[i].format == ALZ_FMT_LZ4_BLOCK && streams[i].aux0 > streams[i].dst_off)   // (as alz_decode_batch_multi: the history lies in front of the block's output)
-            return fail(ALZ_E_INVALID, "stream %u: LZ4 history (aux0) reaches in front of the destination buffer", i);
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return rc;
-    if ((rc = staged_h2d(c, c->d_src, src_base, src_bytes))) return rc;
+    int rc;   // (the ranges of every stream first; the plan refuses an unknown format behind them)
+    if ((rc = validate_streams("", 0, n, streams, &src_bytes, &dst_bytes, [](uint32_t i, const alz_stream& s) -> int {   // (as alz_decode_batch_multi: the history lies in front of the block's output)
+            return lz4_history_outside(s) ? fail(ALZ_E_INVALID, "stream %u: LZ4 history (aux0) reaches in front of the destination buffer", i) : ALZ_OK;
+        }))) return rc;
+    if ((rc = stage_source(c, src_base, src_bytes, true, dst_bytes))) return rc;
     for (uint32_t i = 0; i < n; i++)   // LZ4 blocks that continue a frame's window: their history has to be in HBM too
         if (streams[i].format == ALZ_FMT_LZ4_BLOCK && streams[i].aux0 && streams[i].aux0 <= streams[i].dst_off)
             HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_dst + streams[i].dst_off - streams[i].aux0, dst_base + streams[i].dst_off - streams[i].aux0,
@@ -910,13 +1006,11 @@ int alz_decode_batch(alz_ctx* c, const alz_lz_properties* props, uint32_t n, con
             if (results[0].dst_len <= spec) { if (results[0].dst_len) memcpy(dst_base + streams[0].dst_off, c->pin[0], results[0].dst_len); }
             else rc = download_outputs(c, n, streams, results, dst_base, false);         // (an overshoot of the declared size: E4)
         }
-        if (rc) (void)hipStreamSynchronize(c->stream);       // (an error path: the plan's pageable upload sources may still be queued)
-        alz_plan_destroy(c, p);
-        return rc;
+    } else {
+        if (!rc) rc = alz_plan_results(c, p, results);
+        if (!rc) rc = download_outputs(c, n, streams, results, dst_base, false);   // copy back only what each stream produced
     }
-    if (!rc) rc = alz_plan_results(c, p, results);
-    if (!rc) rc = download_outputs(c, n, streams, results, dst_base, false);   // copy back only what each stream produced
-    if (rc) (void)hipStreamSynchronize(c->stream);
+    if (rc) (void)hipStreamSynchronize(c->stream);           // (an error path: the plan's pageable upload sources may still be queued)
     alz_plan_destroy(c, p);
     return rc;
 }
@@ -943,51 +1037,28 @@ enum batch_download {
 };
 // the arguments every one of these entry points takes; src / dst are device pointers in a device form (dst NULL where there is none)
 struct batch_args { uint32_t n; const uint8_t* src; size_t src_bytes; const alz_stream* streams; uint8_t* dst; size_t dst_bytes; alz_result* results; };
-static const uint32_t kMaxKinds = ALZ_FMT_COUNT;
-static_assert(ALZ_RLH_COUNT <= kMaxKinds && ALZ_BITLZ_COUNT <= kMaxKinds, "the per-kind counters of grouped_core");
-
-// what every family refuses a call for: an unknown kind, a source or (where there is one) a destination range outside the stated sizes
-static int validate_streams(const char* what, uint32_t kinds, bool has_dst, const batch_args& a) {
-    for (uint32_t i = 0; i < a.n; i++) {
-        const alz_stream& s = a.streams[i];
-        if (kinds > 1 && s.format >= kinds) return fail(ALZ_E_INVALID, "%s: stream %u: unknown format / kind %u", what, i, s.format);
-        if (!range_ok(s.src_off, s.src_len, a.src_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: source range exceeds src_bytes", what, i);
-        if (has_dst && !range_ok(s.dst_off, s.dst_cap, a.dst_bytes)) return fail(ALZ_E_INVALID, "%s: stream %u: destination range exceeds dst_bytes", what, i);
-    }
-    return ALZ_OK;
-}
 static int no_refusals() { return ALZ_OK; }
 
 // n > 0 validated streams: group, sort, upload the tables, one launch(kind, d_streams, d_index of the kind, count, d_results) -> hipError_t per
 // kind present between the two events, results to the host, wait.
 template <class Launch>
 static int grouped_core(alz_ctx* c, const char* what, uint32_t kinds, uint32_t n, const alz_stream* streams, alz_result* results, Launch launch) {
-    uint32_t cnt[kMaxKinds] = {0}, off[kMaxKinds] = {0}, fill[kMaxKinds] = {0};
-    auto kind_of = [&](uint32_t i) { return kinds > 1 ? streams[i].format : 0u; };
-    for (uint32_t i = 0; i < n; i++) cnt[kind_of(i)]++;
+    uint32_t cnt[kMaxKinds], off[kMaxKinds]; std::vector<uint32_t> index;
     c->last_kernel_ms = 0.f;
     HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint32_t> index(n);
-    for (uint32_t f = 1; f < kinds; f++) off[f] = off[f - 1] + cnt[f - 1];
-    for (uint32_t i = 0; i < n; i++) { const uint32_t f = kind_of(i); index[off[f] + fill[f]++] = i; }
-    for (uint32_t f = 0; f < kinds; f++)     // a stream's cost is its tokens: the compressed bytes
-        if (cnt[f] > 1) std::stable_sort(index.begin() + off[f], index.begin() + off[f] + cnt[f], [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
+    group_streams(n, kinds, [&](uint32_t i) { return kinds > 1 ? streams[i].format : 0u; },
+                  [&](uint32_t i) { return streams[i].src_len; }, index, off, cnt);     // a stream's cost is its tokens: the compressed bytes
     plan_tables t;
     if (int rc = carve_plan_scratch(c, n, &t)) return rc;
-    hipError_t e = hipMemcpyAsync(t.streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t.index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t.results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    for (uint32_t f = 0; f < kinds && e == hipSuccess; f++)
-        if (cnt[f]) e = launch(f, t.streams, t.index + off[f], cnt[f], t.results);
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, t.results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's tables and `index`)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
-    return ALZ_OK;
+    return launch_bracket(c, what,
+        [&] {   // (the uploads read the caller's table and `index`: the bracket waits for them)
+            hipError_t e = hipMemcpyAsync(t.streams, streams, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(t.index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(t.results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+            return e;
+        },
+        [&] { hipError_t e = hipSuccess; for (uint32_t f = 0; f < kinds && e == hipSuccess; f++) if (cnt[f]) e = launch(f, t.streams, t.index + off[f], cnt[f], t.results); return e; },
+        [&] { return hipMemcpyAsync(results, t.results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream); });
 }
 
 // One entry point, host or device form: the argument check, the empty batch, validation (once, before anything is allocated or copied: a
@@ -1001,15 +1072,11 @@ static int batch_call(alz_ctx* c, const char* what, uint32_t kinds, batch_downlo
     if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
     if (a.n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
     int rc;
-    if ((rc = validate_streams(what, kinds, has_dst, a))) return rc;
+    if ((rc = validate_streams(what, kinds, a.n, a.streams, &a.src_bytes, has_dst ? &a.dst_bytes : nullptr, no_refusal))) return rc;
     if ((rc = refuse())) return rc;
-    const uint8_t* d_src = a.src;
-    uint8_t* d_dst = a.dst;
+    const uint8_t* d_src = a.src; uint8_t* d_dst = a.dst;
     if (!device) {
-        HIP_TRY(hipSetDevice(c->device));
-        if ((rc = grow(c, &c->d_src, &c->d_src_cap, a.src_bytes + 64))) return rc;
-        if (has_dst && (rc = grow(c, &c->d_dst, &c->d_dst_cap, a.dst_bytes + 64))) return rc;
-        if ((rc = staged_h2d(c, c->d_src, a.src, a.src_bytes))) return rc;
+        if ((rc = stage_source(c, a.src, a.src_bytes, has_dst, a.dst_bytes))) return rc;
         d_src = (const uint8_t*)c->d_src;
         d_dst = has_dst ? (uint8_t*)c->d_dst : nullptr;
     }
@@ -1019,6 +1086,32 @@ static int batch_call(alz_ctx* c, const char* what, uint32_t kinds, batch_downlo
     if (rc || device || !has_dst) return rc;
     return download_outputs(c, a.n, a.streams, a.results, a.dst, rule == DL_ONLY_OK, rule == DL_CRILAYLA_TOP);
 }
+
+// The core of the families over byte ranges (the checksums and XXH32, below), host or device form: the argument check, the empty batch, validation, the
+// host form's staging, the tables -- ranges | the family's own | one word per range -- carved out of the plan scratch, one timed launch, the words
+// back to the host.  check(i, range) -> int: the family's refusal per range, behind the range's own; own_bytes() -> size_t: the bytes of its tables
+// (asked once the ranges are valid); upload(d_own) and launch(d_src, d_ranges, d_own, d_out) -> hipError_t.
+struct range_args { uint32_t n; const uint8_t* src; size_t src_bytes; const alz_stream* ranges; uint32_t* out; };
+template <class Check, class OwnBytes, class Upload, class Launch>
+static int range_call(alz_ctx* c, const char* what, bool device, const range_args& a, Check check, OwnBytes own_bytes, Upload upload, Launch launch) {
+    const bool missing = device ? a.n && (!a.ranges || !a.out || !a.src) : (a.n && (!a.ranges || !a.out)) || (a.src_bytes && !a.src);
+    if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
+    if (a.n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
+    int rc;
+    if ((rc = validate_streams(what, 0, a.n, a.ranges, &a.src_bytes, nullptr, check, true))) return rc;
+    c->last_kernel_ms = 0.f;
+    if (device) HIP_TRY(hipSetDevice(c->device));
+    else if ((rc = stage_source(c, a.src, a.src_bytes, false, 0))) return rc;
+    const uint8_t* d_src = device ? a.src : (const uint8_t*)c->d_src;
+    const size_t r = ((size_t)a.n * sizeof(alz_stream) + 255) & ~(size_t)255, own = own_bytes();
+    if ((rc = grow(c, &c->d_plan, &c->d_plan_cap, r + own + (size_t)a.n * sizeof(uint32_t)))) return rc;
+    alz_stream* d_ranges = (alz_stream*)c->d_plan;
+    uint8_t* d_own = (uint8_t*)c->d_plan + r; uint32_t* d_out = (uint32_t*)(d_own + own);
+    return launch_bracket(c, what,   // (the uploads read the caller's table and the family's: the bracket waits for them)
+        [&] { const hipError_t e = hipMemcpyAsync(d_ranges, a.ranges, (size_t)a.n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream); return e == hipSuccess ? upload(d_own) : e; },
+        [&] { return launch(d_src, d_ranges, d_own, d_out); },
+        [&] { return hipMemcpyAsync(a.out, d_out, (size_t)a.n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream); });
+}
 }   // extern "C++"
 
 // ---------------------------------------------------------------- measure: decoded sizes without decoding (alz_measure.hip); kinds: alz_format
@@ -1026,8 +1119,7 @@ static int measure_batch(alz_ctx* c, bool device, const alz_lz_properties* props
     const alz_lz_properties lz = effective_lz(props);
     return batch_call(c, "alz_measure_batch", ALZ_FMT_COUNT, DL_NO_DST, device, a,
         [&]() -> int {
-            if (lz.window_bits >= 8 && lz.window_bits <= 16 && lz.length_bits >= 1 && lz.length_bits <= 8) return ALZ_OK;
-            for (uint32_t i = 0; i < a.n; i++)
+            for (uint32_t i = 0; i < a.n && !lzss_on_gpu(lz); i++)
                 if (a.streams[i].format == ALZ_FMT_LZSS) return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path (window_bits 8..16, length_bits 1..8)");
             return ALZ_OK;
         },
@@ -1207,58 +1299,34 @@ int alz_debug_checksum_chunk(uint32_t bytes) {   // bytes of a range one wavefro
     if (bytes && bytes % 1024u == 0 && bytes <= ALZ_CHECKSUM_CHUNK_MAX) g_checksum_chunk = bytes;
     return (int)g_checksum_chunk;
 }
-// kind: an alz_checksum_kind, or ALZ_CK_CRC32C (alz_checksum.h) from the alz_crc32c_* entry points below
-static int checksum_batch(alz_ctx* c, bool device, uint32_t kind, uint32_t n, const uint8_t* src, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
+// kind: an alz_checksum_kind, or ALZ_CK_CRC32C (alz_checksum.h) from the alz_crc32c_* entry points below.  Its own tables: first[] (n + 1 words: where
+// a range's chunks start) | one partial sum per chunk
+static int checksum_batch(alz_ctx* c, bool device, uint32_t kind, const range_args& a) {
     const bool crc32c = kind == ALZ_CK_CRC32C;
     const char* what = crc32c ? (device ? "alz_crc32c_batch_device" : "alz_crc32c_batch") : (device ? "alz_checksum_batch_device" : "alz_checksum_batch");
-    const bool missing = device ? n && (!ranges || !out || !src) : (n && (!ranges || !out)) || (src_bytes && !src);
-    if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
-    if (n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
     const uint32_t chunk = g_checksum_chunk;
-    std::vector<uint32_t> first((size_t)n + 1);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (!range_ok(ranges[i].src_off, ranges[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: range %u exceeds src_bytes", what, i);
-        first[i] = (uint32_t)total;
-        total += ((uint64_t)ranges[i].src_len + chunk - 1) / chunk;
-        if (total > 0x7FFFFFFFull) return fail(ALZ_E_UNSUPPORTED, "%s: more than 2^31 chunks of %u bytes", what, chunk);
-    }
-    first[n] = (uint32_t)total;
-    c->last_kernel_ms = 0.f;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    const uint8_t* d_src = src;
-    if (!device) {
-        if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-        if ((rc = staged_h2d(c, c->d_src, src, src_bytes))) return rc;
-        d_src = (const uint8_t*)c->d_src;
-    }
-    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255, b = (((size_t)n + 1) * sizeof(uint32_t) + 255) & ~(size_t)255,
-                 p = ((size_t)total * sizeof(uint32_t) + 255) & ~(size_t)255;
-    if ((rc = grow(c, &c->d_plan, &c->d_plan_cap, a + b + p + (size_t)n * sizeof(uint32_t)))) return rc;
-    alz_stream* d_ranges = (alz_stream*)c->d_plan;
-    uint32_t* d_first = (uint32_t*)((uint8_t*)c->d_plan + a), *d_partial = (uint32_t*)((uint8_t*)c->d_plan + a + b), *d_out = (uint32_t*)((uint8_t*)c->d_plan + a + b + p);
-    hipError_t e = hipMemcpyAsync(d_ranges, ranges, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_first, first.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess) e = alz_launch_checksum(kind, c->stream, d_src, d_ranges, n, d_first, (uint32_t)total, chunk, d_partial, d_out);
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the uploads read the caller's table and `first`)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
-    return ALZ_OK;
+    std::vector<uint32_t> first; uint64_t total = 0;
+    const size_t b = (((size_t)a.n + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+    return range_call(c, what, device, a,
+        [&](uint32_t i, const alz_stream& r) -> int {
+            if (i == 0) first.resize((size_t)a.n + 1);          // (here, not above: the arguments have been checked)
+            first[i] = (uint32_t)total; total += ((uint64_t)r.src_len + chunk - 1) / chunk;
+            return total > 0x7FFFFFFFull ? fail(ALZ_E_UNSUPPORTED, "%s: more than 2^31 chunks of %u bytes", what, chunk) : ALZ_OK;
+        },
+        [&] { first[a.n] = (uint32_t)total; return b + (((size_t)total * sizeof(uint32_t) + 255) & ~(size_t)255); },
+        [&](uint8_t* d_own) { return hipMemcpyAsync(d_own, first.data(), ((size_t)a.n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream); },
+        [&](const uint8_t* d_src, const alz_stream* d_ranges, uint8_t* d_own, uint32_t* d_out) {
+            return alz_launch_checksum(kind, c->stream, d_src, d_ranges, a.n, (const uint32_t*)d_own, (uint32_t)total, chunk, (uint32_t*)(d_own + b), d_out);
+        });
 }
 // (the public kinds end at CRC-32: the launcher's third kind has entry points of its own, and 2 stays an unknown kind here)
 int alz_checksum_batch(alz_ctx* c, uint32_t kind, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
     if (kind > ALZ_CK_CRC32) return fail(ALZ_E_INVALID, "alz_checksum_batch: unknown kind %u", kind);
-    return checksum_batch(c, false, kind, n, src_base, src_bytes, ranges, out);
+    return checksum_batch(c, false, kind, {n, src_base, src_bytes, ranges, out});
 }
 int alz_checksum_batch_device(alz_ctx* c, uint32_t kind, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
     if (kind > ALZ_CK_CRC32) return fail(ALZ_E_INVALID, "alz_checksum_batch_device: unknown kind %u", kind);
-    return checksum_batch(c, true, kind, n, d_src_base, src_bytes, ranges, out);
+    return checksum_batch(c, true, kind, {n, d_src_base, src_bytes, ranges, out});
 }
 // the checksum of A || B from those of A and of B: pure host code, the arithmetic of the fold kernel (alz_checksum.h).  An unknown kind gives 0.
 uint32_t alz_checksum_combine(uint32_t kind, uint32_t a, uint32_t b, uint64_t len_b) {
@@ -1268,10 +1336,10 @@ uint32_t alz_checksum_combine(uint32_t kind, uint32_t a, uint32_t b, uint64_t le
 
 // CRC-32C (Castagnoli; the checksum of the framed Snappy container, before its mask): the same batch over the other polynomial
 int alz_crc32c_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
-    return checksum_batch(c, false, ALZ_CK_CRC32C, n, src_base, src_bytes, ranges, out);
+    return checksum_batch(c, false, ALZ_CK_CRC32C, {n, src_base, src_bytes, ranges, out});
 }
 int alz_crc32c_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
-    return checksum_batch(c, true, ALZ_CK_CRC32C, n, d_src_base, src_bytes, ranges, out);
+    return checksum_batch(c, true, ALZ_CK_CRC32C, {n, d_src_base, src_bytes, ranges, out});
 }
 uint32_t alz_crc32c_combine(uint32_t a, uint32_t b, uint64_t len_b) {
     return alz_checksum_join(ALZ_CK_CRC32C, a, b, len_b, alz_crc_xpow_bytes<ALZ_CRC32C_POLY>(len_b));
@@ -1279,43 +1347,15 @@ uint32_t alz_crc32c_combine(uint32_t a, uint32_t b, uint64_t len_b) {
 
 // ---------------------------------------------------------------- XXH32 of byte ranges (alz_xxh32.hip): the argument rules of the checksum family
 // One launch, four lanes per range.  The tables (ranges, results) live in the context's plan scratch; the device writes nothing but them.
-static int xxh32_batch(alz_ctx* c, bool device, uint32_t seed, uint32_t n, const uint8_t* src, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
-    const char* what = device ? "alz_xxh32_batch_device" : "alz_xxh32_batch";
-    const bool missing = device ? n && (!ranges || !out || !src) : (n && (!ranges || !out)) || (src_bytes && !src);
-    if (!c || missing) return fail(ALZ_E_INVALID, "%s: bad argument", what);
-    if (n == 0) { c->last_kernel_ms = 0.f; return ALZ_OK; }
-    for (uint32_t i = 0; i < n; i++)
-        if (!range_ok(ranges[i].src_off, ranges[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "%s: range %u exceeds src_bytes", what, i);
-    c->last_kernel_ms = 0.f;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    const uint8_t* d_src = src;
-    if (!device) {
-        if ((rc = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return rc;
-        if ((rc = staged_h2d(c, c->d_src, src, src_bytes))) return rc;
-        d_src = (const uint8_t*)c->d_src;
-    }
-    const size_t a = ((size_t)n * sizeof(alz_stream) + 255) & ~(size_t)255;
-    if ((rc = grow(c, &c->d_plan, &c->d_plan_cap, a + (size_t)n * sizeof(uint32_t)))) return rc;
-    alz_stream* d_ranges = (alz_stream*)c->d_plan;
-    uint32_t* d_out = (uint32_t*)((uint8_t*)c->d_plan + a);
-    hipError_t e = hipMemcpyAsync(d_ranges, ranges, (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess) e = alz_launch_xxh32(c->stream, seed, d_src, d_ranges, n, d_out);
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);             // (always: the upload reads the caller's table)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ALZ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms;
-    return ALZ_OK;
+static int xxh32_batch(alz_ctx* c, bool device, uint32_t seed, const range_args& a) {
+    return range_call(c, device ? "alz_xxh32_batch_device" : "alz_xxh32_batch", device, a, no_refusal, [] { return (size_t)0; }, [](uint8_t*) { return hipSuccess; },
+        [&](const uint8_t* d_src, const alz_stream* d_ranges, uint8_t*, uint32_t* d_out) { return alz_launch_xxh32(c->stream, seed, d_src, d_ranges, a.n, d_out); });
 }
 int alz_xxh32_batch(alz_ctx* c, uint32_t seed, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
-    return xxh32_batch(c, false, seed, n, src_base, src_bytes, ranges, out);
+    return xxh32_batch(c, false, seed, {n, src_base, src_bytes, ranges, out});
 }
 int alz_xxh32_batch_device(alz_ctx* c, uint32_t seed, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* ranges, uint32_t* out) {
-    return xxh32_batch(c, true, seed, n, d_src_base, src_bytes, ranges, out);
+    return xxh32_batch(c, true, seed, {n, d_src_base, src_bytes, ranges, out});
 }
 // The range copy of the batched LZ4 / Snappy file layer (alz_xxh32.h): HBM to HBM, one launch for the whole list
 int alz_host_range_copy(alz_ctx* c, uint32_t n, alz_copy_range* ranges, const uint8_t* d_src, size_t src_bytes, uint8_t* d_dst, size_t dst_bytes) {
@@ -1361,9 +1401,8 @@ struct EncScratch {
 extern "C++" int alz_encode_seg_spec_format(int fmt);
 static void release_scratch(alz_ctx* c) {
     for (int k = 0; k < alz_ctx::ENC_SLOTS; k++) { if (c->enc_buf[k]) (void)hipFree(c->enc_buf[k]); c->enc_buf[k] = nullptr; c->enc_cap[k] = 0; }
-    void** bufs[] = {&c->d_src, &c->d_dst, &c->d_items, &c->d_pack, &c->d_plan, &c->d_bigbuf};
-    size_t* caps[] = {&c->d_src_cap, &c->d_dst_cap, &c->d_items_cap, &c->d_pack_cap, &c->d_plan_cap, &c->d_bigbuf_cap};
-    for (int i = 0; i < 6; i++) { if (*bufs[i]) (void)hipFree(*bufs[i]); *bufs[i] = nullptr; *caps[i] = 0; }
+    const struct { void** buf; size_t* cap; } own[] = {{&c->d_src, &c->d_src_cap}, {&c->d_dst, &c->d_dst_cap}, {&c->d_items, &c->d_items_cap}, {&c->d_pack, &c->d_pack_cap}, {&c->d_plan, &c->d_plan_cap}, {&c->d_bigbuf, &c->d_bigbuf_cap}};
+    for (const auto& o : own) { if (*o.buf) (void)hipFree(*o.buf); *o.buf = nullptr; *o.cap = 0; }
 }
 int alz_ctx_release_scratch(alz_ctx* c) {
     if (!c) return fail(ALZ_E_INVALID, "ctx is NULL");
@@ -1384,37 +1423,62 @@ static inline bool fastlz_level2(const alz_settings& st, uint32_t src_len) { ret
 // buffer need not: the finder's look-ahead loads read up to 32 bytes past a stream's end, so the streams that end inside the last 64
 // bytes of the caller's buffer are copied into scratch with room behind them and searched there (their descriptors -- the device copy
 // only -- point at the copy; offsets are differences of device addresses).
-static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_settings* settings, uint32_t n, size_t src_bytes, const alz_stream* streams,
-                       size_t dst_bytes, alz_result* results, alz_encode_aux* aux, const std::function<int(const void*&, void*&)>& upload,
-                       bool src_has_slack = true, bool no_big = false) {
-    const void* d_src_base = nullptr; void* d_dst_base = nullptr;
+// encode_core runs the stages below in turn; what one stage works out for the next travels in these three structs.
+namespace {
+// One format slot of a batch: ALZ_FMT_COUNT slots for the formats and a last one for FastLZ level 2, which has a geometry and a launch of its own
+struct enc_slot {
+    unsigned char* geom = nullptr;                 // alz_encode_geometry's bytes (all zero while the batch has no stream of the slot)
+    uint32_t seg_len = 0, seg_kmax = 0;            // the segmented parse + emit (alz_encode_seg.h) takes the slot's launch: segment length and segments per buffer
+    bool min_table = false, narrows = false, match = false, mask = false;   // the scratch the slot's kernels need: the min-length table's links, the narrowed links, the match array, the start mask
+};
+struct enc_batch {
+    alz_settings st; alz_lz_properties lz;
+    uint32_t cnt[ALZ_FMT_COUNT], off[ALZ_FMT_COUNT];   // per format; a FastLZ list holds the level-1 streams first, then the n_fastlz2 level-2 ones
+    std::vector<uint32_t> index; std::vector<uint64_t> pos_off;   // pos_off: where a stream's positions start in the per-position scratch arrays, `total` positions in all
+    uint64_t total = 0; uint32_t max_len = 0, n_fastlz2 = 0;
+    std::vector<unsigned char> geom_bytes; enc_slot slot[ALZ_FMT_COUNT + 1]; size_t seg_bytes = 0;
+    bool any(bool enc_slot::*need) const { for (const enc_slot& s : slot) if (s.*need) return true; return false; }
+};
+// The device side of one call, shared by its two paths: the buffers `upload` hands over (once), and the streams relocated out of a caller's tail
+struct enc_io {
+    const std::function<int(const void*&, void*&)>& upload; size_t src_bytes; bool src_has_slack; phase_timer tm;
+    const void* d_src = nullptr; void* d_dst = nullptr; bool staged = false;
+    std::vector<alz_stream> moved; bool tails_done = false;      // the stream table with the relocated streams' src_off patched (empty: nothing moved)
+    int stage() { if (staged) return ALZ_OK; const int rc = upload(d_src, d_dst); staged = rc == ALZ_OK; tm.mark("upload"); return rc; }
+};
+}
+// Stage 1: the settings, then the streams
+static int enc_validate(const alz_settings* settings, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes, alz_settings* out) {
     alz_settings st; if (settings) st = *settings; else { st.quality = 8; st.max_window_bits = 0; st.strategy = 0; st.min_distance = 0; }
     if (st.quality < 0 || st.quality > 15) return fail(ALZ_E_INVALID, "quality %d outside 0..15 (CompressionSettings.cs:38-50)", st.quality);
     if (st.max_window_bits < 0 || st.max_window_bits > 24) return fail(ALZ_E_INVALID, "max_window_bits %d outside 0..24", st.max_window_bits);
-    alz_lz_properties lz = effective_lz(props);
-    phase_timer tm("alz_encode_batch");
-    std::vector<uint32_t> cnt(ALZ_FMT_COUNT, 0);
-    std::vector<uint64_t> pos_off(n);
-    uint64_t total = 0; uint32_t max_len = 0, n_fastlz2 = 0;
+    *out = st;
+    return validate_streams("", ALZ_FMT_COUNT, n, streams, &src_bytes, &dst_bytes, [](uint32_t i, const alz_stream& s) -> int {
+        return s.src_len > 0x7FFFFF00u ? fail(ALZ_E_UNSUPPORTED, "stream %u: inputs above 2 GiB are not supported", i) : ALZ_OK;
+    });
+}
+// Stage 2: the streams grouped per format, their places in the per-position arrays, and the geometry of every format slot present
+static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams, enc_batch* b) {
+    const alz_settings& st = b->st;
+    group_streams(n, ALZ_FMT_COUNT, [&](uint32_t i) { return streams[i].format; }, b->index, b->off, b->cnt);
+    const uint32_t* cnt = b->cnt;
+    b->pos_off.resize(n);
     for (uint32_t i = 0; i < n; i++) {
-        if (streams[i].format >= ALZ_FMT_COUNT) return fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, streams[i].format);
-        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
-        if (!range_ok(streams[i].dst_off, streams[i].dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "stream %u: destination range exceeds dst_bytes", i);
-        if (streams[i].src_len > 0x7FFFFF00u) return fail(ALZ_E_UNSUPPORTED, "stream %u: inputs above 2 GiB are not supported", i);
-        cnt[streams[i].format]++;
-        if (streams[i].format == ALZ_FMT_FASTLZ && fastlz_level2(st, streams[i].src_len)) n_fastlz2++;
-        pos_off[i] = total; total += ((uint64_t)streams[i].src_len + 16 + 63) & ~63ull;   // 64-aligned: one start-mask word per 64 positions
-        if (streams[i].src_len > max_len) max_len = streams[i].src_len;
+        if (streams[i].format == ALZ_FMT_FASTLZ && fastlz_level2(st, streams[i].src_len)) b->n_fastlz2++;
+        b->pos_off[i] = b->total; b->total += ((uint64_t)streams[i].src_len + 16 + 63) & ~63ull;   // 64-aligned: one start-mask word per 64 positions
+        if (streams[i].src_len > b->max_len) b->max_len = streams[i].src_len;
     }
-    if (cnt[ALZ_FMT_LZSS] && (lz.window_bits < 8 || lz.window_bits > 16 || lz.length_bits < 1 || lz.length_bits > 8 || lz.max_distance != (1u << lz.window_bits)))
-        return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path");
-    std::vector<unsigned char> geom((ALZ_FMT_COUNT + 1) * alz_encode_geom_size());   // last slot: FastLZ level 2
-    bool any_min = false, any_match = false, any_mask = false, any_narrow = false;
-    std::vector<uint32_t> seg_len(ALZ_FMT_COUNT + 1, 0), seg_kmax(ALZ_FMT_COUNT + 1, 0); size_t seg_bytes = 0;
+    if (b->n_fastlz2)                                        // FastLZ: the level-1 streams first, then the level-2 ones (own geometry, own launch)
+        std::stable_partition(b->index.begin() + b->off[ALZ_FMT_FASTLZ], b->index.begin() + b->off[ALZ_FMT_FASTLZ] + cnt[ALZ_FMT_FASTLZ],
+                              [&](uint32_t i) { return !fastlz_level2(st, streams[i].src_len); });
+    const uint32_t n_fastlz2 = b->n_fastlz2, max_len = b->max_len;
+    if (cnt[ALZ_FMT_LZSS] && (!lzss_on_gpu(b->lz) || b->lz.max_distance != (1u << b->lz.window_bits))) return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path");
+    b->geom_bytes.resize((ALZ_FMT_COUNT + 1) * alz_encode_geom_size());   // (zeros) last slot: FastLZ level 2
     for (int f = 0; f <= ALZ_FMT_COUNT; f++) {
+        enc_slot& s = b->slot[f];
+        void* g = s.geom = b->geom_bytes.data() + f * alz_encode_geom_size();
         const bool lvl2 = f == ALZ_FMT_COUNT;
         if (lvl2 ? !n_fastlz2 : !(cnt[f] - (f == ALZ_FMT_FASTLZ ? n_fastlz2 : 0u))) continue;
-        void* g = geom.data() + f * alz_encode_geom_size();
         alz_settings sf = st;
         if (st.max_window_bits != 0 && f != ALZ_FMT_FASTLZ && !lvl2) {
             // CompressionSettings.MaxWindowBits can only WIDEN the finder (windowsBits = max(.., maxWindowBits), maxDistance = max(.., 1 <<
@@ -1423,126 +1487,132 @@ static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_set
             // level 2 is selected by it, aside): the caller's own encoder.
             sf.max_window_bits = 0;
             int wb0 = 0;
-            if (!alz_encode_geometry(f, &lz, &sf, g, &wb0, 0)) return fail(ALZ_E_UNSUPPORTED, "format %d: geometry not supported by the GPU encoder", f);
+            if (!alz_encode_geometry(f, &b->lz, &sf, g, &wb0, 0)) return fail(ALZ_E_UNSUPPORTED, "format %d: geometry not supported by the GPU encoder", f);
             if (st.max_window_bits > wb0 || (1ll << st.max_window_bits) > (long long)alz_encode_geom_max_dist(g))
                 return fail(ALZ_E_UNSUPPORTED, "format %d: CompressionSettings.MaxWindowBits %d is beyond the format's window (%d bits, distances up to %d): "
                             "the managed finder would return distances the format cannot store", f, st.max_window_bits, wb0, alz_encode_geom_max_dist(g));
         }
-        if (!alz_encode_geometry(lvl2 ? ALZ_FMT_FASTLZ : f, &lz, &sf, g, nullptr, lvl2 ? 1 : 0))
+        if (!alz_encode_geometry(lvl2 ? ALZ_FMT_FASTLZ : f, &b->lz, &sf, g, nullptr, lvl2 ? 1 : 0))
             return fail(ALZ_E_UNSUPPORTED, "format %d: geometry not supported by the GPU encoder", lvl2 ? ALZ_FMT_FASTLZ : f);
-        any_min = any_min || alz_encode_geom_min_table(g);
-        any_narrow = any_narrow || alz_encode_geom_narrows(g);
-        any_match = any_match || alz_encode_geom_needs_match(lvl2 ? ALZ_FMT_FASTLZ : f, g);
-        any_mask = any_mask || alz_encode_format_needs_mask(lvl2 ? ALZ_FMT_FASTLZ : f);
+        s.min_table = alz_encode_geom_min_table(g);
+        s.narrows = alz_encode_geom_narrows(g);
+        s.match = alz_encode_geom_needs_match(lvl2 ? ALZ_FMT_FASTLZ : f, g);
+        s.mask = alz_encode_format_needs_mask(lvl2 ? ALZ_FMT_FASTLZ : f);
         // a batch of few buffers of a flag-bit format: parse and emitter over segments (alz_encode_seg.h) -- behind kernel B and the roles walk
         uint32_t seg_hist = 0;
-        if (!lvl2 && !c->exact && c->variant == 0 && alz_encode_segmented(f, g, cnt[f], max_len, c->seg_max_streams, &seg_len[f], &seg_kmax[f], &seg_hist)) {
-            any_match = any_mask = true;
+        if (!lvl2 && !c->exact && c->variant == 0 && alz_encode_segmented(f, g, cnt[f], max_len, c->seg_max_streams, &s.seg_len, &s.seg_kmax, &seg_hist)) {
+            s.match = s.mask = true;
             size_t ab = 0; (void)alz_encode_aseg(g, cnt[f], max_len, nullptr, nullptr, nullptr, nullptr, &ab);
-            const size_t b = ((alz_encode_seg_bytes(cnt[f], seg_kmax[f], seg_hist) + 255) & ~(size_t)255) + ab; if (b > seg_bytes) seg_bytes = b;
+            const size_t sb = ((alz_encode_seg_bytes(cnt[f], s.seg_kmax, seg_hist) + 255) & ~(size_t)255) + ab; if (sb > b->seg_bytes) b->seg_bytes = sb;
         }
     }
-    // ---- a handful of big streams: each of them on the whole GPU (alz_encode_big.h).  A stream the path declines (too many positions that
-    // need an exact second search) sends the whole call through the batch pipeline below.
-    // As in the decoder (plan_create): one after the other on the whole GPU while that beats side by side with a workgroup + a wavefront
-    // each -- measured at quality 0-8 on Test.bmp (tools/mid_batch_encode.py): ~0.10 ms + 0.10 ms per MiB on the whole GPU, ~22 ms per MiB of the LONGEST buffer side by side.
-    if (!no_big && n <= ALZ_BIG_MAX_STREAMS && c->big_min != 0xFFFFFFFFu && !c->exact && c->variant == 0) {
-        // (from 8 KiB on -- not the decoder's 24 KiB: ONE buffer of 8 KiB takes 0.08 ms of kernels this way and 0.22 through the batch pipeline, of
-        // 64 KiB 0.10 against 1.6, tools/single_encode_sizes.py; a threshold the caller has set below that is the caller's)
-        const uint32_t enc_min = c->big_min < 8192u ? c->big_min : 8192u;
-        bool all = true; size_t sb = 0;
-        double t_big = 0, t_side = 0;
-        const bool q0 = st.quality == 0;                                      // (no narrowing behind kernel A, one candidate per position in kernel B: 8 x 1 MB 0.99 one by one / 0.68)
-        for (uint32_t i = 0; all && i < n; i++) {
-            const void* g = geom.data() + streams[i].format * alz_encode_geom_size();
-            all = streams[i].format != ALZ_FMT_FASTLZ && alz_encode_big_eligible((int)streams[i].format, g, &streams[i], enc_min);
-            if (all) { const size_t b = alz_encode_big_scratch_bytes((int)streams[i].format, g, &streams[i]); if (b > sb) sb = b; }
-            const double mib = streams[i].src_len / 1048576.0;
-            // (round 6, 2-32 x 1 MiB of Test.bmp one by one, ms per MiB: LZ4 blocks / LZO -- 64 KiB windows -- 0.32 at quality 0 and 0.80 at quality 8, LZ11 / LZ40 0.21 / 0.37)
-            const bool wide = alz_encode_geom_max_dist(g) > 8192, l11 = streams[i].format == ALZ_FMT_LZ11 || streams[i].format == ALZ_FMT_LZ40;
-            const double rate = wide ? (q0 ? 0.22 : 0.70) : (l11 && !q0) ? 0.27 : 0.10;
-            t_big += 0.10 + rate * mib; if (22.0 * mib > t_side) t_side = 22.0 * mib;
-        }
-        // (side by side is no longer one wavefront per buffer where the segmented parse + emit takes the launch, alz_encode_seg.h: what is left of the longest
-        // buffer's serial time is kernel A -- over segments too, for these few buffers: ~0.9 ms per MiB; one workgroup per buffer where that does not apply: 2.2 --
-        // + ~0.14 ms of small kernels per format + ~0.08 ms per MiB of the whole call.  tools/mid_batch_encode.py with ALZ_MID_BIG=on / off,
-        // profiles/r05_mid_big_vs_seg.txt: 4 x 256 KiB at quality 8 0.47 ms one by one against 0.42, 8 x 1 MB 1.66 / 1.73, 16 x 1 MB 3.33 / 2.18)
-        {
-            bool seg_all = true, aseg_all = true, spec_any = false, wide_any = false; int nf = 0; double mib_all = 0;
-            for (int f = 0; f < ALZ_FMT_COUNT; f++) if (cnt[f]) {
-                nf++; seg_all = seg_all && seg_len[f] != 0; spec_any = spec_any || alz_encode_seg_spec_format(f);
-                wide_any = wide_any || alz_encode_geom_max_dist(geom.data() + f * alz_encode_geom_size()) > 8192;
-                aseg_all = aseg_all && alz_encode_aseg(geom.data() + f * alz_encode_geom_size(), cnt[f], max_len, nullptr, nullptr, nullptr, nullptr, nullptr);
-            }
-            for (uint32_t i = 0; i < n; i++) mib_all += streams[i].src_len / 1048576.0;
-            // (the formats of the speculative walk -- alz_encode_seg_seq.h -- have one serial step per segment of the longest buffer behind that, and the 64 KiB windows above quality 0 their
-            // words / narrowing passes: ~0.4 / 2.0 ms per MiB; 2 / 4 / 8 / 16 x 1 MiB at the end of round 6, ms, one by one | side by side: LZ4 blocks at quality 0 0.65 / 1.28 / 2.53 / 5.09 |
-            // 0.99 / 1.03 / 1.11 / 1.60, at quality 8 1.61 / 3.19 / 6.39 / 12.8 | 2.93 / 3.06 / 3.43 / 4.63; LZ11 at quality 0 0.42 / 0.84 / 1.64 / 3.27 | 0.72 / 0.79 / 0.90 / 1.42, at quality 8
-            // 0.76 / 1.47 / 2.92 / 5.89 | 1.65 / 1.84 / 2.07 / 2.95)
-            const double t_spec = spec_any ? ((wide_any && !q0) ? 2.0 : 0.4) : 0.0;
-            if (seg_all) { const double t_seg = 0.14 * nf + ((aseg_all ? (q0 ? 0.45 : 0.9) : 2.2) + t_spec) * (max_len / 1048576.0) + (q0 ? 0.03 : 0.08) * mib_all; if (t_seg < t_side) t_side = t_seg; }
-        }
-        all = all && t_big < t_side;
-        if (all) {
-            HIP_TRY(hipSetDevice(c->device));
-            EncScratch sc(c);
-            size_t tail_bytes = 0;
-            if (!src_has_slack)
-                for (uint32_t i = 0; i < n; i++)
-                    if (streams[i].src_off + streams[i].src_len + 64 > src_bytes) tail_bytes += ((size_t)streams[i].src_len + 64 + 63) & ~(size_t)63;
-            // what travels back: per stream its result, its section offsets and the path's 16 control words -- one block, one copy
-            const size_t out_one = sizeof(alz_result) + sizeof(alz_encode_aux) + 16 * sizeof(uint32_t), sb_al = (sb + 255) & ~(size_t)255;
-            hipError_t e = hipSuccess;
-            void* d_tail = sc.get(alz_ctx::ENC_TAIL, tail_bytes, tail_bytes != 0);                 // (shared with the batch pipeline below)
-            void* d_big = sc.get(alz_ctx::ENC_BIG, sb_al + (size_t)n * out_one + 64);
-            if (sc.err != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(sc.err));
-            uint8_t* d_out = (uint8_t*)d_big + sb_al;
-            alz_result* d_results = (alz_result*)d_out;
-            alz_encode_aux* d_aux = (alz_encode_aux*)(d_out + (size_t)n * sizeof(alz_result));
-            uint32_t* d_ctl = (uint32_t*)(d_out + (size_t)n * (sizeof(alz_result) + sizeof(alz_encode_aux)));
-            int rc;
-            if ((rc = upload(d_src_base, d_dst_base))) return rc;
-            tm.mark("upload");
-            HIP_TRY(hipEventRecord(c->ev0, c->stream));
-            size_t toff = 0;
-            for (uint32_t i = 0; i < n; i++) {
-                alz_stream st1 = streams[i];
-                if (!src_has_slack && st1.src_off + st1.src_len + 64 > src_bytes) {      // its look-ahead would leave the caller's buffer
-                    uint8_t* to = (uint8_t*)d_tail + toff;
-                    HIP_TRY(hipMemcpyAsync(to, (const uint8_t*)d_src_base + st1.src_off, st1.src_len, hipMemcpyDeviceToDevice, c->stream));
-                    st1.src_off = (uint64_t)(uintptr_t)to - (uint64_t)(uintptr_t)d_src_base;
-                    toff += ((size_t)st1.src_len + 64 + 63) & ~(size_t)63;
-                }
-                e = alz_launch_encode_big((int)st1.format, c->stream, d_src_base, d_dst_base, &st1, d_results + i, d_aux + i, d_big, d_ctl + 16 * (size_t)i,
-                                          geom.data() + st1.format * alz_encode_geom_size());
-                if (e != hipSuccess) return fail(ALZ_E_HIP, "big-stream encode launch (format %u) failed: %s", st1.format, hipGetErrorString(e));
-            }
-            HIP_TRY(hipEventRecord(c->ev1, c->stream));
-            std::vector<uint8_t> hout((size_t)n * out_one);
-            HIP_TRY(hipMemcpyAsync(hout.data(), d_out, hout.size(), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            { float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms; }
-            tm.mark("kernels (big streams)");
-            const alz_encode_aux* haux = (const alz_encode_aux*)(hout.data() + (size_t)n * sizeof(alz_result));
-            const uint32_t* hctl = (const uint32_t*)(hout.data() + (size_t)n * (sizeof(alz_result) + sizeof(alz_encode_aux)));
-            bool any = false;
-            for (uint32_t i = 0; i < n; i++) any = any || hctl[16 * (size_t)i] != 0u;
-            if (!any) {
-                c->big_enc_launches += n;
-                memcpy(results, hout.data(), (size_t)n * sizeof(alz_result));
-                for (uint32_t i = 0; i < n; i++) if (aux) aux[i] = haux[i];
-                return ALZ_OK;
-            }
-            return encode_core(c, props, settings, n, src_bytes, streams, dst_bytes, results, aux, upload, src_has_slack, true);
-        }
+    return ALZ_OK;
+}
+// Stage 3: a handful of big streams: each of them on the whole GPU (alz_encode_big.h)?  true: yes, with *scratch the bytes that path needs.
+// As in the decoder (plan_create): one after the other on the whole GPU while that beats side by side with a workgroup + a wavefront
+// each -- measured at quality 0-8 on Test.bmp (tools/mid_batch_encode.py): ~0.10 ms + 0.10 ms per MiB on the whole GPU, ~22 ms per MiB of the LONGEST buffer side by side.
+static bool enc_takes_big_path(const alz_ctx* c, const enc_batch& b, uint32_t n, const alz_stream* streams, size_t* scratch) {
+    const uint32_t* cnt = b.cnt; const uint32_t max_len = b.max_len;
+    if (!(n <= ALZ_BIG_MAX_STREAMS && c->big_min != 0xFFFFFFFFu && !c->exact && c->variant == 0)) return false;
+    // (from 8 KiB on -- not the decoder's 24 KiB: ONE buffer of 8 KiB takes 0.08 ms of kernels this way and 0.22 through the batch pipeline, of
+    // 64 KiB 0.10 against 1.6, tools/single_encode_sizes.py; a threshold the caller has set below that is the caller's)
+    const uint32_t enc_min = c->big_min < 8192u ? c->big_min : 8192u;
+    bool all = true; size_t sb = 0;
+    double t_big = 0, t_side = 0;
+    const bool q0 = b.st.quality == 0;                                        // (no narrowing behind kernel A, one candidate per position in kernel B: 8 x 1 MB 0.99 one by one / 0.68)
+    for (uint32_t i = 0; all && i < n; i++) {
+        const void* g = b.slot[streams[i].format].geom;
+        all = streams[i].format != ALZ_FMT_FASTLZ && alz_encode_big_eligible((int)streams[i].format, g, &streams[i], enc_min);
+        if (all) { const size_t sbi = alz_encode_big_scratch_bytes((int)streams[i].format, g, &streams[i]); if (sbi > sb) sb = sbi; }
+        const double mib = streams[i].src_len / 1048576.0;
+        // (round 6, 2-32 x 1 MiB of Test.bmp one by one, ms per MiB: LZ4 blocks / LZO -- 64 KiB windows -- 0.32 at quality 0 and 0.80 at quality 8, LZ11 / LZ40 0.21 / 0.37)
+        const bool wide = alz_encode_geom_max_dist(g) > 8192, l11 = streams[i].format == ALZ_FMT_LZ11 || streams[i].format == ALZ_FMT_LZ40;
+        const double rate = wide ? (q0 ? 0.22 : 0.70) : (l11 && !q0) ? 0.27 : 0.10;
+        t_big += 0.10 + rate * mib; if (22.0 * mib > t_side) t_side = 22.0 * mib;
     }
-    // streams whose look-ahead would leave the caller's source buffer (see above)
-    std::vector<uint32_t> tail_ix; size_t tail_bytes = 0;
-    if (!src_has_slack)
-        for (uint32_t i = 0; i < n; i++)
-            if (streams[i].src_off + streams[i].src_len + 64 > src_bytes) { tail_ix.push_back(i); tail_bytes += ((size_t)streams[i].src_len + 64 + 63) & ~(size_t)63; }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
+    // (side by side is no longer one wavefront per buffer where the segmented parse + emit takes the launch, alz_encode_seg.h: what is left of the longest
+    // buffer's serial time is kernel A -- over segments too, for these few buffers: ~0.9 ms per MiB; one workgroup per buffer where that does not apply: 2.2 --
+    // + ~0.14 ms of small kernels per format + ~0.08 ms per MiB of the whole call.  tools/mid_batch_encode.py with ALZ_MID_BIG=on / off,
+    // profiles/r05_mid_big_vs_seg.txt: 4 x 256 KiB at quality 8 0.47 ms one by one against 0.42, 8 x 1 MB 1.66 / 1.73, 16 x 1 MB 3.33 / 2.18)
+    {
+        bool seg_all = true, aseg_all = true, spec_any = false, wide_any = false; int nf = 0; double mib_all = 0;
+        for (int f = 0; f < ALZ_FMT_COUNT; f++) if (cnt[f]) {
+            nf++; seg_all = seg_all && b.slot[f].seg_len != 0; spec_any = spec_any || alz_encode_seg_spec_format(f);
+            wide_any = wide_any || alz_encode_geom_max_dist(b.slot[f].geom) > 8192;
+            aseg_all = aseg_all && alz_encode_aseg(b.slot[f].geom, cnt[f], max_len, nullptr, nullptr, nullptr, nullptr, nullptr);
+        }
+        for (uint32_t i = 0; i < n; i++) mib_all += streams[i].src_len / 1048576.0;
+        // (the formats of the speculative walk -- alz_encode_seg_seq.h -- have one serial step per segment of the longest buffer behind that, and the 64 KiB windows above quality 0 their
+        // words / narrowing passes: ~0.4 / 2.0 ms per MiB; 2 / 4 / 8 / 16 x 1 MiB at the end of round 6, ms, one by one | side by side: LZ4 blocks at quality 0 0.65 / 1.28 / 2.53 / 5.09 |
+        // 0.99 / 1.03 / 1.11 / 1.60, at quality 8 1.61 / 3.19 / 6.39 / 12.8 | 2.93 / 3.06 / 3.43 / 4.63; LZ11 at quality 0 0.42 / 0.84 / 1.64 / 3.27 | 0.72 / 0.79 / 0.90 / 1.42, at quality 8
+        // 0.76 / 1.47 / 2.92 / 5.89 | 1.65 / 1.84 / 2.07 / 2.95)
+        const double t_spec = spec_any ? ((wide_any && !q0) ? 2.0 : 0.4) : 0.0;
+        if (seg_all) { const double t_seg = 0.14 * nf + ((aseg_all ? (q0 ? 0.45 : 0.9) : 2.2) + t_spec) * (max_len / 1048576.0) + (q0 ? 0.03 : 0.08) * mib_all; if (t_seg < t_side) t_side = t_seg; }
+    }
+    *scratch = sb;
+    return all && t_big < t_side;
+}
+// Stage 4: the streams whose look-ahead would leave the caller's source buffer (`src_has_slack`, below) are copied into scratch with room behind
+// them, and their descriptors -- in `moved`, the table the device gets -- point at the copy.  Once per call, whichever path asks first.
+static hipError_t enc_relocate_tails(alz_ctx* c, enc_io& io, uint32_t n, const alz_stream* streams) {
+    if (io.src_has_slack || io.tails_done) return hipSuccess;
+    io.tails_done = true;
+    auto in_tail = [&](const alz_stream& s) { return s.src_off + s.src_len + 64 > io.src_bytes; };
+    auto room = [](const alz_stream& s) { return ((size_t)s.src_len + 64 + 63) & ~(size_t)63; };
+    size_t bytes = 0; for (uint32_t i = 0; i < n; i++) if (in_tail(streams[i])) bytes += room(streams[i]);
+    if (!bytes) return hipSuccess;
+    EncScratch sc(c);
+    uint8_t* to = (uint8_t*)sc.get(alz_ctx::ENC_TAIL, bytes);
+    if (!to) return sc.err;
+    io.moved.assign(streams, streams + n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!in_tail(streams[i])) continue;
+        if (streams[i].src_len)
+            if (hipError_t e = hipMemcpyAsync(to, (const uint8_t*)io.d_src + streams[i].src_off, streams[i].src_len, hipMemcpyDeviceToDevice, c->stream)) return e;
+        io.moved[i].src_off = (uint64_t)(uintptr_t)to - (uint64_t)(uintptr_t)io.d_src;
+        to += room(streams[i]);
+    }
+    return hipSuccess;
+}
+// Stage 5: every stream on the whole GPU, one after the other.  *taken = false: a stream was declined (too many positions that need an exact
+// second search) and nothing has been delivered: the batch path below encodes the call.
+static int enc_big_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n, const alz_stream* streams, size_t sb, alz_result* results, alz_encode_aux* aux, bool* taken) {
+    EncScratch sc(c); *taken = false;
+    // what travels back: per stream its result, its section offsets and the path's 16 control words -- one block, one copy
+    const size_t out_one = sizeof(alz_result) + sizeof(alz_encode_aux) + 16 * sizeof(uint32_t), sb_al = (sb + 255) & ~(size_t)255;
+    void* d_big = sc.get(alz_ctx::ENC_BIG, sb_al + (size_t)n * out_one + 64);
+    if (sc.err != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(sc.err));
+    uint8_t* d_out = (uint8_t*)d_big + sb_al;
+    alz_result* d_results = (alz_result*)d_out;
+    alz_encode_aux* d_aux = (alz_encode_aux*)(d_out + (size_t)n * sizeof(alz_result));
+    uint32_t* d_ctl = (uint32_t*)(d_out + (size_t)n * (sizeof(alz_result) + sizeof(alz_encode_aux)));
+    int rc = io.stage();
+    if (rc) return rc;
+    std::vector<uint8_t> hout((size_t)n * out_one);
+    rc = launch_bracket(c, "alz_encode_batch", [] { return hipSuccess; },
+        [&] {
+            hipError_t e = enc_relocate_tails(c, io, n, streams);        // (between the events, where this path's copies have always been)
+            const alz_stream* table = io.moved.empty() ? streams : io.moved.data();
+            for (uint32_t i = 0; i < n && e == hipSuccess; i++)
+                e = alz_launch_encode_big((int)table[i].format, c->stream, io.d_src, io.d_dst, &table[i], d_results + i, d_aux + i, d_big, d_ctl + 16 * (size_t)i, b.slot[table[i].format].geom);
+            return e;
+        },
+        [&] { return hipMemcpyAsync(hout.data(), d_out, hout.size(), hipMemcpyDeviceToHost, c->stream); });
+    if (rc) return rc;
+    io.tm.mark("kernels (big streams)");
+    const alz_encode_aux* haux = (const alz_encode_aux*)(hout.data() + (size_t)n * sizeof(alz_result));
+    const uint32_t* hctl = (const uint32_t*)(hout.data() + (size_t)n * (sizeof(alz_result) + sizeof(alz_encode_aux)));
+    for (uint32_t i = 0; i < n; i++) if (hctl[16 * (size_t)i] != 0u) return ALZ_OK;
+    c->big_enc_launches += n;
+    memcpy(results, hout.data(), (size_t)n * sizeof(alz_result));
+    for (uint32_t i = 0; i < n; i++) if (aux) aux[i] = haux[i];
+    *taken = true;
+    return ALZ_OK;
+}
+// Stage 6: the batch pipeline, one launch per format slot present
+static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n, const alz_stream* streams, alz_result* results, alz_encode_aux* aux) {
+    const uint32_t* cnt = b.cnt; const uint64_t total = b.total;
+    const bool any_min = b.any(&enc_slot::min_table), any_match = b.any(&enc_slot::match), any_mask = b.any(&enc_slot::mask), any_narrow = b.any(&enc_slot::narrows);
     // (kernel A keeps its hash table in LDS: no per-stream tables in HBM, nothing that bounds the streams of a launch but the grid:
     // a launch carries the stream in gridDim.y; 70 000 went through on this runtime, the cap is caution)
     const uint32_t CH = 65535u;
@@ -1557,79 +1627,75 @@ static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_set
     void* d_match = sc.get(alz_ctx::ENC_MATCH, (size_t)total * 4 + 64, any_match);   // one 32-bit entry per position (alz_encode.hip: mentry); not when every launch searches inside its parse + emit kernel
     void* d_side = sc.get(alz_ctx::ENC_SIDE, (size_t)total * 2 + 64, cnt[ALZ_FMT_YAY0] || cnt[ALZ_FMT_MIO0] || cnt[ALZ_FMT_SMSR00]);   // section buffers
     void* d_mask = sc.get(alz_ctx::ENC_MASK, (size_t)total / 8 + 64, any_mask);          // a bit per position: the start mask of enc_roles_kernel, for the formats whose emitter is a kernel of its own
-    void* d_tail = sc.get(alz_ctx::ENC_TAIL, tail_bytes, !tail_ix.empty());
     uint32_t* d_sel = (uint32_t*)sc.get(alz_ctx::ENC_SEL, ((size_t)4 * n + 128) * sizeof(uint32_t), any_match);     // which kernel B per stream (enc_probe_kernel); behind it the two lists of enc_scan_select_kernel
     int* d_narrow = (int*)sc.get(alz_ctx::ENC_NARROW, (size_t)total * sizeof(int) + 256, any_narrow);   // the links of the finder's own hash width, narrowed from 15-bit ones (enc_narrow_kernel)
-    void* d_seg = sc.get(alz_ctx::ENC_SEG, seg_bytes, seg_bytes != 0);                                  // segment records of alz_encode_seg.h
-    hipError_t e = sc.err;
-    if (e != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(e));
-    tm.mark("validate + allocate");
-    std::vector<uint32_t> index(n), foff(ALZ_FMT_COUNT, 0), fill(ALZ_FMT_COUNT, 0);
-    { uint32_t off = 0; for (int f = 0; f < ALZ_FMT_COUNT; f++) { foff[f] = off; off += cnt[f]; } }
-    for (uint32_t i = 0; i < n; i++) { uint32_t f = streams[i].format; index[foff[f] + fill[f]++] = i; }
-    if (n_fastlz2)                                           // FastLZ: the level-1 streams first, then the level-2 ones (own geometry, own launch)
-        std::stable_partition(index.begin() + foff[ALZ_FMT_FASTLZ], index.begin() + foff[ALZ_FMT_FASTLZ] + cnt[ALZ_FMT_FASTLZ],
-                              [&](uint32_t i) { return !fastlz_level2(st, streams[i].src_len); });
-    if ((rc = upload(d_src_base, d_dst_base))) return rc;
-    tm.mark("upload");
-    std::vector<alz_stream> moved;                               // (stays alive until the synchronise below: the copy is asynchronous)
-    if (!tail_ix.empty()) {
-        moved.assign(streams, streams + n);
-        size_t off = 0;
-        for (uint32_t i : tail_ix) {
-            uint8_t* to = (uint8_t*)d_tail + off;
-            if (streams[i].src_len) HIP_TRY(hipMemcpyAsync(to, (const uint8_t*)d_src_base + streams[i].src_off, streams[i].src_len, hipMemcpyDeviceToDevice, c->stream));
-            moved[i].src_off = (uint64_t)(uintptr_t)to - (uint64_t)(uintptr_t)d_src_base;
-            off += ((size_t)streams[i].src_len + 64 + 63) & ~(size_t)63;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(d_streams, moved.empty() ? streams : moved.data(), (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_index, index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_pos, pos_off.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream));
-    HIP_TRY(hipMemsetAsync(d_aux, 0, (size_t)n * sizeof(alz_encode_aux), c->stream));
-    if (any_mask) HIP_TRY(hipMemsetAsync(d_mask, 0, (size_t)total / 8 + 64, c->stream));
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    const alz_encode_side side_q = { c->aux[0], c->fork, c->join[1] };      // (the scan streams' kernel runs beside the others: alz_launch_encode)
-    for (int f = 0; f <= ALZ_FMT_COUNT; f++) {
-        const bool lvl2 = f == ALZ_FMT_COUNT;
-        const int fmt = lvl2 ? ALZ_FMT_FASTLZ : f;
-        const uint32_t first = foff[fmt] + (lvl2 ? cnt[fmt] - n_fastlz2 : 0u);
-        const uint32_t count = lvl2 ? n_fastlz2 : cnt[f] - (f == ALZ_FMT_FASTLZ ? n_fastlz2 : 0u);
-        const void* g = geom.data() + f * alz_encode_geom_size();
-        for (uint32_t done = 0; done < count; done += CH) {
-            const uint32_t k = count - done < CH ? count - done : CH;
-            // (positional on purpose: the prototype lives in alz_internal.h, which the decode counters are hashed over -- a struct in its place belongs to the change that next re-profiles the decoder)
-            e = alz_launch_encode(fmt, c->stream, d_src_base, d_dst_base, d_streams, d_index + first + done, k, max_len, d_prev4, d_prevm, d_narrow,
-                                  d_match, d_pos, d_side, d_mask, d_results, d_aux, g, d_sel, n, seg_len[f] ? d_seg : nullptr, seg_len[f], seg_kmax[f], (c->exact || c->variant != 0) ? 2 : c->scan_mode, c->d_big_accepted ? c->d_big_accepted + 1 : nullptr, &side_q);
-            if (e != hipSuccess) return fail(ALZ_E_HIP, "encode launch (format %d) failed: %s", fmt, hipGetErrorString(e));
-            if (seg_len[f]) c->seg_enc_launches++;
-        }
-    }
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream));
+    void* d_seg = sc.get(alz_ctx::ENC_SEG, b.seg_bytes, b.seg_bytes != 0);                              // segment records of alz_encode_seg.h
+    if (sc.err != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(sc.err));
+    io.tm.mark("validate + allocate");
+    int rc = io.stage();
+    if (rc) return rc;
     std::vector<alz_encode_aux> haux(n);
-    HIP_TRY(hipMemcpyAsync(haux.data(), d_aux, (size_t)n * sizeof(alz_encode_aux), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    { float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_kernel_ms = ms; }   // table resets + the encode kernels
-    tm.mark("kernels");
+    const alz_encode_side side_q = { c->aux[0], c->fork, c->join[1] };      // (the scan streams' kernel runs beside the others: alz_launch_encode)
+    rc = launch_bracket(c, "alz_encode_batch",
+        [&] {   // (the tables are read out of `io.moved`, `b` and the caller's table: the bracket waits for the copies)
+            hipError_t e = enc_relocate_tails(c, io, n, streams);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_streams, io.moved.empty() ? streams : io.moved.data(), (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_index, b.index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_pos, b.pos_off.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(d_results, 0xFF, (size_t)n * sizeof(alz_result), c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(d_aux, 0, (size_t)n * sizeof(alz_encode_aux), c->stream);
+            if (e == hipSuccess && any_mask) e = hipMemsetAsync(d_mask, 0, (size_t)total / 8 + 64, c->stream);
+            return e;
+        },
+        [&] {   // table resets + the encode kernels
+            for (int f = 0; f <= ALZ_FMT_COUNT; f++) {
+                const bool lvl2 = f == ALZ_FMT_COUNT;
+                const int fmt = lvl2 ? ALZ_FMT_FASTLZ : f;
+                const uint32_t first = b.off[fmt] + (lvl2 ? cnt[fmt] - b.n_fastlz2 : 0u);
+                const uint32_t count = lvl2 ? b.n_fastlz2 : cnt[f] - (f == ALZ_FMT_FASTLZ ? b.n_fastlz2 : 0u);
+                const enc_slot& s = b.slot[f];
+                for (uint32_t done = 0; done < count; done += CH) {
+                    const uint32_t k = count - done < CH ? count - done : CH;
+                    // (positional on purpose: the prototype lives in alz_internal.h, which the decode counters are hashed over -- a struct in its place belongs to the change that next re-profiles the decoder)
+                    const hipError_t e = alz_launch_encode(fmt, c->stream, io.d_src, io.d_dst, d_streams, d_index + first + done, k, b.max_len, d_prev4, d_prevm, d_narrow,
+                                          d_match, d_pos, d_side, d_mask, d_results, d_aux, s.geom, d_sel, n, s.seg_len ? d_seg : nullptr, s.seg_len, s.seg_kmax, (c->exact || c->variant != 0) ? 2 : c->scan_mode, c->d_big_accepted ? c->d_big_accepted + 1 : nullptr, &side_q);
+                    if (e != hipSuccess) return e;
+                    if (s.seg_len) c->seg_enc_launches++;
+                }
+            }
+            return hipSuccess;
+        },
+        [&] { const hipError_t e = hipMemcpyAsync(results, d_results, (size_t)n * sizeof(alz_result), hipMemcpyDeviceToHost, c->stream);
+              return e == hipSuccess ? hipMemcpyAsync(haux.data(), d_aux, (size_t)n * sizeof(alz_encode_aux), hipMemcpyDeviceToHost, c->stream) : e; });
+    if (rc) return rc;
+    io.tm.mark("kernels");
     for (uint32_t i = 0; i < n; i++) if (aux) aux[i] = haux[i];
     return ALZ_OK;
+}
+static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_settings* settings, uint32_t n, size_t src_bytes, const alz_stream* streams,
+                       size_t dst_bytes, alz_result* results, alz_encode_aux* aux, const std::function<int(const void*&, void*&)>& upload, bool src_has_slack = true) {
+    enc_batch b; int rc;
+    if ((rc = enc_validate(settings, n, src_bytes, streams, dst_bytes, &b.st))) return rc;
+    b.lz = effective_lz(props);
+    enc_io io{upload, src_bytes, src_has_slack, phase_timer("alz_encode_batch")};
+    if ((rc = enc_geometry(c, n, streams, &b))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // A stream the whole-GPU path declines sends the whole call through the batch pipeline: in this same invocation, over the source staged once
+    size_t big_scratch = 0; bool taken = false;
+    if (enc_takes_big_path(c, b, n, streams, &big_scratch) && ((rc = enc_big_path(c, b, io, n, streams, big_scratch, results, aux, &taken)) || taken)) return rc;
+    return enc_batch_path(c, b, io, n, streams, results, aux);
 }
 
 int alz_encode_batch(alz_ctx* c, const alz_lz_properties* props, const alz_settings* settings, uint32_t n, const uint8_t* src_base,
                      size_t src_bytes, const alz_stream* streams, uint8_t* dst_base, size_t dst_bytes, alz_result* results, alz_encode_aux* aux) {
     if (!c || (n && (!streams || !results || !dst_base))) return fail(ALZ_E_INVALID, "alz_encode_batch: bad argument");
     if (n == 0) return ALZ_OK;
-    int rc = encode_core(c, props, settings, n, src_bytes, streams, dst_bytes, results, aux, [&](const void*& ds, void*& dd) {
-        int r;
-        if ((r = grow(c, &c->d_src, &c->d_src_cap, src_bytes + 64))) return r;
-        if ((r = grow(c, &c->d_dst, &c->d_dst_cap, dst_bytes + 64))) return r;
+    const int rc = encode_core(c, props, settings, n, src_bytes, streams, dst_bytes, results, aux, [&](const void*& ds, void*& dd) {
+        const int r = stage_source(c, src_base, src_bytes, true, dst_bytes);
         ds = c->d_src; dd = c->d_dst;
-        return staged_h2d(c, c->d_src, src_base, src_bytes);
+        return r;
     });
-    if (rc) return rc;
-    return download_outputs(c, n, streams, results, dst_base, true);
+    return rc ? rc : download_outputs(c, n, streams, results, dst_base, true);
 }
 
 // The same with the raw buffers already in HBM and the compressed streams left there (alz_stream offsets are relative to the two
@@ -1659,20 +1725,12 @@ static uint32_t format_weight(uint32_t fmt) {
 int alz_partition_batch(uint32_t n, const alz_stream* streams, uint32_t n_parts, uint32_t* part_of, uint64_t* part_cost) {
     if ((n && (!streams || !part_of)) || n_parts == 0) return fail(ALZ_E_INVALID, "alz_partition_batch: bad argument");
     std::vector<uint64_t> cost(n), load(n_parts, 0);
-    std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t f = streams[i].format < ALZ_FMT_COUNT ? streams[i].format : 0;
         const uint64_t out = streams[i].decom_len && streams[i].decom_len < streams[i].dst_cap ? streams[i].decom_len : streams[i].dst_cap;
         cost[i] = (out + 4096) * format_weight(f);           // (+ a fixed share: a wave per stream, header / tail handling)
-        order[i] = i;
     }
-    // greedy LPT: longest job first onto the least loaded part (equal jobs, as in the metric's batches, are dealt round-robin)
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-    for (uint32_t k = 0; k < n; k++) {
-        uint32_t best = 0;
-        for (uint32_t q = 1; q < n_parts; q++) if (load[q] < load[best]) best = q;
-        part_of[order[k]] = best; load[best] += cost[order[k]];
-    }
+    lpt_deal(n, n_parts, [&](uint32_t i) { return cost[i]; }, part_of, load.data());
     if (part_cost) for (uint32_t q = 0; q < n_parts; q++) part_cost[q] = load[q];
     return ALZ_OK;
 }
@@ -1705,87 +1763,76 @@ static int upload_segs(alz_ctx* c, void* d_base, const std::vector<in_seg>& segs
 }
 
 // One context's share of a batch: its streams are packed into device buffers of their own (16-byte aligned inputs, 256-byte
-// aligned outputs), so every device receives and returns only the bytes of its share.
+// aligned outputs), so every device receives and returns only the bytes of its share.  `src_slack`: bytes kept free behind every input;
+// `lz4_history`: an LZ4 block's history (aux0 bytes) gets room in front of its 256-aligned output slot.
+namespace { struct share_layout { std::vector<alz_stream> ds; std::vector<in_seg> ins; uint64_t so = 0, dof = 0; }; }
+static share_layout pack_share(const std::vector<uint32_t>& idx, const uint8_t* src_base, const alz_stream* streams, uint32_t src_slack, bool lz4_history) {
+    share_layout L; L.ds.reserve(idx.size()); L.ins.reserve(idx.size());
+    for (uint32_t i : idx) {
+        alz_stream st = streams[i];
+        L.ins.push_back(in_seg{L.so, src_base + st.src_off, st.src_len});
+        st.src_off = L.so; L.so += ((uint64_t)st.src_len + src_slack + 15) & ~15ull;
+        L.dof = (L.dof + (lz4_history && st.format == ALZ_FMT_LZ4_BLOCK ? st.aux0 : 0u) + 255) & ~255ull;
+        st.dst_off = L.dof; L.dof = (L.dof + st.dst_cap + 255) & ~255ull;
+        L.ds.push_back(st);
+    }
+    return L;
+}
+// ... the library's device buffers grown to the layout and its inputs uploaded
+static int stage_share(alz_ctx* c, const share_layout& L) {
+    int rc;
+    if ((rc = grow(c, &c->d_src, &c->d_src_cap, L.so + 64))) return rc;
+    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, L.dof + 64))) return rc;
+    return upload_segs(c, c->d_src, L.ins, L.so);
+}
+// ... and the share's results (and section offsets: `ax`, an encoder's) back in the caller's tables, what the streams produced (`only_ok`: the
+// streams that are ALZ_ST_OK) back in the caller's buffer
+static int scatter_share(alz_ctx* c, const std::vector<uint32_t>& idx, const share_layout& L, const alz_stream* streams, const alz_result* rs, const alz_encode_aux* ax,
+                         bool only_ok, uint8_t* dst_base, alz_result* results, alz_encode_aux* aux) {
+    std::vector<out_seg> outs; outs.reserve(idx.size());
+    for (size_t j = 0; j < idx.size(); j++) {
+        results[idx[j]] = rs[j];
+        if (ax && aux) aux[idx[j]] = ax[j];
+        if (rs[j].dst_len && (!only_ok || rs[j].status == ALZ_ST_OK)) outs.push_back(out_seg{L.ds[j].dst_off, dst_base + streams[idx[j]].dst_off, rs[j].dst_len});
+    }
+    return download_segs(c, outs);
+}
+
 static int decode_share(alz_ctx* c, const alz_lz_properties* props, const std::vector<uint32_t>& idx, const uint8_t* src_base,
                         const alz_stream* streams, uint8_t* dst_base, alz_result* results) {
     const uint32_t m = (uint32_t)idx.size();
-    if (m == 0) return ALZ_OK;
     HIP_TRY(hipSetDevice(c->device));
-    std::vector<alz_stream> ds(m);
-    std::vector<in_seg> ins; ins.reserve(m);
-    uint64_t so = 0, dof = 0;
-    for (uint32_t j = 0; j < m; j++) {
-        const alz_stream& st = streams[idx[j]];
-        const uint64_t hist = (st.format == ALZ_FMT_LZ4_BLOCK) ? st.aux0 : 0;
-        ds[j] = st;
-        ds[j].src_off = so; ins.push_back(in_seg{so, src_base + st.src_off, st.src_len});
-        so += ((uint64_t)st.src_len + 15) & ~15ull;
-        dof = (dof + hist + 255) & ~255ull;
-        ds[j].dst_off = dof;
-        dof = (dof + st.dst_cap + 255) & ~255ull;
-    }
+    const share_layout L = pack_share(idx, src_base, streams, 0, true);
     int rc;
-    if ((rc = grow(c, &c->d_src, &c->d_src_cap, so + 64))) return rc;
-    if ((rc = grow(c, &c->d_dst, &c->d_dst_cap, dof + 64))) return rc;
-    if ((rc = upload_segs(c, c->d_src, ins, so))) return rc;
+    if ((rc = stage_share(c, L))) return rc;
     for (uint32_t j = 0; j < m; j++) {                       // LZ4 blocks that continue a frame's window: their history travels too
         const alz_stream& st = streams[idx[j]];
         if (st.format == ALZ_FMT_LZ4_BLOCK && st.aux0)
-            HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_dst + ds[j].dst_off - st.aux0, dst_base + st.dst_off - st.aux0, st.aux0, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_dst + L.ds[j].dst_off - st.aux0, dst_base + st.dst_off - st.aux0, st.aux0, hipMemcpyHostToDevice, c->stream));
     }
     alz_plan* p = nullptr;
-    if ((rc = plan_create(c, props, m, ds.data(), &p, true))) return rc;
+    if ((rc = plan_create(c, props, m, L.ds.data(), &p, true))) return rc;
     std::vector<alz_result> rs(m);
     rc = alz_plan_execute(c, p, c->d_src, c->d_dst, nullptr);
     if (!rc) rc = alz_plan_results(c, p, rs.data());
-    if (rc) (void)hipStreamSynchronize(c->stream);           // (the stream table `ds` and the plan's index list are upload sources)
+    if (rc) (void)hipStreamSynchronize(c->stream);           // (the stream table `L.ds` and the plan's index list are upload sources)
     alz_plan_destroy(c, p);
-    if (rc) return rc;
-    std::vector<out_seg> outs; outs.reserve(m);
-    for (uint32_t j = 0; j < m; j++) {
-        results[idx[j]] = rs[j];
-        if (rs[j].dst_len) outs.push_back(out_seg{ds[j].dst_off, dst_base + streams[idx[j]].dst_off, rs[j].dst_len});
-    }
-    return download_segs(c, outs);
+    return rc ? rc : scatter_share(c, idx, L, streams, rs.data(), nullptr, false, dst_base, results, nullptr);
 }
 
 int alz_decode_batch_multi(alz_ctx* const* ctxs, uint32_t n_ctx, const alz_lz_properties* props, uint32_t n,
                            const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                            uint8_t* dst_base, size_t dst_bytes, alz_result* results, uint32_t* part_of_out) {
     if (!ctxs || n_ctx == 0 || n_ctx > 64 || (n && (!streams || !results))) return fail(ALZ_E_INVALID, "alz_decode_batch_multi: bad argument");
-    for (uint32_t q = 0; q < n_ctx; q++) {
-        if (!ctxs[q]) return fail(ALZ_E_INVALID, "alz_decode_batch_multi: context %u is NULL", q);
-        for (uint32_t r = 0; r < q; r++) if (ctxs[r] == ctxs[q]) return fail(ALZ_E_INVALID, "alz_decode_batch_multi: context %u is listed twice (a context is single-threaded)", q);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (streams[i].format >= ALZ_FMT_COUNT) return fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, streams[i].format);
-        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
-        if (!range_ok(streams[i].dst_off, streams[i].dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "stream %u: destination range exceeds dst_bytes", i);
-        if (streams[i].format == ALZ_FMT_LZ4_BLOCK && streams[i].aux0 > streams[i].dst_off) return fail(ALZ_E_INVALID, "stream %u: history %u exceeds dst_off", i, streams[i].aux0);
-    }
+    int rc;
+    if ((rc = check_contexts("alz_decode_batch_multi", ctxs, n_ctx))) return rc;
+    if ((rc = validate_streams("", ALZ_FMT_COUNT, n, streams, &src_bytes, &dst_bytes, refuse_lz4_history))) return rc;
     std::vector<uint32_t> part(n ? n : 1);
-    int rc = alz_partition_batch(n, streams, n_ctx, part.data(), nullptr);
-    if (rc) return rc;
-    if (part_of_out) for (uint32_t i = 0; i < n; i++) part_of_out[i] = part[i];
-    std::vector<std::vector<uint32_t>> idx(n_ctx);
-    for (uint32_t i = 0; i < n; i++) idx[part[i]].push_back(i);        // (ascending inside a share: source order)
-    // one host thread per context (a context is single-threaded; distinct contexts run concurrently), no collective: the
-    // shares are independent (a fresh LzWindows per stream, LZ10.cs:86)
-    std::vector<int> rcs(n_ctx, ALZ_OK);
-    std::vector<std::string> errs(n_ctx);
-    auto work = [&](uint32_t q) {
-        rcs[q] = decode_share(ctxs[q], props, idx[q], src_base, streams, dst_base, results);
-        if (rcs[q]) errs[q] = g_err;
-    };
-    if (n_ctx == 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (uint32_t q = 1; q < n_ctx; q++) th.emplace_back(work, q);
-        work(0);
-        for (std::thread& t : th) t.join();
-    }
-    for (uint32_t q = 0; q < n_ctx; q++) if (rcs[q]) return fail(rcs[q], "context %u (device %d): %s", q, ctxs[q]->device, errs[q].c_str());
-    return ALZ_OK;
+    if ((rc = alz_partition_batch(n, streams, n_ctx, part.data(), nullptr))) return rc;
+    // (the shares are independent: a fresh LzWindows per stream, LZ10.cs:86)
+    return run_shares(ctxs, n_ctx, n, part.data(), part_of_out, [&](uint32_t q, const std::vector<uint32_t>& idx) {
+        return decode_share(ctxs[q], props, idx, src_base, streams, dst_base, results);
+    });
 }
 
 // ---------------------------------------------------------------- device-resident batches over several contexts
@@ -1803,10 +1850,7 @@ void alz_plan_destroy_multi(alz_multi_plan* mp) {
 int alz_plan_create_multi(alz_ctx* const* ctxs, uint32_t n_ctx, const alz_lz_properties* props, uint32_t n, const alz_stream* streams,
                           const uint32_t* part_of, alz_multi_plan** out, uint32_t* part_of_out) {
     if (!ctxs || n_ctx == 0 || n_ctx > 64 || !out || (n && !streams)) return fail(ALZ_E_INVALID, "alz_plan_create_multi: bad argument");
-    for (uint32_t q = 0; q < n_ctx; q++) {
-        if (!ctxs[q]) return fail(ALZ_E_INVALID, "alz_plan_create_multi: context %u is NULL", q);
-        for (uint32_t r = 0; r < q; r++) if (ctxs[r] == ctxs[q]) return fail(ALZ_E_INVALID, "alz_plan_create_multi: context %u is listed twice (a context is single-threaded)", q);
-    }
+    if (int rc = check_contexts("alz_plan_create_multi", ctxs, n_ctx)) return rc;
     std::vector<uint32_t> part(n ? n : 1);
     if (part_of) { for (uint32_t i = 0; i < n; i++) { if (part_of[i] >= n_ctx) return fail(ALZ_E_INVALID, "alz_plan_create_multi: part_of[%u] = %u, %u contexts", i, part_of[i], n_ctx); part[i] = part_of[i]; } }
     else if (int rc = alz_partition_batch(n, streams, n_ctx, part.data(), nullptr)) return rc;
@@ -1850,35 +1894,15 @@ int alz_plan_results_multi(alz_multi_plan* mp, alz_result* results) {
 static int encode_share(alz_ctx* c, const alz_lz_properties* props, const alz_settings* settings, const std::vector<uint32_t>& idx,
                         const uint8_t* src_base, const alz_stream* streams, uint8_t* dst_base, alz_result* results, alz_encode_aux* aux) {
     const uint32_t m = (uint32_t)idx.size();
-    if (m == 0) return ALZ_OK;
-    std::vector<alz_stream> ds(m);
-    std::vector<in_seg> ins; ins.reserve(m);
-    uint64_t so = 0, dof = 0;
-    for (uint32_t j = 0; j < m; j++) {
-        const alz_stream& st = streams[idx[j]];
-        ds[j] = st;
-        ds[j].src_off = so; ins.push_back(in_seg{so, src_base + st.src_off, st.src_len});
-        so += ((uint64_t)st.src_len + 16 + 15) & ~15ull;    // (the match finder reads up to 16 bytes past a buffer: never another stream's)
-        ds[j].dst_off = dof;
-        dof = (dof + st.dst_cap + 255) & ~255ull;
-    }
+    const share_layout L = pack_share(idx, src_base, streams, 16, false);    // (the match finder reads up to 16 bytes past a buffer: never another stream's)
     std::vector<alz_result> rs(m);
     std::vector<alz_encode_aux> ax(m);
-    int rc = encode_core(c, props, settings, m, (size_t)so, ds.data(), (size_t)dof, rs.data(), ax.data(), [&](const void*& dsrc, void*& ddst) {
-        int r;
-        if ((r = grow(c, &c->d_src, &c->d_src_cap, so + 64))) return r;
-        if ((r = grow(c, &c->d_dst, &c->d_dst_cap, dof + 64))) return r;
+    int rc = encode_core(c, props, settings, m, (size_t)L.so, L.ds.data(), (size_t)L.dof, rs.data(), ax.data(), [&](const void*& dsrc, void*& ddst) {
+        const int r = stage_share(c, L);
         dsrc = c->d_src; ddst = c->d_dst;
-        return upload_segs(c, c->d_src, ins, so);
+        return r;
     });
-    if (rc) return rc;
-    std::vector<out_seg> outs; outs.reserve(m);
-    for (uint32_t j = 0; j < m; j++) {
-        results[idx[j]] = rs[j];
-        if (aux) aux[idx[j]] = ax[j];
-        if (rs[j].dst_len && rs[j].status == ALZ_ST_OK) outs.push_back(out_seg{ds[j].dst_off, dst_base + streams[idx[j]].dst_off, rs[j].dst_len});
-    }
-    return download_segs(c, outs);
+    return rc ? rc : scatter_share(c, idx, L, streams, rs.data(), ax.data(), true, dst_base, results, aux);
 }
 
 // alz_encode_batch over several contexts (one per GPU): streams are independent -- a fresh LzChainMatchFinder per CompressHeaderless
@@ -1887,43 +1911,16 @@ int alz_encode_batch_multi(alz_ctx* const* ctxs, uint32_t n_ctx, const alz_lz_pr
                            const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                            uint8_t* dst_base, size_t dst_bytes, alz_result* results, alz_encode_aux* aux, uint32_t* part_of_out) {
     if (!ctxs || n_ctx == 0 || n_ctx > 64 || (n && (!streams || !results || !dst_base))) return fail(ALZ_E_INVALID, "alz_encode_batch_multi: bad argument");
-    for (uint32_t q = 0; q < n_ctx; q++) {
-        if (!ctxs[q]) return fail(ALZ_E_INVALID, "alz_encode_batch_multi: context %u is NULL", q);
-        for (uint32_t r = 0; r < q; r++) if (ctxs[r] == ctxs[q]) return fail(ALZ_E_INVALID, "alz_encode_batch_multi: context %u is listed twice (a context is single-threaded)", q);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (streams[i].format >= ALZ_FMT_COUNT) return fail(ALZ_E_INVALID, "stream %u: unknown format %u", i, streams[i].format);
-        if (!range_ok(streams[i].src_off, streams[i].src_len, src_bytes)) return fail(ALZ_E_INVALID, "stream %u: source range exceeds src_bytes", i);
-        if (!range_ok(streams[i].dst_off, streams[i].dst_cap, dst_bytes)) return fail(ALZ_E_INVALID, "stream %u: destination range exceeds dst_bytes", i);
-    }
+    int rc;
+    if ((rc = check_contexts("alz_encode_batch_multi", ctxs, n_ctx))) return rc;
+    if ((rc = validate_streams("", ALZ_FMT_COUNT, n, streams, &src_bytes, &dst_bytes, no_refusal))) return rc;
     // greedy LPT over the raw sizes (the cost of an encode is its positions), longest first onto the least loaded context
-    std::vector<uint32_t> part(n ? n : 1), order(n);
+    std::vector<uint32_t> part(n ? n : 1);
     std::vector<uint64_t> load(n_ctx, 0);
-    for (uint32_t i = 0; i < n; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return streams[a].src_len > streams[b].src_len; });
-    for (uint32_t k = 0; k < n; k++) {
-        uint32_t best = 0;
-        for (uint32_t q = 1; q < n_ctx; q++) if (load[q] < load[best]) best = q;
-        part[order[k]] = best; load[best] += (uint64_t)streams[order[k]].src_len + 4096;
-    }
-    if (part_of_out) for (uint32_t i = 0; i < n; i++) part_of_out[i] = part[i];
-    std::vector<std::vector<uint32_t>> idx(n_ctx);
-    for (uint32_t i = 0; i < n; i++) idx[part[i]].push_back(i);
-    std::vector<int> rcs(n_ctx, ALZ_OK);
-    std::vector<std::string> errs(n_ctx);
-    auto work = [&](uint32_t q) {
-        rcs[q] = encode_share(ctxs[q], props, settings, idx[q], src_base, streams, dst_base, results, aux);
-        if (rcs[q]) errs[q] = g_err;
-    };
-    if (n_ctx == 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (uint32_t q = 1; q < n_ctx; q++) th.emplace_back(work, q);
-        work(0);
-        for (std::thread& t : th) t.join();
-    }
-    for (uint32_t q = 0; q < n_ctx; q++) if (rcs[q]) return fail(rcs[q], "context %u (device %d): %s", q, ctxs[q]->device, errs[q].c_str());
-    return ALZ_OK;
+    lpt_deal(n, n_ctx, [&](uint32_t i) { return (uint64_t)streams[i].src_len + 4096; }, part.data(), load.data());
+    return run_shares(ctxs, n_ctx, n, part.data(), part_of_out, [&](uint32_t q, const std::vector<uint32_t>& idx) {
+        return encode_share(ctxs[q], props, settings, idx, src_base, streams, dst_base, results, aux);
+    });
 }
 
 // ---------------------------------------------------------------- measurement helper: device copy bandwidth
