@@ -85,6 +85,60 @@ __device__ __forceinline__ u32 mask_window(u64 lo, u64 hi, int i) {
     return (u32)w;
 }
 
+// The real group chain of an iteration whose groups may start in its first 128 input bytes (WIDE): `gsize` / `gsize1` hold, per lane, the size of
+// "the group that would start at byte lane / 64 + lane".  Up to 8 hops from byte 0; the walk ends at the first group that would start at byte 128 or
+// beyond.  Returns the end of the last group taken (g), the number of groups (ng) and, in lanes 8 j .. 8 j + 7, the start of group j (gstart; 0 in
+// the lanes of groups not taken).
+// Written by hand: compiled from `g += g < 64 ? readlane(gsize, g) : readlane(gsize1, g - 64)` a hop was 9-10 scalar instructions, three of them
+// branches (the select became two guarded v_readlane with a 64-bit "taken" flag between them), and v_mov + v_cndmask for gstart -- a VALU instruction of
+// gfx9 reads ONE scalar operand, and the select needs the lane-group mask and g.  Here the walk has two phases, "while g < 64 on gsize" and "while
+// g < 128 on gsize1" (a group has at least one byte: g never comes back below 64; v_readlane takes the low six bits of its lane select, which are
+// g - 64 there), and the lanes of group j are selected by EXEC (0xFF << 8 j, one s_lshl_b64 per hop), so that gstart takes g with one v_mov.
+// Per hop: compare, branch, shift, add + v_readlane, v_mov.  The lane select of every v_readlane is written by the scalar unit (the wait states gfx9
+// asks for between a VALU write of an SGPR and its use as a lane select do not arise), EXEC is put back before the block ends.
+#ifndef ALZ_CHAIN_ASM
+#define ALZ_CHAIN_ASM 1
+#endif
+#define ALZ_HOP(it, entry, lim, src, fail) \
+    entry \
+    "s_cmpk_lt_u32 %[g], " lim "\n\t" \
+    "s_cbranch_scc0 " fail #it "_%=\n\t" \
+    "v_readlane_b32 %[n], " src ", %[g]\n\t" \
+    "s_lshl_b64 exec, exec, 8\n\t" \
+    "v_mov_b32 %[gs], %[g]\n\t" \
+    "s_add_u32 %[g], %[g], %[n]\n\t"
+#define ALZ_HOP_A(it) ALZ_HOP(it, "", "64", "%[s0]", ".LALZB")
+#define ALZ_HOP_B(it) ALZ_HOP(it, ".LALZB" #it "_%=:\n\t", "128", "%[s1]", ".LALZX")
+#define ALZ_HOP_X(it) ".LALZX" #it "_%=:\n\t" "s_movk_i32 %[ng], " #it "\n\t" "s_branch .LALZD_%=\n"
+__device__ __forceinline__ void chain_walk_wide(u32 gsize, u32 gsize1, u32& g_out, u32& ng_out, u32& gstart_out) {
+    u32 g, ng, n, gstart = 0;
+    u64 ex;
+    asm volatile(
+        "s_mov_b64 %[ex], exec\n\t"
+        "v_readlane_b32 %[n], %[s0], 0\n\t"                  // group 0 starts at byte 0 (gstart is 0 there already)
+        "s_mov_b64 exec, 0xff\n\t"
+        "s_mov_b32 %[g], %[n]\n\t"
+        ALZ_HOP_A(1) ALZ_HOP_A(2) ALZ_HOP_A(3) ALZ_HOP_A(4) ALZ_HOP_A(5) ALZ_HOP_A(6) ALZ_HOP_A(7)
+        "s_movk_i32 %[ng], 8\n\t"
+        "s_branch .LALZD_%=\n"
+        ALZ_HOP_B(1) ALZ_HOP_B(2) ALZ_HOP_B(3) ALZ_HOP_B(4) ALZ_HOP_B(5) ALZ_HOP_B(6) ALZ_HOP_B(7)
+        "s_movk_i32 %[ng], 8\n\t"
+        "s_branch .LALZD_%=\n"
+        ALZ_HOP_X(1) ALZ_HOP_X(2) ALZ_HOP_X(3) ALZ_HOP_X(4) ALZ_HOP_X(5) ALZ_HOP_X(6)
+        ".LALZX7_%=:\n\t"
+        "s_movk_i32 %[ng], 7\n"
+        ".LALZD_%=:\n\t"
+        "s_mov_b64 exec, %[ex]"
+        : [g] "=&s"(g), [ng] "=&s"(ng), [n] "=&s"(n), [ex] "=&s"(ex), [gs] "+v"(gstart)
+        : [s0] "v"(gsize), [s1] "v"(gsize1)
+        : "scc");
+    g_out = g; ng_out = ng; gstart_out = gstart;
+}
+#undef ALZ_HOP_X
+#undef ALZ_HOP_B
+#undef ALZ_HOP_A
+#undef ALZ_HOP
+
 // Interleaved formats.  Precondition: s.bits == 0 (group boundary), s.p + 128 <= src_len, out.produced < size.
 template <int FMT, class OW>
 __device__ __forceinline__ bool fast_iter_interleaved(InCache& in, OW& out, DecState& s, u32 size, u32 src_len, bool& to_serial, u8* segmark, int lane, const FastGeom& gm) {
@@ -139,8 +193,11 @@ __device__ __forceinline__ bool fast_iter_interleaved(InCache& in, OW& out, DecS
     // real group chain (round 4 measured two other forms: the hops written with selects instead of branches -- 14 vector instructions fewer per
     // iteration, 3.17 against 2.97 ms per launch: ten dependent scalar instructions per hop instead of five, and the tail of a launch runs at
     // the latency of exactly this chain --, and the starts packed into a scalar pair with one bit-field extract per lane afterwards: 3.09 ms,
-    // while two batches in flight gained 1 %)
+    // while two batches in flight gained 1 %.  The "five" was the chain of round 4; with groups starting in 128 bytes the compiled hop had grown to
+    // 9-10 scalar instructions: the WIDE chain is chain_walk_wide, above.)
     u32 g = 0, ng = 0, gstart = 0;
+    if (WIDE && ALZ_CHAIN_ASM != 0) chain_walk_wide(gsize, gsize1, g, ng, gstart);
+    else {
 #pragma unroll
     for (int it = 0; it < 8; it++) {
         if (g < (WIDE ? 128u : 64u)) {
@@ -149,6 +206,7 @@ __device__ __forceinline__ bool fast_iter_interleaved(InCache& in, OW& out, DecS
             else g += wave_readlane(gsize, g);
             ng = (u32)it + 1u;
         }
+    }
     }
     // lane 8j+k = token k of group j
     const u32 k = (u32)lane & 7u;

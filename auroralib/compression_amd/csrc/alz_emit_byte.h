@@ -49,7 +49,7 @@ __device__ __forceinline__ u32 pointer_jump(bool instep, u32 srclane, u32 val) {
 // mapping chain is paid once per 128 bytes -- was measured on top of the tags: 2.96 against 2.90 ms, PRS 5.80.  Not kept.)
 struct Mapper {
     u32 relm;        // my token's LAST byte relative to the next block to be marked (huge: no token / already behind)
-    u32 tbase4;      // 4 x (tokens that ended before the next step to be mapped)
+    u32 tbase;       // tokens that ended before the next step to be mapped (counted as tokens: the x 4 of the table / bpermute address is one v_add_lshl_u32 with the lane's count)
     u32 m;           // steps mapped so far in this batch (wave-uniform)
 };
 // The descriptor of token idx4 / 4.  DESCTAB: the descriptors of a batch's tokens live in a 64-entry LDS table behind the marks for the length of
@@ -85,8 +85,8 @@ template <class OW, bool DESCTAB, int PAR>
 __device__ __forceinline__ u32 map_one(OW& out, u8* segmark, int lane, u32 desc, Mapper& mp) {
     const u64 M = step_marks<OW, PAR>(out, segmark, lane, mp);
     const u32 cnt = __builtin_amdgcn_mbcnt_hi((u32)(M >> 32), __builtin_amdgcn_mbcnt_lo((u32)M, 0u));
-    const u32 dsc = desc_of<DESCTAB>(segmark, (cnt << 2) + mp.tbase4, desc);   // match: the distance; literal: bit31 | ...
-    mp.tbase4 += 4u * (u32)__popcll(M);
+    const u32 dsc = desc_of<DESCTAB>(segmark, (cnt + mp.tbase) << 2, desc);   // match: the distance; literal: bit31 | ...
+    mp.tbase += (u32)__popcll(M);
     mp.m += 1u;
     return dsc;
 }
@@ -131,8 +131,8 @@ __device__ __forceinline__ void fused_step(OW& out, u8* segmark, const u8* inlds
     const u32 mk = segmark[64u * (u32)PAR + (u32)lane];      // map side: marks of step k+1
     const u64 M = __ballot(mk == out.mtag);
     const u32 cnt = __builtin_amdgcn_mbcnt_hi((u32)(M >> 32), __builtin_amdgcn_mbcnt_lo((u32)M, 0u));
-    const u32 dscn = desc_of<CFG::DESCTAB>(segmark, (cnt << 2) + mp.tbase4, desc);
-    mp.tbase4 += 4u * (u32)__popcll(M);
+    const u32 dscn = desc_of<CFG::DESCTAB>(segmark, (cnt + mp.tbase) << 2, desc);
+    mp.tbase += (u32)__popcll(M);
     mp.m += 1u;
     u32 val;
     if (CFG::LITRUN) val = ((int)dsc < 0) ? lv : wv;
@@ -159,7 +159,7 @@ __device__ __forceinline__ void byte_emit_steps(OW& out, u8* segmark, const u8* 
     u32 X = 0;
     u32 qs = O + (u32)lane + out.oshift;                     // slot coordinate of this lane's byte in the current step
     Mapper mp;
-    mp.tbase4 = 0; mp.m = 0;
+    mp.tbase = 0; mp.m = 0;
     mp.relm = e.kept ? e.off + e.clen - 1u : 0xFFFFFF00u;
     if (CFG::DESCTAB) reinterpret_cast<u32*>(segmark + 128u)[lane] = desc;    // (ordered before the first read by the wave_sync behind the first block's marks)
     // unpipelined steps: the first W bytes of a stream (E2 test), and one more if that leaves the mapper in the middle of a block
@@ -169,6 +169,10 @@ __device__ __forceinline__ void byte_emit_steps(OW& out, u8* segmark, const u8* 
         X += 64u; out.produced = O + X; if (out.produced - out.flushed >= out.fl) out.flush_blocks();
     }
     u32 dA = 0, dB = 0; u32 ahead = 0;                        // steps mapped and not yet copied (their descriptors: dA, then dB)
+    // (Measured and not kept, docs/EXPERIMENTS.md 23: ONE trip counter for this loop -- the trips until the first of end of batch / next flush point / tag wrap
+    // counted before they run, a trip = the two steps, a decrement and a branch: 12 instead of 23 scalar instructions per trip in the ISA, but ~25 to set the
+    // counter up, and a batch of the synthetic mix is three trips.  Per launch Yaz0 lost 8.6 % of its scalar instructions with the chain of alz_decode_fast.h
+    // and this together, while MIO0 and Yay0, which have no chain, GAINED 14 % / 4 %: MIO0 3.22 -> 3.48 ms, Yay0 2.25 -> 2.29, LZSS 3.46 -> 3.54.)
     if (X + 128u <= T) {                                      // the steady state: two steps per trip (descriptor registers ping-pong, no copy)
         dA = map_one<OW, CFG::DESCTAB, 0>(out, segmark, lane, desc, mp);
         ahead = 1;
@@ -181,7 +185,7 @@ __device__ __forceinline__ void byte_emit_steps(OW& out, u8* segmark, const u8* 
     }
     if (X + 64u <= T) {                                       // one more whole step (fusing it with the mapping of a partial step behind it: Yaz0 2.94 against 2.90 ms)
         if (!ahead) dA = map_one<OW, CFG::DESCTAB, -1>(out, segmark, lane, desc, mp);
-        copy_one<OW, CFG, true, true>(out, inlds, lane, dA, qs, 64u); ahead = 0;
+        copy_one<OW, CFG, false, true>(out, inlds, lane, dA, qs, 64u); ahead = 0;   // (behind the first W bytes -- the first loop ran as long as O + X < W --: no E2 test)
         X += 64u; out.produced = O + X; if (out.produced - out.flushed >= out.fl) out.flush_blocks();
     }
     if (X < T) {
