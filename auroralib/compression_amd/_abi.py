@@ -92,6 +92,12 @@ MEASURE_PROTOTYPES = {
 RLH_PROTOTYPES = {name: [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
                   for name in ("alz_rlh_decode_batch", "alz_rlh_decode_batch_device", "alz_rlh_encode_batch", "alz_rlh_encode_batch_device")}
 
+# the RLHudson entry points (RLE30's sibling, a family with one kind): the same parameter list; `format`, aux0 and aux1 of a stream are ignored
+RLHUDSON_PROTOTYPES = {name: RLH_PROTOTYPES["alz_rlh_decode_batch"]
+                       for name in ("alz_rlhudson_decode_batch", "alz_rlhudson_decode_batch_device", "alz_rlhudson_encode_batch", "alz_rlhudson_encode_batch_device")}
+RLHUDSON_PROTOTYPES["alz_rlhudson_encode_bound"] = [C.c_size_t]
+RLHUDSON_RESTYPES = {"alz_rlhudson_encode_bound": C.c_size_t}
+
 # the aPLib entry points (decode only): batches of headerless bodies, their sizes without decoding, and the aPLib class on a file in host memory
 APLIB_WINDOW = 0x200000
 _APLIB_DECODE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -190,6 +196,31 @@ CRC32C_RESTYPES = {"alz_crc32c_combine": C.c_uint32}
 FRAMING_COMPRESS_PROTOTYPES = {
     "alz_framing_compress_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
 }
+
+# the wrapped files (alz_wfile_*): RLHudson and the seven wrapper classes of the .Extended assembly; in a batch Stream.format is the kind, aux0 bit 0 the byte order
+WF_ASURAZLB, WF_ZLB, WF_MDF0, WF_RAREZIP, WF_HWGZ, WF_SSZL, WF_ZLWF, WF_RLHUDSON = range(8)
+WF_COUNT = 8
+WF_NAMES = ["asurazlb", "zlb", "mdf0", "rarezip", "hwgz", "sszl", "zlwf", "rlhudson"]
+WB_ZLIB, WB_GZIP, WB_DEFLATE, WB_WFLZ, WB_WFLZ_BE, WB_RLHUDSON, WB_PLAIN = range(7)
+SSZL_COMPRESSED, SSZL_USE_GZIP, SSZL_ENCRYPTED = 0x1, 0x2, 0x80000000
+
+
+class WfilePart(C.Structure):
+    """alz_wfile_part"""
+    _fields_ = [("src_off", C.c_uint32), ("src_len", C.c_uint32), ("body", C.c_uint32), ("dst_len", C.c_uint32)]
+
+
+_U32P, _SZP = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)
+WFILE_PROTOTYPES = {
+    "alz_wfile_is_match": [C.c_uint32, C.c_void_p, C.c_size_t],
+    "alz_wfile_decompressed_size": [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, _U32P],
+    "alz_wfile_walk": [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, _U32P, _U32P, _U32P],
+    "alz_wfile_decompress": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _SZP, _SZP, C.POINTER(C.c_int32)],
+    "alz_wfile_decode_batch": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "alz_wfile_compress_bound": [C.c_uint32, C.c_void_p, C.c_size_t],
+    "alz_wfile_compress": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _SZP],
+}
+WFILE_RESTYPES = {"alz_wfile_compress_bound": C.c_size_t}
 
 # DEFLATE written on the GPU: raw streams (level 0..9, flags DEFLATE_FIXED) and ZLib / GZip files (kind: ZFILE_ZLIB / ZFILE_GZIP, in a batch Stream.format)
 DEFLATE_FIXED = 1

@@ -154,6 +154,23 @@ class Context:
         """alz_rlh_encode_batch_device: raw buffers in HBM at d_src, RLE30 streams left at d_dst."""
         return self._device(self.lib.alz_rlh_encode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
+    # ---- RLHudson: RLE30's sibling, a family with one kind (format, aux0 and aux1 of a stream are ignored)
+    def rlhudson_decode_batch(self, streams, src, dst_bytes):
+        """alz_rlhudson_decode_batch on host buffers: headerless RLHudson bodies, decom_len is the size their header states."""
+        return self._host_decode(self.lib.alz_rlhudson_decode_batch, (), streams, src, dst_bytes)
+
+    def rlhudson_encode_batch(self, streams, src, dst_bytes):
+        """alz_rlhudson_encode_batch: RLHudson.CompressHeaderless of raw buffers, bit-identical to the managed bytes (alz_rlhudson_encode_bound per buffer suffices)."""
+        return self._host_decode(self.lib.alz_rlhudson_encode_batch, (), streams, src, dst_bytes)
+
+    def rlhudson_decode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_rlhudson_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launch."""
+        return self._device(self.lib.alz_rlhudson_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
+
+    def rlhudson_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes):
+        """alz_rlhudson_encode_batch_device: raw buffers in HBM at d_src, RLHudson bodies left at d_dst."""
+        return self._device(self.lib.alz_rlhudson_encode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
+
     # ---- aPLib (decode only): headerless bodies; format, decom_len, aux0 and aux1 of a stream are ignored
     def aplib_decode_batch(self, streams, src, dst_bytes, dst=None):
         """alz_aplib_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
@@ -221,6 +238,15 @@ class Context:
         dst = _dst_array(dst, dst_bytes)
         res = (A.FileResult * len(files))()
         check(self.lib.alz_zfile_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
+    def wfile_decode_batch(self, files, src, dst_bytes, dst=None):
+        """alz_wfile_decode_batch on host buffers -> (dst, results): files[i].format is an A.WF_* kind (a batch may mix them), aux0 bit 0 the byte
+        order of an HWGZ / ZLWF file; per file what alz_wfile_decompress returns for it alone."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        check(self.lib.alz_wfile_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
         return dst, res
 
     def zfile_measure_batch(self, files, src):

@@ -15,6 +15,7 @@
 
 #include "alz_file_batch.h"
 #include "alz_framing.h"
+#include "alz_zfile.h"
 #include "auroralz.h"
 
 // The RLE30 / HUF20 entry points are referenced WEAKLY from here: the sanitized fuzz binary of these header parsers (oracle/Makefile,
@@ -738,9 +739,8 @@ int alz_container_decompress(alz_ctx* ctx, uint32_t container, const alz_contain
         if (len < 4 || memcmp(src, "WFLZ", 4)) return ALZ_E_FORMAT;
         if (len < 12) { r.status = ALZ_ST_INPUT_TRUNCATED; break; }
         const bool wbig = opt && opt->big_endian;                                           // FormatByteOrder: little unless the caller says otherwise
-        uint32_t csz = rd32(src + 4, wbig);
-        size = rd32(src + 8, wbig); hdr = 12;
-        if (csz > len - hdr) csz = clamp32(len - hdr);                                      // Stream.Read returns what is there; the body then runs off its end
+        uint32_t csz;
+        alz_wframe::wflz_header(src, len, wbig, &csz, &size); hdr = 12;                     // (shared with the ZLWF walk; Stream.Read returns what is there: the body then runs off its end)
         rc = run_body(ctx, wbig ? ALZ_FMT_WFLZ_BE : ALZ_FMT_WFLZ, nullptr, src + hdr, csz, 0, 0, 0, dst, dst_cap, &r);
         if (rc == ALZ_OK && r.status == ALZ_ST_OK && r.dst_len != size) r.status = ALZ_ST_OUTPUT_SIZE_MISMATCH;   // '!='  :82-85
         r.src_used = csz;                                                                   // the whole compressed span is read up front

@@ -1172,6 +1172,34 @@ int alz_rlh_encode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_bas
     return rlh_batch(c, true, true, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
 }
 
+// ---------------------------------------------------------------- RLHudson: RLE30's sibling of the HudsonSoft assembly (alz_rlh.hip)
+// Decode and encode.  One kind: `format`, aux0 and aux1 of a stream are ignored.
+size_t alz_rlhudson_encode_bound(size_t src_len) { return 2 * src_len; }   // a token never has more bytes than twice what it covers (a run of 3: 2, one literal: 2)
+
+static int rlhudson_batch(alz_ctx* c, bool device, bool encode, const batch_args& a) {
+    return batch_call(c, encode ? "alz_rlhudson_encode_batch" : "alz_rlhudson_decode_batch", 1, encode ? DL_ONLY_OK : DL_PRODUCED, device, a, no_refusals,
+        [&](uint32_t, const uint8_t* d_src, uint8_t* d_dst, const alz_stream* d_streams, const uint32_t* d_index, uint32_t count, alz_result* d_results) {
+            return encode ? alz_launch_rlhudson_encode(c->stream, d_src, d_dst, d_streams, d_index, count, d_results)
+                          : alz_launch_rlhudson_decode(c->stream, d_src, d_dst, d_streams, d_index, count, d_results, c->exact);
+        });
+}
+int alz_rlhudson_decode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                              uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return rlhudson_batch(c, false, false, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
+}
+int alz_rlhudson_encode_batch(alz_ctx* c, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                              uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return rlhudson_batch(c, false, true, {n, src_base, src_bytes, streams, dst_base, dst_bytes, results});
+}
+int alz_rlhudson_decode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                     uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    return rlhudson_batch(c, true, false, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
+}
+int alz_rlhudson_encode_batch_device(alz_ctx* c, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                     uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    return rlhudson_batch(c, true, true, {n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results});
+}
+
 // ---------------------------------------------------------------- aPLib: the last LzWindows user (alz_aplib.hip)
 // Decode and measure.  One kind: `format`, decom_len, aux0 and aux1 of a stream are ignored.
 static int aplib_batch(alz_ctx* c, bool device, bool measure, const batch_args& a) {

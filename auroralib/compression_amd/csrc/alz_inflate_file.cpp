@@ -84,19 +84,7 @@ int run(file_fn f, alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* ds
 
 // IsMatchStatic  ZLib.cs:26-27: Position + 4 < Length && CheckZlibHeaderAndFirstBlock(Peek<uint>())  :52-76
 int alz_zlib_is_match(const uint8_t* src, size_t src_len) {
-    if (!src || !(src_len > 4)) return 0;
-    const uint32_t cmf = src[0], flg = src[1], d1 = src[2], d2 = src[3];
-    if ((cmf & 0x0Fu) != 8u) return 0;                                          // CM != deflate
-    if (((cmf >> 4) & 0x0Fu) > 7u) return 0;                                    // CINFO > 7
-    if ((cmf * 256u + flg) % 31u != 0u) return 0;
-    const uint32_t btype = (d1 >> 1) & 3u;
-    if (btype == 3u) return 0;
-    if (btype == 0u) {                                                          // as written: LEN is read from the first two data bytes  :70
-        const uint16_t len = (uint16_t)(d1 | (d2 << 8)), nlen = (uint16_t)~len;
-        if ((len ^ nlen) != 0xFFFF) return 0;
-        if (len == 0) return 0;
-    }
-    return 1;
+    return zlib_is_match(src, src_len) ? 1 : 0;                                 // (alz_zfile.h: the wrapped-file walks ask the same question)
 }
 
 // IsMatchStatic  GZip.cs:25-26: Position + 8 < Length && the bytes 1F 8B 08

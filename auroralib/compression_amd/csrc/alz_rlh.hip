@@ -1,24 +1,26 @@
-// alz_rlh.hip -- gfx950 kernels of the two non-LZ members of the Nintendo GBA / DS family: RLE30 (decode + encode) and HUF20 (decode).
+// alz_rlh.hip -- gfx950 kernels of the two non-LZ members of the Nintendo GBA / DS family: RLE30 (decode + encode) and HUF20 (decode), and of
+// RLE30's sibling RLHudson (Hudson Soft's byte RLE, decode + encode: the RLE30 kernels over another grammar trait, alz_rlh_hudson_*).
 // A family of its own beside decode / encode / measure (tools/kernel_hash.py "rlh"): these bodies have no window, no match copy and
 // no oracle body, so they share nothing with the LZ kernels but the input cache (InCache), the wave scan and the chain walk
 // (lane_walk_pos) of alz_decode_fast.h, included as they are.  Citations are relative to the reference's
-// src/AuroraLib.Compression.Nintendo (Nintendo/RLE30.cs, Nintendo/HUF20.cs) and src/AuroraLib.Compression (MatchFinder/RleMatchFinder.cs).
+// src/AuroraLib.Compression.Nintendo (Nintendo/RLE30.cs, Nintendo/HUF20.cs, HudsonSoft/RLHudson.cs) and src/AuroraLib.Compression
+// (MatchFinder/RleMatchFinder.cs).
 //
 // Grid mapping: one wavefront per stream, ALZ_RLH_WPB wavefronts (= streams) per workgroup; the wavefronts of a workgroup never
 // interact.  Control flow is wave-uniform (parse state through readfirstlane), the 64 lanes share the byte work.
 //
 // Two families per alz_ctx_set_exact_kernels:
 //   exact       one token (RLE30) / one bit (HUF20) at a time: the statement-for-statement restatement.
-//   production  RLE30 decode: where the element that starts at input byte p ends is a function of byte p alone (p + 2 for a run,
-//               p + n + 1 for n literals), so every lane sizes "the element that would start at my byte" of a 256-byte window, the chain
-//               walk finds the real starts, output offsets are a prefix sum over the element lengths, and the round's bytes are
+//   production  RLE30 / RLHudson decode: where the element that starts at input byte p ends is a function of byte p alone (p + 2 for a run,
+//               p + n + 1 for n literals; RLHudson's `80`, no literals in one byte, is left to the exact step), so every lane sizes "the
+//               element that would start at my byte" of a 256-byte window, the chain walk finds the real starts, output offsets are a prefix sum over the element lengths, and the round's bytes are
 //               written back in aligned 16-byte granules, one per lane (a run is a broadcast of one byte, a literal run a copy out of
 //               the input cache).  The stream's tail, the token that meets dst_cap and every error end in the exact step.
 //               HUF20 decode: lanes decode consecutive 32-bit words speculatively from the root state, then re-decode from their
 //               left neighbour's exit state until nothing changes (bounded; fixed-length codes never self-synchronise and take
 //               the full bound), symbols per lane are prefix-summed and written per output byte.  A round that does not settle, the
 //               tail and every error go to the exact path.
-//               RLE30 encode: one kernel for both families (run lengths and the literal walk of TryToFindMatch by ballots over
+//               RLE30 / RLHudson encode: one kernel for both families (run lengths and the literal walk of TryToFindMatch by ballots over
 //               128 positions, one token per step).
 #include <hip/hip_runtime.h>
 
@@ -33,43 +35,72 @@ __device__ __forceinline__ void rlh_write(alz_result* r, int lane, u32 dst_len, 
     if (lane == 0) { r->dst_len = dst_len; r->src_used = src_used; r->status = status; r->reserved = 0; }
 }
 
-// ------------------------------------------------------------------------------------------------ RLE30 decode
+// ------------------------------------------------------------------------------------------------ RLE30 / RLHudson decode
+// The two byte RLEs differ in their grammar only, which a trait carries: which half of the control bytes is a run (polarity), the length bias,
+// and whether an element may produce nothing.  Everything else -- the token step, the finish, the lane-parallel round -- is written once.
+//   RLE30     c >= 0x80: the next byte (c & 0x7F) + 3 times, else (c & 0x7F) + 1 literals; end of input reads as a literal run  RLE30.cs:84-98
+//   RLHudson  c <  0x80: the next byte (c & 0x7F) times, else (c & 0x7F) literals, both may be 0; ReadByte() = -1 reads as a run of 127
+//             whose ReadUInt8 throws  HudsonSoft/RLHudson.cs:60-75
+struct Rle30Grammar {
+    static constexpr bool kZeroLen = false;                              // every element writes at least one byte
+    __device__ static __forceinline__ bool run(u32 c) { return c >= 0x80u; }                          // :87
+    __device__ static __forceinline__ u32 len(u32 c) { return (c & 0x7Fu) + (c >= 0x80u ? 3u : 1u); } // :85, :90
+    // input bytes of the element that starts with control byte b, for the chain walk
+    __device__ static __forceinline__ u32 size(u32 b) { return b >= 0x80u ? 2u : b + 2u; }            // control + byte | control + (b + 1) literals
+    // the encoder's control bytes  RLE30.cs:119, :124 (a literal run of 129 -> 0x80: the defect)
+    __device__ static __forceinline__ u8 ctl_run(u32 dur) { return (u8)((dur - 3u) | 0x80u); }
+    __device__ static __forceinline__ u8 ctl_lit(u32 dur) { return (u8)(dur - 1u); }
+};
+struct HudsonGrammar {
+    static constexpr bool kZeroLen = true;                               // `00 xx` is two bytes that write nothing
+    __device__ static __forceinline__ bool run(u32 c) { return c < 0x80u; }                           // RLHudson.cs:65
+    __device__ static __forceinline__ u32 len(u32 c) { return c & 0x7Fu; }                            // :63
+    // `80`, no literals, is the one element of a single byte: the walk's bound of 32 elements per 64-byte sub-window needs two, so it is an
+    // unusual element and the exact step's
+    __device__ static __forceinline__ u32 size(u32 b) { return b < 0x80u ? 2u : (b == 0x80u ? ALZ_NX_BAD : (b & 0x7Fu) + 1u); }
+    // the encoder's control bytes  RLHudson.cs:92, :97 (literal runs of 128 / 129 -> 0x80 / 0x81: the defect)
+    __device__ static __forceinline__ u8 ctl_run(u32 dur) { return (u8)dur; }
+    __device__ static __forceinline__ u8 ctl_lit(u32 dur) { return (u8)(dur | 0x80u); }
+};
+
 struct RleState { u32 p, o; bool eof, ovf; u64 attempted_end; };
 
-// RLE30.DecompressHeaderless, one pass of its loop (RLE30.cs:84-98), read from global memory.  false: decoding ends here.
-__device__ __forceinline__ bool rle30_token(const u8* __restrict__ src, u32 n, u8* __restrict__ dst, u32 cap, int lane, RleState& s) {
-    if (s.p >= n) { s.eof = true; return false; }                        // ReadByte() = -1: a literal run of 128 that cannot be read  :84-96
+// DecompressHeaderless, one pass of its loop (RLE30.cs:84-98, RLHudson.cs:62-74), read from global memory.  false: decoding ends here.
+template <class G>
+__device__ __forceinline__ bool rle_token(const u8* __restrict__ src, u32 n, u8* __restrict__ dst, u32 cap, int lane, RleState& s) {
+    if (s.p >= n) { s.eof = true; return false; }                        // ReadByte() = -1: an element that cannot be read  RLE30.cs:84-96, RLHudson.cs:62-67
     const u32 c = uni((u32)src[s.p]);
-    u32 len = (c & 0x7Fu) + 1u;                                          // :85
-    const bool run = c >= 0x80u;                                         // :87
+    const u32 len = G::len(c);
+    const bool run = G::run(c);
     const u32 left = n - s.p - 1u;                                       // input behind the control byte
-    if (run) { if (left < 1u) { s.eof = true; return false; } len += 2u; }   // ReadUInt8 throws  :90
-    else if (left < len) { s.eof = true; return false; }                 // Read(section) != length  :95-96 (nothing of the short run is written)
+    if (run) { if (left < 1u) { s.eof = true; return false; } }          // ReadUInt8 throws, also in front of a run of 0  RLE30.cs:90, RLHudson.cs:67
+    else if (left < len) { s.eof = true; return false; }                 // Read(section) != length (nothing of the short run is written)  RLE30.cs:95-96, RLHudson.cs:71-72
     const u32 room = cap - s.o, cl = len < room ? len : room;            // E5
     if (run) {
         const u32 b = uni((u32)src[s.p + 1u]);
-        for (u32 k = (u32)lane; k < cl; k += 64u) dst[s.o + k] = (u8)b;  // section.Fill  :90
+        for (u32 k = (u32)lane; k < cl; k += 64u) dst[s.o + k] = (u8)b;  // section.Fill
         s.p += 2u;
     } else {
         for (u32 k = (u32)lane; k < cl; k += 64u) dst[s.o + k] = src[s.p + 1u + k];
         s.p += 1u + len;
     }
     if (len > room) { s.ovf = true; s.attempted_end = (u64)s.o + len; s.o = cap; return false; }
-    s.o += len;                                                          // :98
+    s.o += len;                                                          // RLE30.cs:98, RLHudson.cs:74
     return true;
 }
 
-__device__ __forceinline__ void rle30_finish(alz_result* r, int lane, const RleState& s, u32 n, u32 size, u32 cap) {
+__device__ __forceinline__ void rle_finish(alz_result* r, int lane, const RleState& s, u32 n, u32 size, u32 cap) {
     int status = ALZ_ST_OK;
     if (s.eof) status = ALZ_ST_INPUT_TRUNCATED;
     else if (s.ovf) status = (s.attempted_end > (u64)size && cap >= size) ? ALZ_ST_OUTPUT_SIZE_MISMATCH : ALZ_ST_OUTPUT_CAPACITY;
-    else if (s.o > size) status = ALZ_ST_OUTPUT_SIZE_MISMATCH;           // :101-104
+    else if (s.o > size) status = ALZ_ST_OUTPUT_SIZE_MISMATCH;           // RLE30.cs:101-104, RLHudson.cs:77-80
     rlh_write(r, lane, s.o, s.eof ? n : s.p, status);
 }
 
-__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_exact_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base,
-                                                                                     const alz_stream* __restrict__ streams, const u32* __restrict__ index_list,
-                                                                                     u32 count, alz_result* __restrict__ results) {
+// the exact family: one token per step
+template <class G>
+__device__ __forceinline__ void rle_decode_exact(const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
+                                                 const u32* __restrict__ index_list, u32 count, alz_result* __restrict__ results) {
     const u32 bid = blockIdx.x * ALZ_RLH_WPB + ((u32)threadIdx.x >> 6);
     if (bid >= count) return;
     const int lane = (int)(threadIdx.x & 63u);
@@ -79,19 +110,19 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_exact_k
     u8* dst = dst_base + st.dst_off;
     const u32 n = uni(st.src_len), size = uni(st.decom_len), cap = uni(st.dst_cap);
     RleState s; s.p = 0; s.o = 0; s.eof = false; s.ovf = false; s.attempted_end = 0;
-    while (s.o < size)                                                   // :82
-        if (!rle30_token(src, n, dst, cap, lane, s)) break;
-    rle30_finish(&results[sid], lane, s, n, size, cap);
+    while (s.o < size)                                                   // RLE30.cs:82, RLHudson.cs:60
+        if (!rle_token<G>(src, n, dst, cap, lane, s)) break;
+    rle_finish(&results[sid], lane, s, n, size, cap);
 }
 
 // LDS per wavefront: the input cache (two 512-byte chunks + 32) and the round's element table (64 ends + 64 descriptors).
 #define ALZ_RLH_QCH 512u
 #define ALZ_RLH_CACHE (2u * ALZ_RLH_QCH + 32u)
 #define ALZ_RLH_RLE_PER (ALZ_RLH_CACHE + 512u)
-__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base,
-                                                                               const alz_stream* __restrict__ streams, const u32* __restrict__ index_list,
-                                                                               u32 count, alz_result* __restrict__ results) {
-    __shared__ __attribute__((aligned(16))) u8 lds_all[ALZ_RLH_WPB * ALZ_RLH_RLE_PER];
+// the production family; lds_all: ALZ_RLH_WPB * ALZ_RLH_RLE_PER bytes of the workgroup
+template <class G>
+__device__ __forceinline__ void rle_decode_rounds(u8* lds_all, const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
+                                                  const u32* __restrict__ index_list, u32 count, alz_result* __restrict__ results) {
     const u32 wid = (u32)threadIdx.x >> 6;
     const u32 bid = blockIdx.x * ALZ_RLH_WPB + wid;
     if (bid >= count) return;
@@ -113,31 +144,28 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_kernel(
             const u32 i0 = in.idx(s.p);
             u32 nx[4];
 #pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const u32 b = in.lds[i0 + 64u * (u32)w + (u32)lane];
-                nx[w] = b >= 0x80u ? 2u : b + 2u;                        // control + byte | control + (b + 1) literals
-            }
+            for (int w = 0; w < 4; w++) nx[w] = G::size((u32)in.lds[i0 + 64u * (u32)w + (u32)lane]);
             u32 spos, sp, nel;
             // lane_walk_pos walks four 64-byte sub-windows and records element j's start in lane j (v_writelane, lane index in m0).  A sub-window is
-            // entered only while fewer than 33 elements are taken, and adds at most 32 (every element has >= 2 bytes): at most 32 + 32 = 64
+            // entered only while fewer than 33 elements are taken, and adds at most 32 (every element it takes has >= 2 bytes): at most 32 + 32 = 64
             // elements, so the lane index stays <= 63 and never wraps to lane 0.
             lane_walk_pos(nx, 33u, spos, sp, nel);
             const u32 pos = i0 + (spos & 255u);
             const u32 b = in.lds[pos], e1 = in.lds[pos + 1u];
             const bool mine = (u32)lane < nel;
-            const u32 len = !mine ? 0u : (b >= 0x80u ? (b & 0x7Fu) + 3u : b + 1u);
+            const u32 len = !mine ? 0u : G::len(b);
             const u32 incl = wave_incl_scan(len, lane), excl = incl - len;
-            // elements are taken while the output is short of the declared size (:82) and they fit dst_cap whole (E5 is the exact step's)
+            // elements are taken while the output is short of the declared size (the loop condition) and they fit dst_cap whole (E5 is the exact step's)
             const u64 takem = wave_ballot(mine && excl < size - s.o && incl <= cap - s.o);
             const u32 k = (u32)__popcll(takem);
             if (k) {
                 const u32 total = wave_readlane(incl, k - 1u);
                 const u32 adv = k == nel ? sp : (wave_readlane(spos, k) & 255u);
-                tend[lane] = incl; tdesc[lane] = b >= 0x80u ? (0x80000000u | e1) : pos + 1u;
+                tend[lane] = incl; tdesc[lane] = G::run(b) ? (0x80000000u | e1) : pos + 1u;
                 wave_sync();
                 u8* const o = dst + s.o;
                 const u32 a0 = (u32)(reinterpret_cast<uintptr_t>(o) & 15u);
-                const u32 ng = (a0 + total + 15u) >> 4;
+                const u32 ng = (G::kZeroLen && total == 0u) ? 0u : (a0 + total + 15u) >> 4;   // (a round of empty runs only moves the input on)
                 for (u32 g = (u32)lane; g < ng; g += 64u) {              // one aligned 16-byte granule per lane and pass
                     const int k0 = (int)(g << 4) - (int)a0;
                     const u32 kb = k0 < 0 ? 0u : (u32)k0, ke = (u32)(k0 + 16) < total ? (u32)(k0 + 16) : total;
@@ -153,7 +181,8 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_kernel(
                     for (int j = 0; j < 16; j++) {
                         const u32 q = (u32)(k0 + j);
                         if (k0 + j >= (int)kb && q < ke) {
-                            if (q >= te) { ts = te; t++; te = tend[t]; d = tdesc[t]; }   // (every element has at least one byte)
+                            if (G::kZeroLen) { while (q >= te) { ts = te; t++; te = tend[t]; d = tdesc[t]; } }   // q < total = tend[k - 1]: stops inside the table
+                            else if (q >= te) { ts = te; t++; te = tend[t]; d = tdesc[t]; }                     // (every element has at least one byte)
                             const u32 v = (d >> 31) ? (d & 0xFFu) : (u32)in.lds[d + (q - ts)];
                             w[j >> 2] |= v << (8 * (j & 3));
                         }
@@ -170,19 +199,37 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_kernel(
                 continue;
             }
         }
-        if (!rle30_token(src, n, dst, cap, lane, s)) break;
+        if (!rle_token<G>(src, n, dst, cap, lane, s)) break;
     }
-    rle30_finish(&results[sid], lane, s, n, size, cap);
+    rle_finish(&results[sid], lane, s, n, size, cap);
 }
 
-// ------------------------------------------------------------------------------------------------ RLE30 encode
-// RLE30.CompressHeaderless (RLE30.cs:110-129) over RleMatchFinder(3, 127).TryToFindMatch (RleMatchFinder.cs:29-51), one token per step:
-// the 127 candidate positions of a step are two ballots of 64.  The managed defect is kept: `duration = source.Length - offset` (:43)
-// makes a literal run of up to 129 bytes, whose control byte (duration - 1) wraps to 0x80.
+#define ALZ_RLH_KERNEL_ARGS const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams, \
+                            const u32* __restrict__ index_list, u32 count, alz_result* __restrict__ results
+__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_exact_kernel(ALZ_RLH_KERNEL_ARGS) {
+    rle_decode_exact<Rle30Grammar>(src_base, dst_base, streams, index_list, count, results);
+}
+__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_hudson_decode_exact_kernel(ALZ_RLH_KERNEL_ARGS) {
+    rle_decode_exact<HudsonGrammar>(src_base, dst_base, streams, index_list, count, results);
+}
+__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_decode_kernel(ALZ_RLH_KERNEL_ARGS) {
+    __shared__ __attribute__((aligned(16))) u8 lds_all[ALZ_RLH_WPB * ALZ_RLH_RLE_PER];
+    rle_decode_rounds<Rle30Grammar>(lds_all, src_base, dst_base, streams, index_list, count, results);
+}
+__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_hudson_decode_kernel(ALZ_RLH_KERNEL_ARGS) {
+    __shared__ __attribute__((aligned(16))) u8 lds_all[ALZ_RLH_WPB * ALZ_RLH_RLE_PER];
+    rle_decode_rounds<HudsonGrammar>(lds_all, src_base, dst_base, streams, index_list, count, results);
+}
+
+// ------------------------------------------------------------------------------------------------ RLE30 / RLHudson encode
+// RLE30.CompressHeaderless (RLE30.cs:110-129) and RLHudson.CompressHeaderless (RLHudson.cs:83-102), both over RleMatchFinder(3, 127).TryToFindMatch
+// (RleMatchFinder.cs:29-51), one token per step: the 127 candidate positions of a step are two ballots of 64.  The two differ in the control bytes
+// only (the grammar trait).  The managed defect is kept: `duration = source.Length - offset` (:43) makes a literal run of up to 129 bytes, whose
+// control byte wraps -- RLE30's (duration - 1) to 0x80, RLHudson's (duration | 0x80) to 0x80 / 0x81 for 128 / 129.
 // Over dst_cap: status OUTPUT_CAPACITY and dst_len 0, as the LZ encoders report it; nothing behind dst_cap is written.
-__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_encode_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base,
-                                                                               const alz_stream* __restrict__ streams, const u32* __restrict__ index_list,
-                                                                               u32 count, alz_result* __restrict__ results) {
+template <class G>
+__device__ __forceinline__ void rle_encode(const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
+                                           const u32* __restrict__ index_list, u32 count, alz_result* __restrict__ results) {
     const u32 bid = blockIdx.x * ALZ_RLH_WPB + ((u32)threadIdx.x >> 6);
     if (bid >= count) return;
     const int lane = (int)(threadIdx.x & 63u);
@@ -192,7 +239,7 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_encode_kernel(
     u8* dst = dst_base + st.dst_off;
     const u32 n = uni(st.src_len), cap = uni(st.dst_cap);
     u32 p = 0, q = 0; bool fail = false;
-    while (p < n) {                                                      // RLE30.cs:115
+    while (p < n) {                                                      // RLE30.cs:115, RLHudson.cs:88
         const u32 rem = n - p;
         const u32 b0 = uni((u32)src[p]);
         const u32 lim = rem < 127u ? rem : 127u;                         // RleMatchFinder.cs:31
@@ -230,14 +277,20 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_encode_kernel(
         const u32 tb = run ? 2u : 1u + dur;
         if ((u64)q + tb > (u64)cap) { fail = true; break; }
         if (run) {
-            if (lane == 0) { dst[q] = (u8)((dur - 3u) | 0x80u); dst[q + 1u] = (u8)b0; }   // RLE30.cs:119-120
+            if (lane == 0) { dst[q] = G::ctl_run(dur); dst[q + 1u] = (u8)b0; }   // RLE30.cs:119-120, RLHudson.cs:92-93
         } else {
-            if (lane == 0) dst[q] = (u8)(dur - 1u);                      // :124 (129 -> 0x80: the defect)
-            for (u32 k = (u32)lane; k < dur; k += 64u) dst[q + 1u + k] = src[p + k];   // :125
+            if (lane == 0) dst[q] = G::ctl_lit(dur);                     // RLE30.cs:124, RLHudson.cs:97
+            for (u32 k = (u32)lane; k < dur; k += 64u) dst[q + 1u + k] = src[p + k];   // RLE30.cs:125, RLHudson.cs:98
         }
-        q += tb; p += dur;                                               // :127
+        q += tb; p += dur;                                               // RLE30.cs:127, RLHudson.cs:100
     }
     rlh_write(&results[sid], lane, fail ? 0u : q, n, fail ? ALZ_ST_OUTPUT_CAPACITY : ALZ_ST_OK);
+}
+__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_rle30_encode_kernel(ALZ_RLH_KERNEL_ARGS) {
+    rle_encode<Rle30Grammar>(src_base, dst_base, streams, index_list, count, results);
+}
+__global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_hudson_encode_kernel(ALZ_RLH_KERNEL_ARGS) {
+    rle_encode<HudsonGrammar>(src_base, dst_base, streams, index_list, count, results);
 }
 
 // ------------------------------------------------------------------------------------------------ HUF20 decode
@@ -490,6 +543,21 @@ __global__ __launch_bounds__(64 * ALZ_RLH_WPB) void alz_rlh_huf20_decode_kernel(
 #define ALZ_RLH_GRID(count) dim3(((count) + ALZ_RLH_WPB - 1) / ALZ_RLH_WPB), dim3(64 * ALZ_RLH_WPB), 0, stream
 
 bool alz_rlh_has_production(int fmt, bool encode) { return !encode && fmt >= 0 && fmt < ALZ_RLH_COUNT; }
+
+hipError_t alz_launch_rlhudson_decode(hipStream_t stream, const void* d_src, void* d_dst, const alz_stream* streams, const u32* index,
+                                      u32 count, alz_result* results, bool exact) {
+    if (count == 0) return hipSuccess;
+    if (exact) hipLaunchKernelGGL(alz_rlh_hudson_decode_exact_kernel, ALZ_RLH_GRID(count), (const u8*)d_src, (u8*)d_dst, streams, index, count, results);
+    else hipLaunchKernelGGL(alz_rlh_hudson_decode_kernel, ALZ_RLH_GRID(count), (const u8*)d_src, (u8*)d_dst, streams, index, count, results);
+    return hipGetLastError();
+}
+
+hipError_t alz_launch_rlhudson_encode(hipStream_t stream, const void* d_src, void* d_dst, const alz_stream* streams, const u32* index,
+                                      u32 count, alz_result* results) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(alz_rlh_hudson_encode_kernel, ALZ_RLH_GRID(count), (const u8*)d_src, (u8*)d_dst, streams, index, count, results);
+    return hipGetLastError();
+}
 
 hipError_t alz_launch_rlh_decode(int fmt, hipStream_t stream, const void* d_src, void* d_dst, const alz_stream* streams, const u32* index,
                                  u32 count, alz_result* results, bool exact) {

@@ -754,6 +754,158 @@ class GZip(_InflateFile):
         return (0 if q <= 2 else 1 if q <= 6 else 6 if q <= 9 else 9), False
 
 
+class _WrappedFile:
+    """A class of the reference that is a small header over a body the library decodes already (alz_wfile_*).  No alz_container value backs
+    it, so it stays outside ALL_FORMATS (WRAPPED_FORMATS lists these).  Decompress decodes into the stated size + 64 when no capacity is given,
+    so that an overlong body surfaces as DecompressedSizeException."""
+    provides_size = True
+    kind = None
+    deflate = True                                    # the body is DEFLATE: Compress is the BCL's, Deflate writes the file
+
+    def _opt(self):
+        o = A.ContainerOptions()
+        o.big_endian = 1 if getattr(self, "FormatByteOrder", "Little") == "Big" else 0
+        o.chunk_size = int(getattr(self, "ChunkSize", 0) or getattr(self, "BlockSize", 0))
+        o.variant = int(getattr(self, "Options", 0)) & 0xFFFFFFFF
+        return o
+
+    def IsMatch(self, data):
+        data = bytes(data)
+        return bool(load().alz_wfile_is_match(self.kind, data, len(data)))
+
+    def GetDecompressedSize(self, data):
+        data = bytes(data)
+        v, o = C.c_uint32(), self._opt()
+        rc = load().alz_wfile_decompressed_size(self.kind, C.byref(o), data, len(data), C.byref(v))
+        _raise_for_outcome(rc, A.ST_INPUT_TRUNCATED, 0)
+        return v.value
+
+    def Walk(self, data):
+        """alz_wfile_walk: (parts as (src_off, src_len, body, dst_len), stated size, flags)"""
+        data = bytes(data)
+        o, n, size, fl = self._opt(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        lib = load()
+        rc = lib.alz_wfile_walk(self.kind, C.byref(o), data, len(data), None, 0, C.byref(n), C.byref(size), C.byref(fl))
+        parts = (A.WfilePart * max(n.value, 1))()
+        if rc == A.E_INVALID and n.value:
+            rc = lib.alz_wfile_walk(self.kind, C.byref(o), data, len(data), parts, n.value, C.byref(n), C.byref(size), C.byref(fl))
+        _raise_for_outcome(rc, A.ST_INPUT_TRUNCATED, 0)
+        return [(p.src_off, p.src_len, p.body, p.dst_len) for p in parts[:n.value]], size.value, fl.value
+
+    def Decompress(self, data, capacity=None):
+        data = bytes(data)
+        if capacity is None:
+            capacity = self.GetDecompressedSize(data) + 64
+        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)
+        dl, su, st, o = C.c_size_t(), C.c_size_t(), C.c_int32(), self._opt()
+        rc = load().alz_wfile_decompress(_context().h, self.kind, C.byref(o), data, len(data), dst_arr.ctypes.data_as(C.c_void_p), capacity,
+                                         C.byref(dl), C.byref(su), C.byref(st))
+        self.last_src_used = su.value
+        if self.kind == A.WF_SSZL and len(data) >= 16:
+            self.Options = int.from_bytes(data[12:16], "little")            # Decompress stores the file's Options  SSZL.cs:92
+        _raise_for_outcome(rc, st.value, dl.value)
+        return dst_arr[:dl.value].tobytes()
+
+    def DecompressMany(self, files):
+        """Decompress for a whole set of files of this class in ONE alz_wfile_decode_batch.  Returns a list with, per file, its bytes -- or the
+        exception instance Decompress would have raised for it."""
+        files = [bytes(f) for f in files]
+        lib, o = load(), self._opt()
+        table, so, do = (A.Stream * len(files))(), 0, 0
+        for i, f in enumerate(files):
+            v = C.c_uint32()
+            cap = v.value + 64 if lib.alz_wfile_decompressed_size(self.kind, C.byref(o), f, len(f), C.byref(v)) == 0 else 0
+            table[i] = A.Stream(so, do, len(f), cap, 0, o.big_endian, 0, self.kind)
+            so += len(f)
+            do += (cap + 15) & ~15
+        dst, res = _context().wfile_decode_batch(table, np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8), do + 64)
+        out = []
+        for i, r in enumerate(res):
+            try:
+                _raise_for_outcome(r.rc, r.status, r.dst_len)
+                out.append(dst[int(table[i].dst_off):int(table[i].dst_off) + r.dst_len].tobytes())
+            except Exception as e:          # the instance is the result
+                out.append(e)
+        return out
+
+    def _write(self, data, settings, level, flags):
+        data = bytes(data)
+        lib, o = load(), self._opt()
+        s = settings or CompressionSettings.Balanced
+        st = A.Settings(s.Quality, s.MaxWindowBits, s.Strategy, 0)
+        cap = lib.alz_wfile_compress_bound(self.kind, C.byref(o), len(data))
+        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
+        dl = C.c_size_t()
+        check(lib.alz_wfile_compress(_context().h, self.kind, C.byref(o), C.byref(st), level, flags, data, len(data),
+                                     dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
+        return dst_arr[:dl.value].tobytes()
+
+    def Compress(self, data, settings=None):
+        if self.deflate:
+            raise NotImplementedError(INFLATE_NO_ENCODER % type(self).__name__)
+        return self._write(data, settings, 0, 0)
+
+    def Deflate(self, data, level=6, fixed=False):
+        """The file of this class around DEFLATE bodies of `level` 0..9 from the library's own encoder (alz_wfile_compress)."""
+        if not self.deflate:
+            raise NotImplementedError("%s has managed bytes: use Compress" % type(self).__name__)
+        return self._write(data, None, level, A.DEFLATE_FIXED if fixed else 0)
+
+
+class AsuraZlb(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/EA/AsuraZlb.cs"""
+    kind = A.WF_ASURAZLB
+
+
+class ZLB(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/Rare/ZLB.cs"""
+    kind = A.WF_ZLB
+
+
+class MDF0(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/Konami/MDF0.cs"""
+    kind = A.WF_MDF0
+
+
+class RareZip(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/Rare/RareZip.cs"""
+    kind = A.WF_RAREZIP
+
+
+class HWGZ(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/Specialized/HWGZ.cs -- ChunkSize, FormatByteOrder (default big)"""
+    kind = A.WF_HWGZ
+
+    def __init__(self):
+        self.ChunkSize, self.FormatByteOrder = 0x10000, "Big"
+
+
+class SSZL(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/Specialized/SSZL.cs -- Options (default Compressed | Encrypted)"""
+    kind = A.WF_SSZL
+    Compressed, UseGzip, Unknown, Encrypted = 0x1, 0x2, 0x10000, 0x80000000
+
+    def __init__(self):
+        self.Options = SSZL.Compressed | SSZL.Encrypted
+
+
+class ZLWF(_WrappedFile):
+    """src/AuroraLib.Compression-Extended/WayForward/ZLWF.cs -- BlockSize, FormatByteOrder (default big); N independent WFLZ files"""
+    kind = A.WF_ZLWF
+    deflate = False
+
+    def __init__(self):
+        self.BlockSize, self.FormatByteOrder = 0x400000, "Big"
+
+
+class RLHudson(_WrappedFile):
+    """src/AuroraLib.Compression.Nintendo/HudsonSoft/RLHudson.cs -- u32 BE size, u32 BE 5, the byte RLE of alz_rlhudson_*"""
+    kind = A.WF_RLHUDSON
+    deflate = False
+
+
+WRAPPED_FORMATS = [AsuraZlb, ZLB, MDF0, RareZip, HWGZ, SSZL, ZLWF, RLHudson]
+
 BITLZ_NO_ENCODER = ("%s has no encoder here: CompressHeaderless runs the LzChainMatchFinder, the bar is bit-identity with the managed bytes checked against "
                     "the CPU oracle, and there is no oracle body to hold bit-identity against (include/auroralz.h)")
 

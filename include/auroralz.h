@@ -315,6 +315,7 @@ int alz_measure_batch_device(alz_ctx* ctx, const alz_lz_properties* props, uint3
  *   INPUT_TRUNCATED, src_used = src_len, dst_len = the whole tokens before it (the managed code reads a literal run into a
  *   temporary and throws before it writes).  The last token may overshoot decom_len: written, OUTPUT_SIZE_MISMATCH (E4, the '>'
  *   rule of :101).  A token that would exceed dst_cap is clipped and ends decoding (E5, as LZ10).  decom_len 0: OK, nothing read.
+ *   (These are also the rules of RLHudson, alz_rlhudson_* below: the same kernels over another grammar.)
  * RLE30.CompressHeaderless (:110-129 over MatchFinder/RleMatchFinder.cs:29-64, minMatch 3, maxMatch 127): bit-identical to the managed
  *   bytes INCLUDING ITS DEFECT (E7): 127 literals followed by fewer than 3 bytes become ONE literal run of up to 129 bytes
  *   (`duration = source.Length - offset`, RleMatchFinder.cs:43), whose control byte wraps to 0x80 -- such a stream does not decode
@@ -344,6 +345,36 @@ int alz_rlh_encode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size
                          uint8_t* dst_base, size_t dst_bytes, alz_result* results);
 int alz_rlh_encode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                 uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+
+/* ---------------------------------------- RLHudson: Hudson Soft's byte RLE, the sibling of RLE30
+ * RLHudson (src/AuroraLib.Compression.Nintendo/HudsonSoft/RLHudson.cs) is RLE30 with the other polarity and no length bias.  It is
+ * NOT a fourth alz_rlh_format (ALZ_RLH_COUNT stays 3 and alz_rlh_decode_batch refuses format 3): it is a family with one kind and
+ * entry points of its own, as aPLib has.  alz_stream and alz_result are reused; `format`, aux0 and aux1 of a stream are IGNORED.
+ * Parameter lists, slack rules, the context modes (alz_ctx_set_exact_kernels: one token per step against the lane-parallel rounds,
+ * the same two kernels as RLE30 over another grammar) and alz_last_kernel_ms are those of alz_rlh_*.
+ *
+ * RLHudson.DecompressHeaderless (:54-81): control byte c, n = c & 0x7F; c < 0x80: the next byte n times, else n literals.  n MAY BE
+ *   0: `00 xx` consumes two bytes and `80` one, and neither writes anything.  Everything else is RLE30's rule set above, and for the
+ *   same reasons: input that ends at a control byte (ReadByte() = -1 reads as a run of 127 whose ReadUInt8 throws), at a run byte or
+ *   inside a literal run (the short read throws before anything is written): INPUT_TRUNCATED, src_used = src_len, dst_len = the
+ *   whole tokens before it.  The last token may overshoot decom_len: written, OUTPUT_SIZE_MISMATCH (the '>' rule of :77).  A token
+ *   that would exceed dst_cap is clipped and ends decoding (E5, statuses as RLE30).  decom_len 0: OK, nothing read.
+ * RLHudson.CompressHeaderless (:83-102 over RleMatchFinder(3, 0x7F)): bit-identical to the managed bytes INCLUDING ITS DEFECT, which
+ *   is RLE30's E7: `duration = source.Length - offset` (RleMatchFinder.cs:43) yields literal runs of 128 or 129 bytes, whose control
+ *   bytes (byte)(duration | 0x80) come out as 0x80 / 0x81 -- such a stream does not decode back (128, 129 or 255 non-repeating
+ *   bytes; 127 and 130 round-trip).  Over dst_cap: OUTPUT_CAPACITY, dst_len 0.  alz_rlhudson_encode_bound(src_len) always suffices.
+ * The RLHudson FILE (8-byte header: u32 BE size, u32 BE 5) is ALZ_WF_RLHUDSON of the alz_wfile_* family below. */
+int alz_rlhudson_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                              uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_rlhudson_decode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                     uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+/* src_* describe the raw input, dst_* the compressed output capacity; results[i].dst_len is the compressed size */
+int alz_rlhudson_encode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                              uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+int alz_rlhudson_encode_batch_device(alz_ctx* ctx, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                     uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+size_t alz_rlhudson_encode_bound(size_t src_len);   /* 2 * src_len: no token has more bytes than twice what it covers */
 
 /* ---------------------------------------- aPLib: the last LzWindows user of the reference (decode only)
  * aPLib (src/AuroraLib.Compression/Formats/Common/aPLib.cs) is no alz_format: its body carries no size, ends at an end marker and looks
@@ -609,7 +640,7 @@ uint32_t alz_crc32c_combine(uint32_t a, uint32_t b, uint64_t len_b);
  * the ZLib files and CRC-32 for the GZip members (measure: taken as correct); the trailers are compared on the host; the outputs are
  * downloaded once.  A GZip member behind the first is found only when the one before it is decoded, so a batch runs in rounds: round r
  * holds the r-th member of every file that has one, each member with a CRC-32 and ISIZE check of its own.
- * NOT BUILT: device-resident forms (headers and trailers are read on the host), the zlib wrappers of the .Extended assembly, preset
+ * NOT BUILT: device-resident forms (headers and trailers are read on the host), preset
  *   dictionaries.  The single-file entry points above are unchanged, host-side checksums included: they are the yardstick. */
 #define ALZ_ZFILE_ZLIB 0u
 #define ALZ_ZFILE_GZIP 1u
@@ -670,7 +701,7 @@ int alz_zfile_measure_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, s
  *   code, ALZ_ST_OK, 0, 0 }; one file's failure is that file's rc, and nothing outside a file's slot is written.  One batch: one upload,
  *   ONE alz_deflate_encode_batch_device over all bodies, one alz_checksum_batch_device per kind present over the raw inputs where they
  *   lie, the images assembled in HBM by one range copy, one download.
- * NOT BUILT: bit-exact concatenation of blocks, preset dictionaries, device-resident file forms, the .Extended wrappers. */
+ * NOT BUILT: bit-exact concatenation of blocks, preset dictionaries, device-resident file forms. */
 #define ALZ_DEFLATE_FIXED 1u
 size_t alz_deflate_bound(size_t src_len);
 int alz_deflate_block_bytes(void);
@@ -970,6 +1001,78 @@ int alz_container_compress(alz_ctx* ctx, uint32_t container, const alz_container
                            uint8_t* dst, size_t dst_cap, size_t* dst_len);
 /* worst-case compressed size for dst_cap sizing */
 size_t alz_container_compress_bound(uint32_t container, size_t src_len);
+
+/* ---------------------------------------- the wrapped files: RLHudson and the seven wrapper classes of the .Extended assembly
+ * Eight classes of the reference are a small header over a body the library already decodes.  They are no alz_container values (ALZ_C_COUNT
+ * stays 46): one kind enum and entry points of their own.  Paths relative to src/AuroraLib.Compression-Extended.
+ *   ALZ_WF_ASURAZLB  EA/AsuraZlb.cs       "AsuraZlb", u32 LE 1, u32 BE compressed size, u32 BE size, a BOUNDED zlib stream
+ *   ALZ_WF_ZLB       Rare/ZLB.cs          "ZLB\0", u32 BE 1, u32 BE size, u32 BE compressed size, a BOUNDED zlib stream
+ *   ALZ_WF_MDF0      Konami/MDF0.cs       "mdf\0", u32 LE size, a zlib stream to the end
+ *   ALZ_WF_RAREZIP   Rare/RareZip.cs      11 72, u32 BE size, a RAW DEFLATE stream to the end
+ *   ALZ_WF_HWGZ      Specialized/HWGZ.cs  chunk size, count, size (byte order detected: little first, then big), a table of count words that
+ *                                         the reader never looks at, then, each aligned to 128 from the start of the file, count x (size word in
+ *                                         FormatByteOrder = opt->big_endian whatever was detected, a BOUNDED zlib stream).  A batch inside one file.
+ *   ALZ_WF_SSZL      Specialized/SSZL.cs  "SSZL", u32 LE 0x20101109, u32 LE size, u32 LE Options, u32 0, then the payload: XORed with a
+ *                                         Mersenne-Twister keystream (seed 0x40C360F3) if Options & 0x80000000; a gzip file if Compressed (bit 0)
+ *                                         and it starts 1F 8B, a zlib file to the end if Compressed, otherwise plain bytes.
+ *   ALZ_WF_ZLWF      WayForward/ZLWF.cs   "ZLWF", compressed size, size, count, count offsets (FormatByteOrder), each the start of a whole WFLZ
+ *                                         file (ALZ_C_WFLZ) of that byte order.  NOT a zlib wrapper.  A batch inside one file.
+ *   ALZ_WF_RLHUDSON  src/AuroraLib.Compression.Nintendo/HudsonSoft/RLHudson.cs   u32 BE size, u32 BE 5, an RLHudson body (alz_rlhudson_*)
+ * alz_wfile_is_match is each class's IsMatchStatic, statement for statement, odd length tests included (ZLB asks for more than 0x14 bytes
+ * behind a 16-byte header; HWGZ for 0x80 bytes and ZLib.IsMatchStatic four bytes behind the aligned table; MDF0 tests the zlib header too).
+ * alz_wfile_walk is pure host code and needs no context: it returns the file's parts {src_off, src_len, body, dst_len} (dst_len: the decoded
+ * size a part states itself -- WFLZ, RLHudson -- else 0), the size the header states and, for SSZL, its Options in *flags; an encrypted SSZL part
+ * is still encrypted where it lies.  cap too small: ALZ_E_INVALID with *n_parts = the count needed.  Wrong magic (an HWGZ header that validates in
+ * neither order, a ZLWF chunk without "WFLZ"): ALZ_E_FORMAT.  A header, table or chunk that runs past the input -- an HWGZ count or chunk, a ZLWF
+ * count or offset outside the file: ALZ_E_STREAM (INPUT_TRUNCATED).  A caller with device-resident data feeds the parts to the _device batch calls.
+ * alz_wfile_decompress has the signature and conventions of alz_zlib_decompress; a NULL ctx is ALZ_E_INVALID only once a body must be decoded.
+ * alz_wfile_decode_batch: files[i].format is the kind (a batch may mix them), aux0 bit 0 the file's FormatByteOrder (1 = big; HWGZ, ZLWF).  THE
+ *   CONTRACT IS DIFFERENTIAL, as alz_zfile_decode_batch's: file i's result and bytes are exactly what alz_wfile_decompress returns for it
+ *   alone with the same capacity; a file's failure is that file's rc.  The walks run on the host; the source goes to the device once (SSZL
+ *   payloads XORed before, the keystream drawn once per call) and all parts of all files decode as one batch per body kind: one
+ *   alz_inflate_decode_batch_device for every zlib and raw DEFLATE part with one alz_checksum_batch_device for the Adler-32s, one plan of WFLZ
+ *   bodies, one alz_rlhudson_decode_batch_device.  A part's destination is the sum of the decoded sizes in front of it: an HWGZ file's chunks
+ *   are MEASURED first (one alz_inflate_measure_batch_device; ChunkSize is a writer's convention that the reader never enforces), a ZLWF chunk
+ *   states its size.  SSZL gzip payloads go through alz_zfile_decode_batch.
+ * Rules where the reference leaves room:
+ *   bounded zlib bodies (AsuraZlb, ZLB, each HWGZ chunk): the body is src[hdr, hdr + min(csize, bytes left)); result and bytes are
+ *     alz_zlib_decompress's on that range, EXCEPT that a body whose DEFLATE data ended properly and whose trailer has fewer than 4 bytes inside
+ *     the bound is ALZ_OK with the checksum unverified: the reference's own ZLB.Compress writes csize four short and its round-trip test passes
+ *     such files.  (Nobody has run the BCL on such a file here.)  A full trailer is verified: ALZ_E_CHECKSUM, output delivered.
+ *   stated sizes: AsuraZlb, ZLB, HWGZ, MDF0, SSZL, ZLWF: after an otherwise successful decode dst_len != stated is ALZ_E_STREAM /
+ *     OUTPUT_SIZE_MISMATCH with the output delivered.  RareZip and RLHudson use the '>' rule only; a RareZip body that decodes to fewer bytes
+ *     is ALZ_OK, the bytes up to the stated size are zero (SetLength) and dst_len is the stated size, limited by dst_cap.  A body that meets
+ *     dst_cap first is OUTPUT_CAPACITY.  A ZLWF chunk decodes into the size its WFLZ header states and no further: a body that runs past it is
+ *     OUTPUT_SIZE_MISMATCH with the stated bytes of that chunk delivered (dst_len ends there); one that ends short is the same status.  A ZLWF
+ *     file of no chunks with a non-zero stated size is a mismatch too, alone or in any batch.
+ * Writing.  RLHudson and ZLWF have managed bytes: alz_wfile_compress is bit-identical for them (level, flags ignored; ZLWF blocks through
+ *   alz_container_compress(ALZ_C_WFLZ)).  The six DEFLATE kinds have none (the reference hands Compress to the BCL): settings is ignored, level /
+ *   flags go to alz_deflate_*; all chunks of an HWGZ file are ONE alz_deflate_file_compress_batch; header fields as the reference's header code
+ *   writes them, ZLB's compressed size four short included; the HWGZ table is written correctly in the file's order.  opt->chunk_size: HWGZ
+ *   ChunkSize (0 = 0x10000), ZLWF BlockSize (0 = 0x400000); opt->variant: SSZL Options to write (0 = Compressed | Encrypted).
+ * NOT BUILT: device-resident file forms, rows of alz_brute_force / alz_container_scan, shim classes, Brotli (RFC 7932's static dictionary). */
+typedef enum alz_wfile_kind {
+    ALZ_WF_ASURAZLB = 0, ALZ_WF_ZLB, ALZ_WF_MDF0, ALZ_WF_RAREZIP,
+    ALZ_WF_HWGZ, ALZ_WF_SSZL, ALZ_WF_ZLWF, ALZ_WF_RLHUDSON, ALZ_WF_COUNT
+} alz_wfile_kind;
+typedef enum alz_wfile_body {
+    ALZ_WB_ZLIB = 0, ALZ_WB_GZIP, ALZ_WB_DEFLATE, ALZ_WB_WFLZ, ALZ_WB_WFLZ_BE, ALZ_WB_RLHUDSON, ALZ_WB_PLAIN
+} alz_wfile_body;
+typedef struct alz_wfile_part { uint32_t src_off, src_len, body, dst_len; } alz_wfile_part;
+#define ALZ_SSZL_COMPRESSED 0x1u
+#define ALZ_SSZL_USE_GZIP   0x2u
+#define ALZ_SSZL_ENCRYPTED  0x80000000u
+int alz_wfile_is_match(uint32_t kind, const uint8_t* src, size_t len);
+int alz_wfile_decompressed_size(uint32_t kind, const alz_container_options* opt, const uint8_t* src, size_t len, uint32_t* size_out);
+int alz_wfile_walk(uint32_t kind, const alz_container_options* opt, const uint8_t* src, size_t len, alz_wfile_part* parts, uint32_t cap,
+                   uint32_t* n_parts, uint32_t* stated_size, uint32_t* flags);
+int alz_wfile_decompress(alz_ctx* ctx, uint32_t kind, const alz_container_options* opt, const uint8_t* src, size_t len,
+                         uint8_t* dst, size_t dst_cap, size_t* dst_len, size_t* src_used, int32_t* status);
+int alz_wfile_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* files,
+                           uint8_t* dst_base, size_t dst_bytes, alz_file_result* results);
+size_t alz_wfile_compress_bound(uint32_t kind, const alz_container_options* opt, size_t src_len);
+int alz_wfile_compress(alz_ctx* ctx, uint32_t kind, const alz_container_options* opt, const alz_settings* settings, int level, uint32_t flags,
+                       const uint8_t* src, size_t len, uint8_t* dst, size_t dst_cap, size_t* dst_len);
 
 /* ------------------------------------------------ batch producers
  * The two places in the reference that issue many independent decodes, restated as callers of the batched path.

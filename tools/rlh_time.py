@@ -1,6 +1,7 @@
 """usage (GPU box): python tools/rlh_time.py [--commit ID] [--streams N] [--bytes B] [--distinct D]  -- the two kernel families of the RLE30 / HUF20 entry points side by side.
 The bytes are those a synthetic LZ10 batch (synth, N x B, default 10 000 x 64 KiB) decodes to, on the device:
   RLE30    every buffer compressed by alz_rlh_encode_batch_device (its kernel time is printed too), then decoded;
+  RLHudson the same through alz_rlhudson_encode_batch_device / alz_rlhudson_decode_batch_device (RLE30's kernels over another grammar);
   HUF20-8  / HUF20-4 (little nibble order) of the same bytes.  HUF20 has no encoder, so the streams are assembled on the host: the tree of tests/rlh_ref.py
            (huf20_tree, test-only) per buffer, the code words packed with numpy.  That costs seconds per thousand buffers, so D (default 1 000) distinct
            buffers are built and laid out N / D times -- N separate copies in HBM: the traffic is that of N streams, the content repeats.
@@ -84,7 +85,9 @@ def report(label, n, size, in_bytes, pairs):
         "production" if wins == 5 else "exact"), flush=True)
 
 
-def decode_case(ctx, label, fmt, streams, d_src, src_bytes, dst_bytes, raw, doffs, size, check_n):
+def decode_case(ctx, label, fmt, streams, d_src, src_bytes, dst_bytes, raw, doffs, size, check_n, decode=None):
+    """fmt None: RLHudson (`decode` is its entry point); the managed encoder's defect is RLE30's"""
+    decode = decode or ctx.rlh_decode_batch_device
     n = len(streams)
     d_dst = ctx.malloc(dst_bytes + 64)
     try:
@@ -92,18 +95,18 @@ def decode_case(ctx, label, fmt, streams, d_src, src_bytes, dst_bytes, raw, doff
         for exact in (1, 0):                                                       # both families: results and bytes
             ctx.set_exact_kernels(exact)
             ctx.memset(d_dst, 0, dst_bytes)
-            res = synth.result_records(ctx.rlh_decode_batch_device(streams, d_src, src_bytes, d_dst, dst_bytes)).copy()
+            res = synth.result_records(decode(streams, d_src, src_bytes, d_dst, dst_bytes)).copy()
             ok = (res["status"] == 0) & (res["dst_len"] == size)
             # (RLE30 only: a buffer whose last token is the managed encoder's 129-literal run does not decode back -- DESIGN.md 1, E7)
-            assert ok.all() or fmt == A.RLH_RLE30, (label, exact, np.unique(res["status"], return_counts=True))
+            assert ok.all() or fmt in (A.RLH_RLE30, None), (label, exact, np.unique(res["status"], return_counts=True))
             for i in list(range(check_n)) + [n - 1]:
                 if ok[i]:
                     assert np.array_equal(ctx.d2h(d_dst, size, int(doffs[i])), raw[i]), (label, exact, i)
             both.append(res)
         assert all(np.array_equal(both[0][k], both[1][k]) for k in ("status", "dst_len", "src_used")), label
         if not ok.all():
-            print("# %s: %d of %d buffers end in the encoder's 129-literal run and do not decode back (both families agree on them)" % (label, int((~ok).sum()), n))
-        pairs = timed_pairs(ctx, lambda: ctx.rlh_decode_batch_device(streams, d_src, src_bytes, d_dst, dst_bytes))
+            print("# %s: %d of %d buffers end in the encoder's over-long literal run and do not decode back (both families agree on them)" % (label, int((~ok).sum()), n))
+        pairs = timed_pairs(ctx, lambda: decode(streams, d_src, src_bytes, d_dst, dst_bytes))
         report(label, n, size, int(synth.stream_records(streams)["src_len"].astype(np.int64).sum()), pairs)
     finally:
         ctx.free(d_dst)
@@ -151,6 +154,20 @@ def main():
         rec = synth.stream_records(dec)
         rec["src_off"], rec["src_len"], rec["dst_off"], rec["dst_cap"], rec["decom_len"], rec["format"] = np.arange(n, dtype=np.uint64) * slot, eres["dst_len"], doffs, size, size, A.RLH_RLE30
         decode_case(ctx, "rle30", A.RLH_RLE30, dec, d_rle, n * slot, b.dst_bytes, raw, doffs, size, min(distinct, 16))
+        # ---- RLHudson, RLE30's sibling (the same kernels over another grammar): the same buffers, compressed on the device, then decoded
+        rec = synth.stream_records(enc)
+        rec["format"] = 0
+        eres = synth.result_records(ctx.rlhudson_encode_batch_device(enc, d_raw, b.dst_bytes, d_rle, n * slot))
+        assert (eres["status"] == 0).all()
+        ems = []
+        for _ in range(5):
+            ctx.rlhudson_encode_batch_device(enc, d_raw, b.dst_bytes, d_rle, n * slot)
+            ems.append(ctx.last_kernel_ms())
+        print("%-10s %6d x %7d B (%7.1f MB in, %7.1f MB out): RLHudson ENCODE (one kernel for both families), ms per call: %s | mean %.3f ms = %.1f GiB/s of raw bytes" % (
+            "rlhud enc", n, size, n * size / 1e6, int(eres["dst_len"].astype(np.int64).sum()) / 1e6, "  ".join("%.3f" % v for v in ems), sum(ems) / 5, n * size / 2**30 / (sum(ems) / 5e3)), flush=True)
+        rec = synth.stream_records(dec)
+        rec["src_len"], rec["format"] = eres["dst_len"], 0
+        decode_case(ctx, "rlhudson", None, dec, d_rle, n * slot, b.dst_bytes, raw, doffs, size, min(distinct, 16), decode=ctx.rlhudson_decode_batch_device)
         ctx.free(d_rle)
         ctx.free(d_raw)
 
