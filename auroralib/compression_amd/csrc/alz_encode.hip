@@ -25,9 +25,14 @@
 //   C  the greedy/lazy parse as a walk over 64-position windows and the emission of a window's tokens by prefix sums, in ONE kernel from
 //                               the same registers (one wavefront per stream): enc_parse_emit_kernel (the flag-bit formats: LZSS, LZ10, LZ11,
 //                               Yaz0, Yay0, MIO0 ...), enc_parse_seq_kernel (LZ4, Snappy), enc_emit_prs_kernel and enc_parse_lzo_kernel,
-//                               the last three on struct WinParse.  At quality 0 (one candidate per position) kernel B is inside them too.
+//                               the last three on struct WinParse; the flag-bit kernel keeps the same window walk as its own text (on the
+//                               struct its quality-0 form loses a wavefront per SIMD to registers: docs/EXPERIMENTS.md 25).  At quality 0 (one
+//                               candidate per position) kernel B is inside them too.
 //      enc_roles_kernel         the walk alone: a bit per token start, in front of enc_emit_kernel: emission on one lane per stream, for the
 //                               formats that have no parallel emit yet.
+// What every walk shares stands once, in front of its first user: parse_rule / parse_rule_needs_neighbour (FindNextBestMatch's decision at a cursor),
+// hop_walk_lim / hop_walk_full (the hand-written hops over a window), parse_capped_cursor (a cursor on an entry kernel B capped); and what every
+// flag-bit emitter shares: FlagFmt, put_flag_word, flag_payload, flag_window.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -65,8 +70,25 @@ __device__ __forceinline__ int link_at(const int* p4, int pos) {
 __device__ __forceinline__ u32 load32(const u8* p) { u32 v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ u64 load64(const u8* p) { u64 v; __builtin_memcpy(&v, p, 8); return v; }
 
-__device__ __forceinline__ u32 scan_add(u32 v);
-__device__ __forceinline__ u32 scan_max(u32 v);
+__device__ __forceinline__ u32 scan_add(u32 v) {            // inclusive wave prefix sum (gfx9 DPP)
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
+    return v;
+}
+__device__ __forceinline__ u32 scan_max(u32 v) {            // inclusive wave prefix max
+    u32 t;
+    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false); v = v > t ? v : t;
+    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false); v = v > t ? v : t;
+    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false); v = v > t ? v : t;
+    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false); v = v > t ? v : t;
+    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false); v = v > t ? v : t;
+    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false); v = v > t ? v : t;
+    return v;
+}
 
 
 // ---------------------------------------------------------------------------------------------- kernel A
@@ -498,6 +520,22 @@ typedef u32 mentry;
 #define ALZ_M_CAP 0x7FFu
 __device__ __forceinline__ mentry m_pack(u32 d, u32 l) { return (l << ALZ_M_DBITS) | d; }
 __device__ __forceinline__ uint2 m_unpack(mentry e) { const u32 l = e >> ALZ_M_DBITS; return make_uint2(e & ALZ_M_DMASK, l == ALZ_M_CAP ? ALZ_CAPPED : l); }
+
+// The rule of FindNextBestMatch (LzChainMatchFinder.cs:157-212) for a cursor at p whose match has l0 bytes and whose neighbour's (p + 1) has l1: what the
+// parse takes -- `kind` 0: a literal (:166-170), 1: the match here, 2: a literal and the neighbour's match (the lazy step, :175-190) -- and, returned, how far
+// the cursor goes: to the end of the taken match, but not behind the last searched position + 1 and at least over what was looked at (:195-203).
+// THE one copy: every walk (windows, segments, single cursors, the whole-GPU path) takes its decision here.
+__device__ __forceinline__ int parse_rule(const EncGeom& g, int limit, int p, int l0, int l1, int& kind) {
+    int jump = 1; kind = 0;
+    if (l0 >= g.min_len) {
+        const bool lazyc = l0 <= g.lazy && p + 1 <= limit;
+        if (lazyc && l1 > l0) { kind = 2; const int e = p + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 2 > stop ? p + 2 : stop) - p; }
+        else { kind = 1; const int skip = lazyc ? 1 : 0; const int e = p + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 1 + skip > stop ? p + 1 + skip : stop) - p; }
+    }
+    return jump;
+}
+// "the lazy rule looks at the neighbour" (:175-180): only then does l1 count above, and only then is p + 1 searched where a search costs something
+__device__ __forceinline__ bool parse_rule_needs_neighbour(const EncGeom& g, int limit, int p, int l0) { return l0 >= g.min_len && l0 <= g.lazy && p + 1 <= limit; }
 // GetMatchLength  LzChainMatchFinder.cs:338-357
 __device__ __forceinline__ int match_len(const u8* a, const u8* b, int max) {
     int len = 0;
@@ -591,14 +629,13 @@ __device__ __forceinline__ bool match_search(const u8* data, int n, int pos, con
 
 // ---- the exact search by a whole wavefront (wave-uniform control flow): what the parse kernels run when their cursor meets a position
 // kernel B (or the search inside the parse) had capped, and what the whole-GPU path of ONE stream runs for requested positions (alz_encode_big.h)
-__device__ __forceinline__ u32 benc_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ u32 benc_mbcnt(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
 __device__ __forceinline__ u32 benc_last(u32 incl) { return (u32)__builtin_amdgcn_readlane((int)incl, 63); }
 
 // GetMatchLength (LzChainMatchFinder.cs:338-357) by the whole wavefront: 4 KiB per trip -- four loads of sixteen bytes per lane and side in
 // flight (a trip may read up to 63 bytes behind `max`: inside the slack behind every source buffer, never counted)
 __device__ __forceinline__ int benc_wave_match_len(const u8* a, const u8* b, int max) {
-    const int lane = (int)benc_lane();
+    const int lane = lane_id();
     for (int base = 0; base < max; base += 4096) {
         u64 x[4][2];
 #pragma unroll
@@ -669,10 +706,65 @@ __device__ __forceinline__ void benc_capped_cursor(const u8* data, int n, const 
     s0 = c0;
     if (s0) benc_wave_search<MINT>(data, n, g, p4, pm, q, d0, l0); else { d0 = (int)e0.x; l0 = (int)e0.y; }
     d1 = 0; l1 = 0; s1 = false;
-    if (l0 >= g.min_len && l0 <= g.lazy && q + 1 <= limit) {
+    if (parse_rule_needs_neighbour(g, limit, q, l0)) {
         s1 = c1;
         if (s1) benc_wave_search<MINT>(data, n, g, p4, pm, q + 1, d1, l1); else { d1 = (int)e1.x; l1 = (int)e1.y; }
     }
+}
+// ... and what the parse does there: the exact matches as above (`mint`: the finder has the min-length table -- g.use_min_table, or the caller's own constant),
+// then the rule.  Returns the jump.  Where the exact results go -- registers, the match array and its tile, nowhere -- is the caller's.
+__device__ __forceinline__ int parse_capped_cursor(const u8* data, int n, const EncGeom& g, bool mint, const int* p4, const int* pm, int q, int limit, uint2 e0, bool c0, uint2 e1, bool c1,
+                                                   int& d0, int& l0, int& d1, int& l1, bool& s0, bool& s1, int& kind) {
+    if (mint) benc_capped_cursor<true>(data, n, g, p4, pm, q, limit, e0, c0, e1, c1, d0, l0, d1, l1, s0, s1);
+    else benc_capped_cursor<false>(data, n, g, p4, pm, q, limit, e0, c0, e1, c1, d0, l0, d1, l1, s0, s1);
+    return parse_rule(g, limit, q, l0, l1, kind);
+}
+
+// The walk over a window of 64 positions none of which is capped: a chain of "cursor += jump[cursor]" hops, ~18 per window.  Written in C++ each hop is three
+// v_readlane and ~30 scalar instructions, and with 32 waves per CU the walk was bound by the CU's one scalar unit (24.6 ms per 10 000 x 256 KiB) -- the
+// largest single item of the parse + emit kernels.  By hand a hop is five instructions: the visited lanes are collected as a bit mask (returned; the token
+// starts then follow from two ballots), `r` is the cursor relative to the window on entry (r < lim) and the first cursor at or behind `lim` on return.
+__device__ __forceinline__ u64 hop_walk_lim(int jump, u32& r, u32 lim) {
+    u64 M = 0; u32 j;
+    asm volatile(
+        "s_nop 3\n"
+        "1:\n\t"
+        "s_bitset1_b64 %[M], %[r]\n\t"
+        "v_readlane_b32 %[j], %[jump], %[r]\n\t"
+        "s_add_u32 %[r], %[r], %[j]\n\t"
+        "s_cmp_lt_u32 %[r], %[lim]\n\t"
+        "s_cbranch_scc1 1b\n\t"
+        : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
+        : [jump] "v"(jump), [lim] "s"(lim)
+        : "scc");
+    return M;
+}
+// A full window (lim = 64): the cursor runs 64 below zero, so that the add's carry IS "left the window" -- four instructions per hop (s_bitset1 and
+// v_readlane take the low six bits of it, which are the cursor's) --, and a hop is TWO tokens: jump2 = my jump + the jump of where it lands (one
+// ds_bpermute), so the scalar loop runs half as often.  It marks every second visited lane; the ones in between are where the marked lanes' own jumps
+// land: scattered through `hopmark` (64 bytes of LDS, zero on entry and on return).
+__device__ __forceinline__ u64 hop_walk_full(int jump, u32& r, int lane, u8* hopmark) {
+    u64 M = 0; u32 j;
+    const u32 tgt = (u32)lane + (u32)jump;                     // where my jump lands (>= 64: outside)
+    const int jn = __builtin_amdgcn_ds_bpermute((int)((tgt < 64u ? tgt : (u32)lane) << 2), jump);
+    const int jump2 = tgt < 64u ? jump + jn : jump;
+    r -= 64u;
+    asm volatile(
+        "s_nop 3\n"
+        "1:\n\t"
+        "s_bitset1_b64 %[M], %[r]\n\t"
+        "v_readlane_b32 %[j], %[jump], %[r]\n\t"
+        "s_add_u32 %[r], %[r], %[j]\n\t"
+        "s_cbranch_scc0 1b\n\t"
+        : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
+        : [jump] "v"(jump2)
+        : "scc");
+    r += 64u;
+    if (((M >> lane) & 1ull) && tgt < 64u) hopmark[tgt] = 1;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    const u32 hm = hopmark[lane];
+    if (hm) hopmark[lane] = 0;
+    return M | __ballot(hm != 0u);
 }
 
 // MatchSearch (:214-246, ChainMatches :248-282) exactly, by the whole wavefront, WITHOUT links (round 6): prev() chains are the positions below `pos` with pos's hash, nearest first,
@@ -742,7 +834,7 @@ __device__ __forceinline__ bool benc_scan_measure(const u8* data, const EncGeom&
 #define ALZ_SCAN_NEAR 2   /* (10 000 windows of Test.bmp at quality 8, ms per call, LZ4 blocks / raw Snappy: 1 -> 144.5 / 126.8, 2 -> 144.4 / 121.5, 4 -> 153.0 / 126.0, 8 -> 160.9 / 131.7; every block: 263.7 / 162.0) */
 #endif
 __device__ __forceinline__ int benc_wave_scan_search(const u8* data, int n, const EncGeom& g, int pos, int& best_d, int& best_l, unsigned short* cl, const int* p4 = nullptr) {
-    const int lane = (int)benc_lane();
+    const int lane = lane_id();
     const u8* dp = data + pos;
     const u32 sh = 32u - (u32)g.hash_bits;
     const u32 own = load32(dp) * 2654435761u;
@@ -813,8 +905,6 @@ __device__ __forceinline__ int benc_wave_scan_search(const u8* data, int n, cons
     return blocks;
 }
 
-__device__ __forceinline__ u32 benc_lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
 // The same function as kernel B runs it (the exact recomputations inside the roles / emit kernels keep the plain form above: the
 // serial emit kernels, one lane per wavefront, ran 12 % slower with this body inlined).  MatchSearch :214-246 with ChainMatches
 // :248-282; returns false when CAP > 0 and a
@@ -871,7 +961,7 @@ __device__ __forceinline__ bool match_search_b(const u8* data, int n, int pos, c
             // (all 64 lanes here; classes of eight or more lanes with one distance, one class after the other while there are such; nobody compares more than
             // the 512 - 63 bytes the bits reach)
             u64 todo = __ballot(ok && cmp_max <= 448);
-            const int lane = (int)benc_lane_id();
+            const int lane = lane_id();
             if (__ballot(true) == ~0ull)
             while (__popcll(todo) >= 8) {
                 const int d0 = __builtin_amdgcn_readlane(dist, (int)__builtin_ctzll(todo));
@@ -1393,6 +1483,9 @@ __device__ void lz4_ext(Out& o, int length) {                // LZ4.WriteExtensi
     if (length >= 0) { int b; do { b = length < 0xFF ? length : 0xFF; o.put((u32)b); length -= b; } while (b == 0xFF); }
 }
 __device__ void lzo_ext(Out& o, int v) { while (v > 255) { o.put(0); v -= 255; } o.put((u32)v); }   // LZO.WriteExtendedInt
+// ... and the bytes the two write, for the emitters that size their tokens by prefix sums before they write them (SeqFmt)
+__device__ __forceinline__ u32 lz4_extn(u32 v) { return v >= 15u ? 1u + (v - 15u) / 255u : 0u; }    // bytes of LZ4.WriteExtension  LZ4.cs:254-268
+__device__ __forceinline__ u32 lzo_extn(u32 v) { return 1u + (v - 1u) / 255u; }                       // bytes of LZO.WriteExtendedInt(v), v >= 1
 
 template <int FMT>
 __global__ __launch_bounds__(64) void enc_emit_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base,
@@ -1821,26 +1914,6 @@ __global__ __launch_bounds__(64) void enc_emit_kernel(const u8* __restrict__ src
 //    offsets.  Token lanes store their payload bytes; flag bytes are accumulated in LDS and stored when their group
 //    completes.  FlagWriter order (IO/FlagWriter.cs:70-80,111-127): flag byte, then the payload of its 8 tokens.
 
-__device__ __forceinline__ u32 scan_add(u32 v) {            // inclusive wave prefix sum (gfx9 DPP)
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-    return v;
-}
-__device__ __forceinline__ u32 scan_max(u32 v) {            // inclusive wave prefix max
-    u32 t;
-    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false); v = v > t ? v : t;
-    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false); v = v > t ? v : t;
-    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false); v = v > t ? v : t;
-    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false); v = v > t ? v : t;
-    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false); v = v > t ? v : t;
-    t = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false); v = v > t ? v : t;
-    return v;
-}
-
 // SEGS (alz_encode_seg.h): the grid's x is a segment of the stream; the walk runs from that segment's synchronisation point (a position every
 // walk lands on, enc_sync_kernel) to the next segment's -- several wavefronts per stream, each exact.  Mask words are OR-ed into memory: the window
 // that holds a synchronisation point is written from both sides (the same bits where they overlap).
@@ -1922,13 +1995,7 @@ __global__ __launch_bounds__(64) void enc_roles_kernel(const u8* __restrict__ sr
             // cursor's two entries come from the tile at a uniform address.  Back to windows at the first short jump or capped entry.
             const uint2 ca = m_unpack(tile[cur - tbase]), cb = m_unpack(tile[cur + 1 - tbase]);
             if (ca.y != ALZ_CAPPED && cb.y != ALZ_CAPPED) {
-                int cj = 1, csr = 0;
-                if ((int)ca.y >= g.min_len) {
-                    const int l0 = (int)ca.y, l1 = (int)cb.y;
-                    const bool lazyc = l0 <= g.lazy && cur + 1 <= limit;
-                    if (lazyc && l1 > l0) { csr = 2; const int e = cur + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; cj = (cur + 2 > stop ? cur + 2 : stop) - cur; }
-                    else { csr = 1; const int skip = lazyc ? 1 : 0; const int e = cur + l0; const int stop = e < limit + 1 ? e : limit + 1; cj = (cur + 1 + skip > stop ? cur + 1 + skip : stop) - cur; }
-                }
+                int csr, cj = parse_rule(g, limit, cur, (int)ca.y, (int)cb.y, csr);
                 cj = __builtin_amdgcn_readfirstlane(cj); csr = __builtin_amdgcn_readfirstlane(csr);
                 if (carry_in && lane == 0) put_mask((u32)P >> 6, 1ull);
                 if (csr && lane == 0) { const u32 bp = (u32)cur + (csr == 2 ? 1u : 0u); put_mask(bp >> 6, 1ull << (bp & 63u)); }
@@ -1943,58 +2010,15 @@ __global__ __launch_bounds__(64) void enc_roles_kernel(const u8* __restrict__ sr
         const uint2 a = m_unpack(tile[P - tbase + lane]);
         const uint2 b = m_unpack(tile[P - tbase + lane + 1]);
         const bool capped = a.y == ALZ_CAPPED || b.y == ALZ_CAPPED;
-        int jump = 1, startrel = 0;   // startrel: 0 no token here, 1 match starts here, 2 literal here + match at p + 1
-        if (!capped && p <= limit && (int)a.y >= g.min_len) {
-            const int l0 = (int)a.y, l1 = (int)b.y;
-            const bool lazyc = l0 <= g.lazy && p + 1 <= limit;
-            if (lazyc && l1 > l0) { startrel = 2; const int e = p + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 2 > stop ? p + 2 : stop) - p; }
-            else { startrel = 1; const int skip = lazyc ? 1 : 0; const int e = p + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 1 + skip > stop ? p + 1 + skip : stop) - p; }
-        }
+        int jump = 1, startrel = 0;   // startrel: the rule's kind -- 0 no token here, 1 match starts here, 2 literal here + match at p + 1
+        if (!capped && p <= limit) jump = parse_rule(g, limit, p, (int)a.y, (int)b.y, startrel);
         u64 bits = carry_in ? 1ull : 0ull;
         int rel = cur - P;
-        // The walk over the window: a chain of "cursor += jump[cursor]" hops, ~18 per window.  Written in C++ each hop is three
-        // v_readlane and ~30 scalar instructions, and with 32 waves per CU the kernel was bound by the CU's one scalar unit
-        // (24.6 ms per 10 000 x 256 KiB).  Without capped candidates in the window the hop is five instructions: the visited lanes
-        // are collected as a bit mask, and the token starts follow from two ballots.
         if (__ballot(capped) == 0) {
-            u64 M = 0; u32 r = (u32)rel, j;
+            // (no capped candidate in the window: the hops by hand, the token starts from two ballots over the visited lanes)
+            u32 r = (u32)rel;
             const u32 lim = (u32)(limit + 1 - P) < 64u ? (u32)(limit + 1 - P) : 64u;     // (r < lim on entry: cur <= limit)
-            if (lim == 64u) {
-                // a full window: the cursor runs 64 below zero, so that the add's carry IS "left the window" -- four instructions per hop
-                // (s_bitset1 and v_readlane take the low six bits of it, which are the cursor's) -- and a hop is TWO tokens: jump2 = my
-                // jump + the jump of where it lands; the lanes in between are where the marked lanes' own jumps land (enc_parse_emit_kernel)
-                const u32 tgt = (u32)lane + (u32)jump;
-                const int jn = __builtin_amdgcn_ds_bpermute((int)((tgt < 64u ? tgt : (u32)lane) << 2), jump);
-                const int jump2 = tgt < 64u ? jump + jn : jump;
-                r -= 64u;
-                asm volatile(
-                    "s_nop 3\n"
-                    "1:\n\t"
-                    "s_bitset1_b64 %[M], %[r]\n\t"
-                    "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                    "s_add_u32 %[r], %[r], %[j]\n\t"
-                    "s_cbranch_scc0 1b\n\t"
-                    : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                    : [jump] "v"(jump2)
-                    : "scc");
-                r += 64u;
-                if (((M >> lane) & 1ull) && tgt < 64u) hopmark[tgt] = 1;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-                const u32 hm = hopmark[lane];
-                if (hm) hopmark[lane] = 0;
-                M |= __ballot(hm != 0u);
-            } else
-            asm volatile(
-                "s_nop 3\n"
-                "1:\n\t"
-                "s_bitset1_b64 %[M], %[r]\n\t"
-                "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                "s_add_u32 %[r], %[r], %[j]\n\t"
-                "s_cmp_lt_u32 %[r], %[lim]\n\t"
-                "s_cbranch_scc1 1b\n\t"
-                : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                : [jump] "v"(jump), [lim] "s"(lim)
-                : "scc");
+            const u64 M = lim == 64u ? hop_walk_full(jump, r, lane, hopmark) : hop_walk_lim(jump, r, lim);
             const u64 s1 = __ballot(startrel == 1) & M, s2 = __ballot(startrel == 2) & M;
             bits |= s1 | (s2 << 1);
             if (s2 >> 63) carryw = ((u32)P >> 6) + 1u;                         // start in lane 0 of the next window
@@ -2009,14 +2033,7 @@ __global__ __launch_bounds__(64) void enc_roles_kernel(const u8* __restrict__ sr
                 int d0, l0, d1 = 0, l1 = 0; bool s0, s1;
                 // (by the whole wavefront, 4 KiB per trip: as a plain loop on every lane a match of a few hundred bytes took ~10 us per cursor)
                 const uint2 e0 = m_unpack(tile[q - tbase]), e1 = m_unpack(tile[q + 1 - tbase]);
-                if (g.use_min_table) benc_capped_cursor<true>(data, n, g, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1);
-                else benc_capped_cursor<false>(data, n, g, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1);
-                j = 1; sr = 0;
-                if (l0 >= g.min_len) {
-                    const bool lazyc = l0 <= g.lazy && q + 1 <= limit;
-                    if (lazyc && l1 > l0) { sr = 2; const int e = q + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; j = (q + 2 > stop ? q + 2 : stop) - q; }
-                    else { sr = 1; const int skip = lazyc ? 1 : 0; const int e = q + l0; const int stop = e < limit + 1 ? e : limit + 1; j = (q + 1 + skip > stop ? q + 1 + skip : stop) - q; }
-                }
+                j = parse_capped_cursor(data, n, g, g.use_min_table != 0, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1, sr);
                 // The exact results go back into the array: the match that is TAKEN in full (the emitters read it; 2 046 bytes or more: the
                 // length in the next entry, a position inside the match), the other one as far as an entry holds it -- q's is never looked
                 // at again, q + 1's is if the walk goes there next, and stays "capped" (recomputed then) when it is too long for an entry.
@@ -2075,14 +2092,8 @@ __global__ __launch_bounds__(64) void enc_sync_kernel(const alz_stream* __restri
     for (int P = x0; P < S; P += 64) {
         const int p = P + lane;
         const uint2 a = ldm(p), b = ldm(p + 1);
-        int jump = 1;
-        if (a.y == ALZ_CAPPED || b.y == ALZ_CAPPED) jump = 0x40000000;
-        else if ((int)a.y >= g.min_len) {                               // (p < S <= limit: searched)
-            const int l0 = (int)a.y, l1 = (int)b.y;
-            const bool lazyc = l0 <= g.lazy && p + 1 <= limit;
-            if (lazyc && l1 > l0) { const int e = p + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 2 > stop ? p + 2 : stop) - p; }
-            else { const int skip = lazyc ? 1 : 0; const int e = p + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 1 + skip > stop ? p + 1 + skip : stop) - p; }
-        }
+        int kind;
+        const int jump = (a.y == ALZ_CAPPED || b.y == ALZ_CAPPED) ? 0x40000000 : parse_rule(g, limit, p, (int)a.y, (int)b.y, kind);   // (p < S <= limit: searched)
         const u32 incl = scan_max((u32)(p + jump));
         u32 excl = (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x138, 0xF, 0xF, false);     // wave_shr:1 -> max over the lanes below
         if (excl < pmx) excl = pmx;
@@ -2095,8 +2106,26 @@ __global__ __launch_bounds__(64) void enc_sync_kernel(const alz_stream* __restri
     if (lane == 0) *out = best;
 }
 
+// ---- the flag-bit formats (FlagWriter, IO/FlagWriter.cs:13-147): what every emitter of theirs shares -- the batch kernels below, the segments
+// (alz_encode_seg.h), the whole-GPU path of ONE stream (alz_encode_big.h)
+template <int FMT> struct FlagFmt {
+    static constexpr bool THREE = (FMT == ALZ_FMT_YAY0 || FMT == ALZ_FMT_MIO0);                                       // flags, tokens and literals in three sections
+    static constexpr bool LIT_BIT = (FMT == ALZ_FMT_LZSS || FMT == ALZ_FMT_YAZ0 || FMT == ALZ_FMT_LZHUDSON || THREE);   // flag bit of a literal token
+    static constexpr bool MSB = (FMT != ALZ_FMT_LZSS && FMT != ALZ_FMT_CLZ0);                                         // the first token's bit is the highest
+    static constexpr u32 FBITS = FMT == ALZ_FMT_LZHUDSON ? 32u : 8u, FB = FBITS / 8u;    // LZHudson: Yay0's tokens behind 32-bit big-endian flag words  LZHudson.cs:55-59
+    static __device__ __forceinline__ u32 bit(bool lit, u32 bitpos) { return (lit ? LIT_BIT : !LIT_BIT) ? 1u << (MSB ? FBITS - 1u - bitpos : bitpos) : 0u; }
+};
+// a finished flag word to its place: one byte (negated for LZ40) or, LZHudson, four big-endian; false: no room
+template <int FMT>
+__device__ __forceinline__ bool put_flag_word(u8* dst, u32 fo, u32 acc, u32 cap) {
+    constexpr u32 FB = FlagFmt<FMT>::FB;
+    if (fo + FB > cap) return false;
+    if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc);
+    else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; }
+    return true;
+}
+
 // The payload bytes of a match token of the flag-bit formats: `mt` = (distance, length) of the match that starts at position p.
-// (Shared by the batch kernel below and the whole-GPU path of ONE stream, alz_encode_big.h.)
 template <int FMT>
 __device__ __forceinline__ void flag_payload(const EncGeom& g, u32 p, uint2 mt, u32& b0, u32& b1, u32& b2, u32& b3, u32& psize) {
     const u32 d1 = (mt.x - 1u) & 0xFFFu, len = mt.y;
@@ -2125,6 +2154,56 @@ __device__ __forceinline__ void flag_payload(const EncGeom& g, u32 p, uint2 mt, 
     }
 }
 
+// Up to 64 tokens, one per lane, laid out by prefix sums (IO/FlagWriter.cs:70-80,111-127: a flag word, then the payload of its tokens).
+//   tok, lit: my lane has a token / it is a literal;  ti: its number (-> flag group and bit);  b0-b3: its bytes
+//   psize, poff: its bytes in the payload (THREE: the token section) and where they start, counted without the flag words
+//   usize, uoff: THREE -- its byte in the literal section (a literal, Yay0's long-length byte)
+//   ntok, psum, usum: what the 64 lanes add to the three running bases;  pmax: the inclusive prefix maximum of the match ends (flag_window)
+struct FlagToks {
+    bool tok, lit; u32 ti, b0, b1, b2, b3, psize, usize, poff, uoff, ntok, psum, usum, pmax;
+    __device__ __forceinline__ void advance(u32& tok_base, u32& pay_base, u32& unc_base, u32& cover) const {     // the running bases behind a window
+        tok_base += ntok; pay_base += psum; unc_base += usum;
+        const u32 wmax = (u32)__builtin_amdgcn_readlane((int)pmax, 63);
+        if (wmax > cover) cover = wmax;
+    }
+};
+// ... bytes, sections and the two scans of my token: a literal of byte `sb`, or (`start`) the match `mt` at position p
+template <int FMT>
+__device__ __forceinline__ void flag_token_bytes(const EncGeom& g, FlagToks& w, u32 p, bool start, uint2 mt, u32 sb, u32 pay_base, u32 unc_base) {
+    constexpr bool THREE = FlagFmt<FMT>::THREE;
+    w.b0 = 0; w.b1 = 0; w.b2 = 0; w.b3 = 0; w.psize = 0; w.usize = 0;
+    if (w.lit) { w.b0 = sb; w.psize = 1; }
+    else if (start) flag_payload<FMT>(g, p, mt, w.b0, w.b1, w.b2, w.b3, w.psize);
+    if (THREE) {   // literals (and Yay0's long-length byte) live in their own section
+        if (w.lit) { w.usize = 1; w.psize = 0; }
+        else if (start && FMT == ALZ_FMT_YAY0 && w.psize == 3) { w.usize = 1; w.psize = 2; }
+    }
+    const u32 pincl = scan_add(w.psize);
+    w.poff = pay_base + pincl - w.psize;
+    const u32 uincl = THREE ? scan_add(w.usize) : 0u;
+    w.uoff = unc_base + uincl - w.usize;
+    w.psum = (u32)__builtin_amdgcn_readlane((int)pincl, 63);
+    w.usum = THREE ? (u32)__builtin_amdgcn_readlane((int)uincl, 63) : 0u;
+}
+// The tokens of one window of 64 POSITIONS (p = P + lane): the lanes where a match starts (`start`, the match `mt`), and the positions no match
+// covers -- behind `cover`, the end of the last match seen before the window, and behind every match that starts in front of them in it -- as
+// literals of their source byte `sb`.  Prefix sums over the start mask give every token its flag group and byte offset.
+template <int FMT>
+__device__ __forceinline__ FlagToks flag_window(const EncGeom& g, u32 p, u32 n, bool start, uint2 mt, u32 sb, u32 cover, u32 tok_base, u32 pay_base, u32 unc_base) {
+    FlagToks w;
+    const u32 mend = start ? p + mt.y : 0u;
+    w.pmax = scan_max(mend);                                         // inclusive
+    u32 before = (u32)__builtin_amdgcn_update_dpp(0, (int)w.pmax, 0x138, 0xF, 0xF, false);   // wave_shr:1 -> max over lanes below
+    if (before < cover) before = cover;
+    w.lit = !start && p < n && p >= before;
+    w.tok = start || w.lit;
+    const u64 tm = __ballot(w.tok);
+    w.ti = tok_base + __builtin_amdgcn_mbcnt_hi((u32)(tm >> 32), __builtin_amdgcn_mbcnt_lo((u32)tm, 0u));
+    w.ntok = (u32)__popcll(tm);
+    flag_token_bytes<FMT>(g, w, p, start, mt, sb, pay_base, unc_base);
+    return w;
+}
+
 // The parse and the emitter of the flag-bit formats in ONE kernel (round 3): enc_roles_kernel's walk over a window of 64 positions, then
 // the emitter's tokens of the same window, from the same registers.  As two kernels the parse wrote a start mask and the exact
 // matches it had recomputed, and the emitter read mask and match array again: 10.5 GB of the 53 the pipeline moved at quality 0, and
@@ -2138,16 +2217,16 @@ __device__ __forceinline__ void flag_payload(const EncGeom& g, u32 p, uint2 mt, 
 // are the links and the positions' own bytes of window w + 3: no match array at all (10.5 GB written, 13 GB read at quality 0),
 // and the search runs at the parse's instruction rate instead of waiting for its own loads (0.75 instructions per cycle as a kernel).
 // 32 bytes per side are compared from the prefetched registers; a longer match finishes in memory.
+// The window walk and the look-ahead stages are this kernel's own text, not struct WinParse's (which repeats them for the sequence kernels): on the struct the
+// SEARCH form of this kernel took 74-76 VGPRs instead of 70-72 -- six wavefronts per SIMD instead of seven (docs/EXPERIMENTS.md 25).  The rule, the hops and the
+// capped cursor inside it are the shared functions.
 template <int FMT, bool SEARCH>
 __global__ __launch_bounds__(64) void enc_parse_emit_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base,
                                                             const alz_stream* __restrict__ streams, const u32* __restrict__ index_list,
                                                             u32 count, const mentry* __restrict__ match, const u64* __restrict__ pos_off,
                                                             const int* __restrict__ prev4, const int* __restrict__ prevm, u8* __restrict__ side,
                                                             alz_result* __restrict__ results, alz_encode_aux* __restrict__ aux, EncGeom g) {
-    constexpr bool THREE = (FMT == ALZ_FMT_YAY0 || FMT == ALZ_FMT_MIO0);
-    constexpr bool LIT_BIT = (FMT == ALZ_FMT_LZSS || FMT == ALZ_FMT_YAZ0 || FMT == ALZ_FMT_LZHUDSON || THREE);   // flag bit of a literal token
-    constexpr bool MSB = (FMT != ALZ_FMT_LZSS && FMT != ALZ_FMT_CLZ0);
-    constexpr u32 FBITS = FMT == ALZ_FMT_LZHUDSON ? 32u : 8u, FB = FBITS / 8u;    // LZHudson: Yay0's tokens behind 32-bit big-endian flag words  LZHudson.cs:55-59
+    typedef FlagFmt<FMT> F;
     __shared__ u32 flagacc[16];
     __shared__ u32 gofs[16];
     __shared__ u8 hopmark[64];
@@ -2167,13 +2246,13 @@ __global__ __launch_bounds__(64) void enc_parse_emit_kernel(const u8* __restrict
     const mentry* m = match + pos_off[sid];
     const int* p4 = prev4 + pos_off[sid];
     const int* pm = g.use_min_table ? prevm + pos_off[sid] : nullptr;
-    u8* compb = THREE ? side + 2 * pos_off[sid] : nullptr;            // token section (Yay0/MIO0)
-    u8* uncb = THREE ? side + 2 * pos_off[sid] + n + 16 : nullptr;    // literal section
+    u8* compb = F::THREE ? side + 2 * pos_off[sid] : nullptr;            // token section (Yay0/MIO0)
+    u8* uncb = F::THREE ? side + 2 * pos_off[sid] + n + 16 : nullptr;    // literal section
     if (lane < 16) { flagacc[lane] = 0; gofs[lane] = 0; }
     __syncthreads();
     u32 tok_base = 0;       // tokens emitted before the window
-    u32 pay_base = 0;       // payload bytes before the window (THREE: token-section bytes)
-    u32 unc_base = 0;       // THREE: literal-section bytes before the window
+    u32 pay_base = 0;       // payload bytes before the window (F::THREE: token-section bytes)
+    u32 unc_base = 0;       // F::THREE: literal-section bytes before the window
     u32 cover = 0;          // end of the last match seen so far
     bool fail = false;
     int cur = 0;            // cursor of FindNextBestMatch (absolute position)
@@ -2257,54 +2336,13 @@ __global__ __launch_bounds__(64) void enc_parse_emit_kernel(const u8* __restrict
                 if (lane == 63) b = make_uint2(n0x, n0y);
             }
             const bool capped = a.y == ALZ_CAPPED || b.y == ALZ_CAPPED;
-            int jump = 1, startrel = 0;   // startrel: 0 no token here, 1 match starts here, 2 literal here + match at p + 1
-            if (!capped && (int)p <= limit && (int)a.y >= g.min_len) {
-                const int l0 = (int)a.y, l1 = (int)b.y, pi = (int)p;
-                const bool lazyc = l0 <= g.lazy && pi + 1 <= limit;
-                if (lazyc && l1 > l0) { startrel = 2; const int e = pi + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (pi + 2 > stop ? pi + 2 : stop) - pi; }
-                else { startrel = 1; const int skip = lazyc ? 1 : 0; const int e = pi + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (pi + 1 + skip > stop ? pi + 1 + skip : stop) - pi; }
-            }
+            int jump = 1, startrel = 0;   // startrel: the rule's kind -- 0 no token here, 1 match starts here, 2 literal here + match at p + 1
+            if (!capped && (int)p <= limit) jump = parse_rule(g, limit, (int)p, (int)a.y, (int)b.y, startrel);
             int rel = cur - (int)P;
             if (__ballot(capped) == 0) {
-                u64 M = 0; u32 r = (u32)rel, j;
+                u32 r = (u32)rel;
                 const u32 lim = (u32)(limit + 1 - (int)P) < 64u ? (u32)(limit + 1 - (int)P) : 64u;     // (r < lim on entry: cur <= limit)
-                if (lim == 64u) {
-                    // Two tokens per hop: jump2 = my jump + the jump of where it lands (one ds_bpermute), so the scalar loop -- four
-                    // instructions per hop, ~18 tokens per window: the largest single item of this kernel -- runs half as often.  It
-                    // marks every second visited lane; the ones in between are where the marked lanes' own jumps land: scattered
-                    // through 64 bytes of LDS.  (The add's carry is "left the window": enc_roles_kernel.)
-                    const u32 tgt = (u32)lane + (u32)jump;                     // where my jump lands (>= 64: outside)
-                    const int jn = __builtin_amdgcn_ds_bpermute((int)((tgt < 64u ? tgt : (u32)lane) << 2), jump);
-                    const int jump2 = tgt < 64u ? jump + jn : jump;
-                    r -= 64u;
-                    asm volatile(
-                        "s_nop 3\n"
-                        "1:\n\t"
-                        "s_bitset1_b64 %[M], %[r]\n\t"
-                        "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                        "s_add_u32 %[r], %[r], %[j]\n\t"
-                        "s_cbranch_scc0 1b\n\t"
-                        : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                        : [jump] "v"(jump2)
-                        : "scc");
-                    r += 64u;
-                    if (((M >> lane) & 1ull) && tgt < 64u) hopmark[tgt] = 1;
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-                    const u32 hm = hopmark[lane];
-                    if (hm) hopmark[lane] = 0;
-                    M |= __ballot(hm != 0u);
-                } else
-                asm volatile(
-                    "s_nop 3\n"
-                    "1:\n\t"
-                    "s_bitset1_b64 %[M], %[r]\n\t"
-                    "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                    "s_add_u32 %[r], %[r], %[j]\n\t"
-                    "s_cmp_lt_u32 %[r], %[lim]\n\t"
-                    "s_cbranch_scc1 1b\n\t"
-                    : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                    : [jump] "v"(jump), [lim] "s"(lim)
-                    : "scc");
+                const u64 M = lim == 64u ? hop_walk_full(jump, r, lane, hopmark) : hop_walk_lim(jump, r, lim);
                 const u64 s1 = __ballot(startrel == 1) & M, s2 = __ballot(startrel == 2) & M;
                 sm |= s1 | (s2 << 1);
                 if (s2 >> 63) carry = true;                                    // start in lane 0 of the next window
@@ -2320,18 +2358,11 @@ __global__ __launch_bounds__(64) void enc_parse_emit_kernel(const u8* __restrict
                     const uint2 e0 = make_uint2((u32)__builtin_amdgcn_readlane((int)a.x, rel), (u32)__builtin_amdgcn_readlane((int)a.y, rel));
                     const uint2 e1 = rel + 1 < 64 ? make_uint2((u32)__builtin_amdgcn_readlane((int)a.x, (rel + 1) & 63), (u32)__builtin_amdgcn_readlane((int)a.y, (rel + 1) & 63))
                                                   : make_uint2((u32)__builtin_amdgcn_readlane((int)a_n.x, 0), (u32)__builtin_amdgcn_readlane((int)a_n.y, 0));
-                    if (g.use_min_table) benc_capped_cursor<true>(data, (int)n, g, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1);
-                    else benc_capped_cursor<false>(data, (int)n, g, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1);
+                    j = parse_capped_cursor(data, (int)n, g, g.use_min_table != 0, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1, sr);
                     if (s0 && lane == rel) a = make_uint2((u32)d0, (u32)l0);
                     if (s1) {
                         if (rel + 1 < 64) { if (lane == rel + 1) a = make_uint2((u32)d1, (u32)l1); }
                         else if (lane == 0) a_n = make_uint2((u32)d1, (u32)l1);
-                    }
-                    j = 1; sr = 0;
-                    if (l0 >= g.min_len) {
-                        const bool lazyc = l0 <= g.lazy && q + 1 <= limit;
-                        if (lazyc && l1 > l0) { sr = 2; const int e = q + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; j = (q + 2 > stop ? q + 2 : stop) - q; }
-                        else { sr = 1; const int skip = lazyc ? 1 : 0; const int e = q + l0; const int stop = e < limit + 1 ? e : limit + 1; j = (q + 1 + skip > stop ? q + 1 + skip : stop) - q; }
                     }
                 } else {
                     j = __builtin_amdgcn_readlane(jump, rel);
@@ -2343,71 +2374,38 @@ __global__ __launch_bounds__(64) void enc_parse_emit_kernel(const u8* __restrict
             }
             cur = (int)P + rel;
         }
-        // ---- the tokens of this window: prefix sums over the start mask give every token its flag group and byte offset
+        // ---- the tokens of this window
         const bool start = ((sm >> lane) & 1ull) && p < n;
-        uint2 mt = make_uint2(0, 0);
-        if (start) mt = a;
-        const u32 mend = start ? p + mt.y : 0u;
-        const u32 pmax = scan_max(mend);                               // inclusive
-        u32 before = (u32)__builtin_amdgcn_update_dpp(0, (int)pmax, 0x138, 0xF, 0xF, false);   // wave_shr:1 -> max over lanes below
-        if (before < cover) before = cover;
-        const bool lit = !start && p < n && p >= before;
-        const bool tok = start || lit;
-        const u64 tm = __ballot(tok);
-        const u32 ti = tok_base + __builtin_amdgcn_mbcnt_hi((u32)(tm >> 32), __builtin_amdgcn_mbcnt_lo((u32)tm, 0u));
-        // payload of my token
-        u32 b0 = 0, b1 = 0, b2 = 0, b3 = 0, psize = 0, usize = 0;
-        if (lit) { b0 = sb; psize = 1; }
-        else if (start) flag_payload<FMT>(g, p, mt, b0, b1, b2, b3, psize);
-        if (THREE) {   // literals (and Yay0's long-length byte) live in their own section
-            if (lit) { usize = 1; psize = 0; }
-            else if (start && FMT == ALZ_FMT_YAY0 && psize == 3) { usize = 1; psize = 2; }
-        }
-        const u32 pincl = scan_add(psize);
-        const u32 poff = pay_base + pincl - psize;
-        const u32 uincl = THREE ? scan_add(usize) : 0u;
-        const u32 uoff = unc_base + uincl - usize;
-        const u32 group = ti / FBITS, bitpos = ti % FBITS;
+        const FlagToks w = flag_window<FMT>(g, p, n, start, start ? a : make_uint2(0, 0), sb, cover, tok_base, pay_base, unc_base);
+        const u32 group = w.ti / F::FBITS, bitpos = w.ti % F::FBITS;
         // flag bytes: the first token of a group fixes the flag byte's position, the last one stores it
-        const u32 flag_off = THREE ? group : poff + FB * group;        // interleaved: flag g sits right before the payload of its first token
-        if (tok && bitpos == 0) { gofs[group & 15u] = flag_off; flagacc[group & 15u] = 0; }
+        const u32 flag_off = F::THREE ? group : w.poff + F::FB * group;      // interleaved: flag g sits right before the payload of its first token
+        if (w.tok && bitpos == 0) { gofs[group & 15u] = flag_off; flagacc[group & 15u] = 0; }
         __syncthreads();
-        if (tok) {
-            const u32 bitv = (lit ? LIT_BIT : !LIT_BIT) ? 1u : 0u;
-            if (bitv) atomicOr(&flagacc[group & 15u], 1u << (MSB ? FBITS - 1u - bitpos : bitpos));
-        }
+        if (w.tok) { const u32 bitv = F::bit(w.lit, bitpos); if (bitv) atomicOr(&flagacc[group & 15u], bitv); }
         __syncthreads();
-        if (tok) {
-            if (bitpos == FBITS - 1u) {
-                const u32 fo = gofs[group & 15u], acc = flagacc[group & 15u];
-                if (fo + FB <= cap) { if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc); else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; } }
-                else fail = true;
-            }
-            if (!THREE) {
-                const u32 o = poff + FB * (group + 1u);
-                if (o + psize <= cap) { dst[o] = (u8)b0; if (psize > 1) dst[o + 1] = (u8)b1; if (psize > 2) dst[o + 2] = (u8)b2; if (psize > 3) dst[o + 3] = (u8)b3; }
+        if (w.tok) {
+            if (bitpos == F::FBITS - 1u && !put_flag_word<FMT>(dst, gofs[group & 15u], flagacc[group & 15u], cap)) fail = true;
+            if (!F::THREE) {
+                const u32 o = w.poff + F::FB * (group + 1u);
+                if (o + w.psize <= cap) { dst[o] = (u8)w.b0; if (w.psize > 1) dst[o + 1] = (u8)w.b1; if (w.psize > 2) dst[o + 2] = (u8)w.b2; if (w.psize > 3) dst[o + 3] = (u8)w.b3; }
                 else fail = true;
             } else {
-                if (lit) uncb[uoff] = (u8)b0;
-                else { compb[poff] = (u8)b0; compb[poff + 1] = (u8)b1; if (usize) uncb[uoff] = (u8)b2; }
+                if (w.lit) uncb[w.uoff] = (u8)w.b0;
+                else { compb[w.poff] = (u8)w.b0; compb[w.poff + 1] = (u8)w.b1; if (w.usize) uncb[w.uoff] = (u8)w.b2; }
             }
         }
         __syncthreads();
-        tok_base += (u32)__popcll(tm);
-        pay_base += (u32)__builtin_amdgcn_readlane((int)pincl, 63);
-        if (THREE) unc_base += (u32)__builtin_amdgcn_readlane((int)uincl, 63);
-        const u32 wmax = (u32)__builtin_amdgcn_readlane((int)pmax, 63);
-        if (wmax > cover) cover = wmax;
+        w.advance(tok_base, pay_base, unc_base, cover);
     }
     // Dispose(): a partial flag byte is written with its unused bits zero (FlagWriter.cs:141-145)
-    const u32 nflags = FB * ((tok_base + FBITS - 1u) / FBITS);          // (bytes)
-    if ((tok_base % FBITS) != 0 && lane == 0) {
-        const u32 gi = tok_base / FBITS; const u32 fo = gofs[gi & 15u], acc = flagacc[gi & 15u];
-        if (fo + FB <= cap) { if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc); else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; } }
-        else fail = true;
+    const u32 nflags = F::FB * ((tok_base + F::FBITS - 1u) / F::FBITS);          // (bytes)
+    if ((tok_base % F::FBITS) != 0 && lane == 0) {
+        const u32 gi = tok_base / F::FBITS;
+        if (!put_flag_word<FMT>(dst, gofs[gi & 15u], flagacc[gi & 15u], cap)) fail = true;
     }
     u32 total;
-    if (!THREE) total = pay_base + nflags;
+    if (!F::THREE) total = pay_base + nflags;
     else {
         total = nflags + pay_base + unc_base;
         if (total <= cap) {
@@ -2421,7 +2419,7 @@ __global__ __launch_bounds__(64) void enc_parse_emit_kernel(const u8* __restrict
     if (lane == 0) {
         alz_result r; r.dst_len = anyfail ? 0u : total; r.src_used = n; r.status = anyfail ? ALZ_ST_OUTPUT_CAPACITY : ALZ_ST_OK; r.reserved = 0;
         results[sid] = r;
-        if (!THREE && aux) { aux[sid].aux0 = 0; aux[sid].aux1 = 0; }
+        if (!F::THREE && aux) { aux[sid].aux0 = 0; aux[sid].aux1 = 0; }
     }
 }
 
@@ -2435,10 +2433,7 @@ template <int FMT>
 __global__ __launch_bounds__(64) void enc_scan_emit_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
                                                            const u32* __restrict__ index_list, u32 count, const u64* __restrict__ pos_off, u8* __restrict__ side,
                                                            alz_result* __restrict__ results, alz_encode_aux* __restrict__ aux, EncGeom g) {
-    constexpr bool THREE = (FMT == ALZ_FMT_YAY0 || FMT == ALZ_FMT_MIO0);
-    constexpr bool LIT_BIT = (FMT == ALZ_FMT_LZSS || FMT == ALZ_FMT_YAZ0 || FMT == ALZ_FMT_LZHUDSON || THREE);   // flag bit of a literal token
-    constexpr bool MSB = (FMT != ALZ_FMT_LZSS && FMT != ALZ_FMT_CLZ0);
-    constexpr u32 FBITS = FMT == ALZ_FMT_LZHUDSON ? 32u : 8u, FB = FBITS / 8u;
+    typedef FlagFmt<FMT> F;
     __shared__ u32 flagacc[16];
     __shared__ u32 gofs[16];
     __shared__ unsigned short candl[64];
@@ -2453,8 +2448,8 @@ __global__ __launch_bounds__(64) void enc_scan_emit_kernel(const u8* __restrict_
     const int limit = (int)n - 4;                                        // FindNextBestMatch searches up to length - 4  :159
     u8* dst = dst_base + st.dst_off;
     const u32 cap = st.dst_cap;
-    u8* compb = THREE ? side + 2 * pos_off[sid] : nullptr;            // token section (Yay0 / MIO0)
-    u8* uncb = THREE ? side + 2 * pos_off[sid] + n + 16 : nullptr;    // literal section
+    u8* compb = F::THREE ? side + 2 * pos_off[sid] : nullptr;            // token section (Yay0 / MIO0)
+    u8* uncb = F::THREE ? side + 2 * pos_off[sid] + n + 16 : nullptr;    // literal section
     if (lane < 16) { flagacc[lane] = 0; gofs[lane] = 0; }
     __syncthreads();
     u32 tok_base = 0, pay_base = 0, unc_base = 0;
@@ -2471,16 +2466,16 @@ __global__ __launch_bounds__(64) void enc_scan_emit_kernel(const u8* __restrict_
             if (cur > limit) { walk = false; tail = (u32)cur > cover ? (u32)cur : cover; break; }
             int d0, l0, d1 = 0, l1 = 0;
             benc_wave_scan_search(data, (int)n, g, cur, d0, l0, candl);
-            if (l0 < g.min_len) { if (lane == k) { tp = (u32)cur; tm2 = make_uint2(0, 0); } k++; cur++; continue; }      // :166-170
-            const bool lazyc = l0 <= g.lazy && cur + 1 <= limit;
-            if (lazyc) benc_wave_scan_search(data, (int)n, g, cur + 1, d1, l1, candl);
-            int mp = cur, md = d0, ml = l0, skip = lazyc ? 1 : 0;
-            if (lazyc && l1 > l0) { if (lane == k) { tp = (u32)cur; tm2 = make_uint2(0, 0); } k++; mp = cur + 1; md = d1; ml = l1; skip = 0; }   // the byte in front becomes a literal  :181-186
-            if (lane == k) { tp = (u32)mp; tm2 = make_uint2((u32)md, (u32)ml); }
-            k++;
-            const int e = mp + ml, stop = e < limit + 1 ? e : limit + 1;  // :195-203
-            cur = mp + 1 + skip > stop ? mp + 1 + skip : stop;
-            cover = (u32)e;
+            if (parse_rule_needs_neighbour(g, limit, cur, l0)) benc_wave_scan_search(data, (int)n, g, cur + 1, d1, l1, candl);
+            int kind; const int jump = parse_rule(g, limit, cur, l0, l1, kind);
+            if (kind != 1) { if (lane == k) { tp = (u32)cur; tm2 = make_uint2(0, 0); } k++; }     // a literal (:166-170), or the byte in front of the neighbour's match becomes one (:181-186)
+            if (kind) {
+                const int mp = kind == 2 ? cur + 1 : cur, md = kind == 2 ? d1 : d0, ml = kind == 2 ? l1 : l0;
+                if (lane == k) { tp = (u32)mp; tm2 = make_uint2((u32)md, (u32)ml); }
+                k++;
+                cover = (u32)(mp + ml);
+            }
+            cur += jump;                                                 // :195-203
         }
         if (!walk) {
             // what is left behind the last match: literals (the last three bytes are never searched; a stream shorter than four bytes is all of this)
@@ -2490,57 +2485,38 @@ __global__ __launch_bounds__(64) void enc_scan_emit_kernel(const u8* __restrict_
         // ---- the tokens of this batch (the arithmetic of enc_parse_emit_kernel: prefix sums over the tokens)
         const bool tok = lane < k;
         const bool start = tok && tm2.y != 0u, lit = tok && tm2.y == 0u;
-        const u32 ti = tok_base + (u32)lane;
-        u32 b0 = 0, b1 = 0, b2 = 0, b3 = 0, psize = 0, usize = 0;
-        if (lit) { b0 = data[tp]; psize = 1; }
-        else if (start) flag_payload<FMT>(g, tp, tm2, b0, b1, b2, b3, psize);
-        if (THREE) {   // literals (and Yay0's long-length byte) live in their own section
-            if (lit) { usize = 1; psize = 0; }
-            else if (start && FMT == ALZ_FMT_YAY0 && psize == 3) { usize = 1; psize = 2; }
-        }
-        const u32 pincl = scan_add(psize);
-        const u32 poff = pay_base + pincl - psize;
-        const u32 uincl = THREE ? scan_add(usize) : 0u;
-        const u32 uoff = unc_base + uincl - usize;
-        const u32 group = ti / FBITS, bitpos = ti % FBITS;
-        const u32 flag_off = THREE ? group : poff + FB * group;        // interleaved: flag g sits right before the payload of its first token
+        FlagToks w; w.tok = tok; w.lit = lit; w.ti = tok_base + (u32)lane;
+        flag_token_bytes<FMT>(g, w, tp, start, tm2, lit ? data[tp] : 0u, pay_base, unc_base);
+        const u32 group = w.ti / F::FBITS, bitpos = w.ti % F::FBITS;
+        const u32 flag_off = F::THREE ? group : w.poff + F::FB * group;      // interleaved: flag g sits right before the payload of its first token
         if (tok && bitpos == 0) { gofs[group & 15u] = flag_off; flagacc[group & 15u] = 0; }
         __syncthreads();
-        if (tok) {
-            const u32 bitv = (lit ? LIT_BIT : !LIT_BIT) ? 1u : 0u;
-            if (bitv) atomicOr(&flagacc[group & 15u], 1u << (MSB ? FBITS - 1u - bitpos : bitpos));
-        }
+        if (tok) { const u32 bitv = F::bit(lit, bitpos); if (bitv) atomicOr(&flagacc[group & 15u], bitv); }
         __syncthreads();
         if (tok) {
-            if (bitpos == FBITS - 1u) {
-                const u32 fo = gofs[group & 15u], acc = flagacc[group & 15u];
-                if (fo + FB <= cap) { if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc); else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; } }
-                else fail = true;
-            }
-            if (!THREE) {
-                const u32 o = poff + FB * (group + 1u);
-                if (o + psize <= cap) { dst[o] = (u8)b0; if (psize > 1) dst[o + 1] = (u8)b1; if (psize > 2) dst[o + 2] = (u8)b2; if (psize > 3) dst[o + 3] = (u8)b3; }
+            if (bitpos == F::FBITS - 1u && !put_flag_word<FMT>(dst, gofs[group & 15u], flagacc[group & 15u], cap)) fail = true;
+            if (!F::THREE) {
+                const u32 o = w.poff + F::FB * (group + 1u);
+                if (o + w.psize <= cap) { dst[o] = (u8)w.b0; if (w.psize > 1) dst[o + 1] = (u8)w.b1; if (w.psize > 2) dst[o + 2] = (u8)w.b2; if (w.psize > 3) dst[o + 3] = (u8)w.b3; }
                 else fail = true;
             } else {
-                if (lit) uncb[uoff] = (u8)b0;
-                else { compb[poff] = (u8)b0; compb[poff + 1] = (u8)b1; if (usize) uncb[uoff] = (u8)b2; }
+                if (lit) uncb[w.uoff] = (u8)w.b0;
+                else { compb[w.poff] = (u8)w.b0; compb[w.poff + 1] = (u8)w.b1; if (w.usize) uncb[w.uoff] = (u8)w.b2; }
             }
         }
         __syncthreads();
         tok_base += (u32)k;
-        pay_base += (u32)__builtin_amdgcn_readlane((int)pincl, 63);
-        if (THREE) unc_base += (u32)__builtin_amdgcn_readlane((int)uincl, 63);
+        pay_base += w.psum; unc_base += w.usum;
         if (!walk && tail >= n) break;
     }
     // Dispose(): a partial flag byte is written with its unused bits zero (FlagWriter.cs:141-145)
-    const u32 nflags = FB * ((tok_base + FBITS - 1u) / FBITS);          // (bytes)
-    if ((tok_base % FBITS) != 0 && lane == 0) {
-        const u32 gi = tok_base / FBITS; const u32 fo = gofs[gi & 15u], acc = flagacc[gi & 15u];
-        if (fo + FB <= cap) { if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc); else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; } }
-        else fail = true;
+    const u32 nflags = F::FB * ((tok_base + F::FBITS - 1u) / F::FBITS);          // (bytes)
+    if ((tok_base % F::FBITS) != 0 && lane == 0) {
+        const u32 gi = tok_base / F::FBITS;
+        if (!put_flag_word<FMT>(dst, gofs[gi & 15u], flagacc[gi & 15u], cap)) fail = true;
     }
     u32 total;
-    if (!THREE) total = pay_base + nflags;
+    if (!F::THREE) total = pay_base + nflags;
     else {
         total = nflags + pay_base + unc_base;
         if (total <= cap) {
@@ -2554,7 +2530,7 @@ __global__ __launch_bounds__(64) void enc_scan_emit_kernel(const u8* __restrict_
     if (lane == 0) {
         alz_result r; r.dst_len = anyfail ? 0u : total; r.src_used = n; r.status = anyfail ? ALZ_ST_OUTPUT_CAPACITY : ALZ_ST_OK; r.reserved = 0;
         results[sid] = r;
-        if (!THREE && aux) { aux[sid].aux0 = 0; aux[sid].aux1 = 0; }
+        if (!F::THREE && aux) { aux[sid].aux0 = 0; aux[sid].aux1 = 0; }
     }
 }
 
@@ -2593,13 +2569,8 @@ __global__ __launch_bounds__(64) void enc_exit_kernel(const alz_stream* __restri
         const uint2 a = a_n, b = b_n;
         if (P - 64 >= lo) { a_n = ldm(p - 64); b_n = ldm(p - 63); }
         if (__ballot(a.y == ALZ_CAPPED || b.y == ALZ_CAPPED)) { bad = true; break; }
-        int jump = 1;
-        if ((int)a.y >= g.min_len) {                                    // (p < B <= limit: searched)
-            const int l0 = (int)a.y, l1 = (int)b.y;
-            const bool lazyc = l0 <= g.lazy && p + 1 <= limit;
-            if (lazyc && l1 > l0) { const int e = p + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 2 > stop ? p + 2 : stop) - p; }
-            else { const int skip = lazyc ? 1 : 0; const int e = p + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (p + 1 + skip > stop ? p + 1 + skip : stop) - p; }
-        }
+        int kind;
+        const int jump = parse_rule(g, limit, p, (int)a.y, (int)b.y, kind);                 // (p < B <= limit: searched)
         const int t = p + jump;
         u32 val = (u32)t; int res = 1, tl = lane;
         if (t < B) { if (t >= P + 64) val = ring[t & 4095]; else { res = 0; tl = t - P; } }
@@ -2803,7 +2774,6 @@ int alz_encode_geom_max_dist(const void* geom) { return ((const EncGeom*)geom)->
 // the two lengths and the distance, so a prefix sum over the window places them all; the literals of the sequences (and the
 // literal-only end) are copied by the whole wavefront.  The serial form (one lane per stream, a byte at a time) took 161 ms (LZ4) per
 // 10 000 x 256 KiB.
-__device__ __forceinline__ u32 lz4_extn(u32 v) { return v >= 15u ? 1u + (v - 15u) / 255u : 0u; }    // bytes of LZ4.WriteExtension  LZ4.cs:254-268
 __device__ __forceinline__ void wave_copy(u8* d, const u8* s, u32 len, int lane) {
     u32 i = 0;
     for (; i + 256u <= len; i += 256u) { const u32 v = load32(s + i + 4u * (u32)lane); __builtin_memcpy(d + i + 4u * (u32)lane, &v, 4); }
@@ -2843,7 +2813,6 @@ template <> struct SeqFmt<ALZ_FMT_SNAPPY_RAW> {
         else { q[0] = (u8)((2u | ((M - 1u) << 2)) & 0xFFu); q[1] = (u8)(D & 0xFFu); q[2] = (u8)((D >> 8) & 0xFFu); }
     }
 };
-__device__ __forceinline__ u32 lzo_extn(u32 v) { return 1u + (v - 1u) / 255u; }                       // bytes of LZO.WriteExtendedInt(v), v >= 1
 __device__ __forceinline__ u32 lzo_put_ext(u8* q, u32 v) { u32 k = 0; while (v > 255u) { q[k++] = 0; v -= 255u; } q[k++] = (u8)v; return k; }
 __device__ __forceinline__ u32 lzo_lit_size(u32 L) { return L > 18u ? 1u + lzo_extn(L - 18u) : 1u; }  // the run's length token (L >= 4)
 __device__ __forceinline__ u32 lzo_put_lit(u8* q, u32 L) { if (L > 18u) { q[0] = 0; return 1u + lzo_put_ext(q + 1, L - 18u); } q[0] = (u8)(L - 3u); return 1u; }
@@ -2981,51 +2950,13 @@ struct WinParse {
                 if (lane == 63) b = make_uint2(n0x, n0y);
             }
             const bool capped = a.y == ALZ_CAPPED || b.y == ALZ_CAPPED;
-            int jump = 1, startrel = 0;   // startrel: 0 no token here, 1 match starts here, 2 literal here + match at p + 1
-            if (!capped && (int)p <= limit && (int)a.y >= g.min_len) {
-                const int l0 = (int)a.y, l1 = (int)b.y, pi = (int)p;
-                const bool lazyc = l0 <= g.lazy && pi + 1 <= limit;
-                if (lazyc && l1 > l0) { startrel = 2; const int e = pi + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (pi + 2 > stop ? pi + 2 : stop) - pi; }
-                else { startrel = 1; const int skip = lazyc ? 1 : 0; const int e = pi + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (pi + 1 + skip > stop ? pi + 1 + skip : stop) - pi; }
-            }
+            int jump = 1, startrel = 0;   // startrel: the rule's kind -- 0 no token here, 1 match starts here, 2 literal here + match at p + 1
+            if (!capped && (int)p <= limit) jump = parse_rule(g, limit, (int)p, (int)a.y, (int)b.y, startrel);
             int rel = cur - (int)P;
             if (__ballot(capped) == 0) {
-                u64 M = 0; u32 r = (u32)rel, j;
+                u32 r = (u32)rel;
                 const u32 lim = (u32)(limit + 1 - (int)P) < 64u ? (u32)(limit + 1 - (int)P) : 64u;     // (r < lim on entry: cur <= limit)
-                if (lim == 64u) {
-                    // (two tokens per hop, the cursor 64 below zero: enc_parse_emit_kernel)
-                    const u32 tgt = (u32)lane + (u32)jump;                     // where my jump lands (>= 64: outside)
-                    const int jn = __builtin_amdgcn_ds_bpermute((int)((tgt < 64u ? tgt : (u32)lane) << 2), jump);
-                    const int jump2 = tgt < 64u ? jump + jn : jump;
-                    r -= 64u;
-                    asm volatile(
-                        "s_nop 3\n"
-                        "1:\n\t"
-                        "s_bitset1_b64 %[M], %[r]\n\t"
-                        "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                        "s_add_u32 %[r], %[r], %[j]\n\t"
-                        "s_cbranch_scc0 1b\n\t"
-                        : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                        : [jump] "v"(jump2)
-                        : "scc");
-                    r += 64u;
-                    if (((M >> lane) & 1ull) && tgt < 64u) hopmark[tgt] = 1;
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-                    const u32 hm = hopmark[lane];
-                    if (hm) hopmark[lane] = 0;
-                    M |= __ballot(hm != 0u);
-                } else
-                asm volatile(
-                    "s_nop 3\n"
-                    "1:\n\t"
-                    "s_bitset1_b64 %[M], %[r]\n\t"
-                    "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                    "s_add_u32 %[r], %[r], %[j]\n\t"
-                    "s_cmp_lt_u32 %[r], %[lim]\n\t"
-                    "s_cbranch_scc1 1b\n\t"
-                    : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                    : [jump] "v"(jump), [lim] "s"(lim)
-                    : "scc");
+                const u64 M = lim == 64u ? hop_walk_full(jump, r, lane, hopmark) : hop_walk_lim(jump, r, lim);
                 const u64 s1 = __ballot(startrel == 1) & M, s2 = __ballot(startrel == 2) & M;
                 sm |= s1 | (s2 << 1);
                 if (s2 >> 63) carry = true;                                    // start in lane 0 of the next window
@@ -3041,18 +2972,11 @@ struct WinParse {
                     const uint2 e0 = make_uint2((u32)__builtin_amdgcn_readlane((int)a.x, rel), (u32)__builtin_amdgcn_readlane((int)a.y, rel));
                     const uint2 e1 = rel + 1 < 64 ? make_uint2((u32)__builtin_amdgcn_readlane((int)a.x, (rel + 1) & 63), (u32)__builtin_amdgcn_readlane((int)a.y, (rel + 1) & 63))
                                                   : make_uint2((u32)__builtin_amdgcn_readlane((int)a_n.x, 0), (u32)__builtin_amdgcn_readlane((int)a_n.y, 0));
-                    if (g.use_min_table) benc_capped_cursor<true>(data, ns, g, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1);
-                    else benc_capped_cursor<false>(data, ns, g, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1);
+                    j = parse_capped_cursor(data, ns, g, g.use_min_table != 0, p4, pm, q, limit, e0, e0.y == ALZ_CAPPED, e1, e1.y == ALZ_CAPPED, d0, l0, d1, l1, s0, s1, sr);
                     if (s0 && lane == rel) a = make_uint2((u32)d0, (u32)l0);
                     if (s1) {
                         if (rel + 1 < 64) { if (lane == rel + 1) a = make_uint2((u32)d1, (u32)l1); }
                         else if (lane == 0) a_n = make_uint2((u32)d1, (u32)l1);
-                    }
-                    j = 1; sr = 0;
-                    if (l0 >= g.min_len) {
-                        const bool lazyc = l0 <= g.lazy && q + 1 <= limit;
-                        if (lazyc && l1 > l0) { sr = 2; const int e = q + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; j = (q + 2 > stop ? q + 2 : stop) - q; }
-                        else { sr = 1; const int skip = lazyc ? 1 : 0; const int e = q + l0; const int stop = e < limit + 1 ? e : limit + 1; j = (q + 1 + skip > stop ? q + 1 + skip : stop) - q; }
                     }
                 } else {
                     j = __builtin_amdgcn_readlane(jump, rel);
@@ -3066,6 +2990,7 @@ struct WinParse {
         }
     }
 };
+
 
 // LZ4 blocks and raw Snappy in ONE kernel behind kernel A (round 4): the walk over a window of 64 positions (WinParse), then the sequences
 // that start in it, from the same registers; at quality 0 the search as well.
@@ -3215,15 +3140,12 @@ __global__ __launch_bounds__(64) void enc_scan_seq_kernel(const u8* __restrict__
             if (cur > limit) { walk = false; break; }
             int d0, l0, d1 = 0, l1 = 0;
             (void)benc_wave_scan_search(src, ns, g, cur, d0, l0, candl, p4);
-            if (l0 < g.min_len) { cur++; continue; }                            // :166-170
-            const bool lazyc = l0 <= g.lazy && cur + 1 <= limit;
-            if (lazyc) (void)benc_wave_scan_search(src, ns, g, cur + 1, d1, l1, candl, p4);
-            int mp = cur, md = d0, ml = l0, skip = lazyc ? 1 : 0;
-            if (lazyc && l1 > l0) { mp = cur + 1; md = d1; ml = l1; skip = 0; }   // :181-186
-            if (lane == k) { tp = (u32)mp; D = (u32)md; M = (u32)ml; }
+            if (parse_rule_needs_neighbour(g, limit, cur, l0)) (void)benc_wave_scan_search(src, ns, g, cur + 1, d1, l1, candl, p4);
+            int kind; const int jump = parse_rule(g, limit, cur, l0, l1, kind);
+            if (kind == 0) { cur++; continue; }                                  // a literal: it waits for the next match  :166-170
+            if (lane == k) { tp = (u32)(kind == 2 ? cur + 1 : cur); D = (u32)(kind == 2 ? d1 : d0); M = (u32)(kind == 2 ? l1 : l0); }   // :181-186
             k++;
-            const int e = mp + ml, stop = e < limit + 1 ? e : limit + 1;         // :195-203
-            cur = mp + 1 + skip > stop ? mp + 1 + skip : stop;
+            cur += jump;                                                         // :195-203
         }
         if (k == 0) break;
         // ---- the sequences of this batch
@@ -3752,11 +3674,11 @@ __global__ __launch_bounds__(64) void enc_scan_select_kernel(const u8* __restric
                 const int end = start + 2048 < limit + 1 ? start + 2048 : limit + 1;
                 int cur = start, cnt = 0, cost = 0;
                 while (cur < end && cnt < 16) {
-                    int d0, l0, d1, l1;
+                    int d0, l0, d1, l1 = 0, kind;
                     cost += 3 + benc_wave_scan_search(data, n, g, cur, d0, l0, candl, p4); cnt++;
-                    if (l0 < g.min_len) { cur++; continue; }
-                    if (l0 <= g.lazy && cur + 1 <= limit) { cost += 3 + benc_wave_scan_search(data, n, g, cur + 1, d1, l1, candl, p4); cnt++; cur += l1 > l0 ? 1 + l1 : l0; }
-                    else cur += l0;
+                    if (parse_rule_needs_neighbour(g, limit, cur, l0)) { cost += 3 + benc_wave_scan_search(data, n, g, cur + 1, d1, l1, candl, p4); cnt++; }
+                    (void)parse_rule(g, limit, cur, l0, l1, kind);
+                    cur += kind == 0 ? 1 : kind == 2 ? 1 + l1 : l0;            // (an estimate: the taken match's length, not the rule's jump)
                 }
                 per_kib += (cost << 8) / (cur > start ? cur - start : 1);   // (quarters of a one-block search, per KiB)
                 if (per_kib > 8 * ALZ_SCAN_MAX_PER_KIB) break;             // (already over: the synthetic batches leave after two places)

@@ -94,19 +94,6 @@ __global__ __launch_bounds__(256) void benc_unpack(BencArgs a, const mentry* __r
     if (stt) stt[p] = capped ? 1u : 0u;
 }
 
-// the rule of FindNextBestMatch (:157-212) for a cursor at p whose match has l0 bytes and whose neighbour's has l1: what it takes
-// (0 a literal, 1 the match here, 2 a literal and the neighbour's match) and where the cursor goes
-__device__ __forceinline__ u32 benc_rule(const EncGeom& g, int limit, int pi, int l0, int l1, u32& s) {
-    int jump = 1; s = 0;
-    if (l0 >= g.min_len) {
-        const bool lazyc = l0 <= g.lazy && pi + 1 <= limit;
-        if (lazyc && l1 > l0) { s = 2; const int e = pi + 1 + l1; const int stop = e < limit + 1 ? e : limit + 1; jump = (pi + 2 > stop ? pi + 2 : stop) - pi; }
-        else { s = 1; const int skip = lazyc ? 1 : 0; const int e = pi + l0; const int stop = e < limit + 1 ? e : limit + 1; jump = (pi + 1 + skip > stop ? pi + 1 + skip : stop) - pi; }
-    }
-    return (u32)(pi + jump);
-}
-__device__ __forceinline__ bool benc_lazy_needs(const EncGeom& g, int limit, int pi, int l0) { return l0 >= g.min_len && l0 <= g.lazy && pi + 1 <= limit; }
-
 // "somebody's cursor may land on x": a capped position is searched exactly once somebody asks
 // (`stride`: the format's longest match where that is a few KiB -- LZ11, LZ40: 16 Ki --, else 0.  Inside a long repeat every cursor takes a match
 // of exactly that length and lands on the next capped position: a chain of requests, one generation each -- 3.7 of the 7.4 ms of Test.bmp as
@@ -135,18 +122,18 @@ __global__ __launch_bounds__(256) void benc_request0(BencArgs a, EncGeom g, cons
     if (l0 == BENC_UNKNOWN) { if (p == 0u) benc_request(a, 0u, stt, front, ctl + BC_F0N, stride); return; }
     u32 l1 = (int)p + 1 <= a.limit ? ml[p + 1u] : 0u;
     if (l1 == BENC_UNKNOWN) {
-        if (benc_lazy_needs(g, a.limit, (int)p, (int)l0)) { benc_request(a, p + 1u, stt, front, ctl + BC_F0N, stride); return; }   // (its own target follows when the neighbour is known)
+        if (parse_rule_needs_neighbour(g, a.limit, (int)p, (int)l0)) { benc_request(a, p + 1u, stt, front, ctl + BC_F0N, stride); return; }   // (its own target follows when the neighbour is known)
         l1 = 0;
     }
-    u32 s;
-    benc_request(a, benc_rule(g, a.limit, (int)p, (int)l0, (int)l1, s), stt, front, ctl + BC_F0N, stride);
+    int kind;
+    benc_request(a, p + (u32)parse_rule(g, a.limit, (int)p, (int)l0, (int)l1, kind), stt, front, ctl + BC_F0N, stride);
 }
 
 // One requested position, by one wavefront: its match, exactly; then where ITS cursor would go -- another request -- and, if the position in
 // front of it was waiting for this length (lazy rule), that one's target too.
 template <bool MINT>
 __device__ __forceinline__ void benc_resolve(const BencArgs& a, const EncGeom& g, const int* p4, const int* pm, u32 c, u32* ml, u32* md, u32* stt, u32* front, u32* tail) {
-    const bool l0lane = benc_lane() == 0u;
+    const bool l0lane = lane_id() == 0;
     const u32 stride = g.max_len <= 65536 ? (u32)g.max_len : 0u;
     auto known = [&](u32 q, int& d, int& l) -> bool {
         const u32 v = __hip_atomic_load(ml + q, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
@@ -164,16 +151,16 @@ __device__ __forceinline__ void benc_resolve(const BencArgs& a, const EncGeom& g
         // the position in front of q, if its own match is known and short enough for the lazy rule, was waiting for this length
         if (q >= 1u) {
             int dq, lq;
-            if (stt[q - 1u] == 0u && known(q - 1u, dq, lq) && benc_lazy_needs(g, a.limit, (int)q - 1, lq)) {
-                u32 s; const u32 x = benc_rule(g, a.limit, (int)q - 1, lq, l, s);
+            if (stt[q - 1u] == 0u && known(q - 1u, dq, lq) && parse_rule_needs_neighbour(g, a.limit, (int)q - 1, lq)) {
+                int kind; const u32 x = q - 1u + (u32)parse_rule(g, a.limit, (int)q - 1, lq, l, kind);
                 if (l0lane) benc_request(a, x, stt, front, tail, stride);
             }
         }
     };
     int d0, l0, d1 = 0, l1 = 0;
     settle(c, d0, l0);
-    if (benc_lazy_needs(g, a.limit, (int)c, l0)) settle(c + 1u, d1, l1);
-    u32 s; const u32 x = benc_rule(g, a.limit, (int)c, l0, l1, s);
+    if (parse_rule_needs_neighbour(g, a.limit, (int)c, l0)) settle(c + 1u, d1, l1);
+    int kind; const u32 x = c + (u32)parse_rule(g, a.limit, (int)c, l0, l1, kind);
     if (l0lane) benc_request(a, x, stt, front, tail, stride);
 }
 
@@ -229,8 +216,8 @@ __global__ __launch_bounds__(1024) void benc_tile_exit(BencArgs a, EncGeom g, co
                 l0 = ml[p]; if (l0 == BENC_UNKNOWN) l0 = 0;
                 if ((int)p + 1 <= limit) { l1 = ml[p + 1u]; if (l1 == BENC_UNKNOWN) l1 = 0; }
             }
-            u32 s; x = benc_rule(g, limit, (int)p, (int)l0, (int)l1, s);
-            sr[p] = (u8)s;
+            int kind; x = p + (u32)parse_rule(g, limit, (int)p, (int)l0, (int)l1, kind);
+            sr[p] = (u8)kind;
         }
         next1[p] = x;
     }
@@ -286,13 +273,6 @@ __global__ __launch_bounds__(1024) void benc_tile_mark(BencArgs a, const u32* __
     }
 }
 
-template <int FMT> struct FlagFmt {
-    static constexpr bool THREE = (FMT == ALZ_FMT_YAY0 || FMT == ALZ_FMT_MIO0);
-    static constexpr bool LIT_BIT = (FMT == ALZ_FMT_LZSS || FMT == ALZ_FMT_YAZ0 || FMT == ALZ_FMT_LZHUDSON || THREE);
-    static constexpr bool MSB = (FMT != ALZ_FMT_LZSS && FMT != ALZ_FMT_CLZ0);
-    static constexpr u32 FBITS = FMT == ALZ_FMT_LZHUDSON ? 32u : 8u, FB = FBITS / 8u;
-};
-
 // The token that starts at position p, if any: 0 none, 1 a literal, 2 a match (its length in `len`)
 struct BencTok { u32 kind, len, dist; };
 __device__ __forceinline__ BencTok benc_token(const BencArgs& a, u32 p, u32 tail, const u8* mark, const u8* sr, const u32* ml, const u32* md) {
@@ -326,7 +306,7 @@ template <int FMT>
 __global__ __launch_bounds__(64) void benc_count(BencArgs a, const u8* __restrict__ mark, const u8* __restrict__ sr, const u32* __restrict__ ml,
                                                  const u32* __restrict__ md, const u32* __restrict__ ctl, u32* __restrict__ tile_t, u32* __restrict__ tile_p,
                                                  u32* __restrict__ tile_u) {
-    const u32 tile = blockIdx.x, lane = benc_lane(), tail = ctl[BC_TAIL];
+    const u32 tile = blockIdx.x, lane = (u32)lane_id(), tail = ctl[BC_TAIL];
     u32 ct = 0, cp = 0, cu = 0;
     for (u32 r = 0; r < BENC_TILE / 64u; r++) {
         const u32 p = tile * BENC_TILE + r * 64u + lane;
@@ -367,7 +347,7 @@ __global__ __launch_bounds__(64) void benc_place(BencArgs a, EncGeom g, const u8
                                                  const u32* __restrict__ md, const u32* __restrict__ ctl, const u32* __restrict__ base_t, const u32* __restrict__ base_p,
                                                  const u32* __restrict__ base_u, u8* __restrict__ dst, u32 cap, u8* __restrict__ tokbit, u32* __restrict__ gofs) {
     typedef FlagFmt<FMT> F;
-    const u32 tile = blockIdx.x, lane = benc_lane(), tail = ctl[BC_TAIL];
+    const u32 tile = blockIdx.x, lane = (u32)lane_id(), tail = ctl[BC_TAIL];
     const u32 T = ctl[BC_T], P = ctl[BC_P], U = ctl[BC_U];
     const u32 nflags = F::FB * ((T + F::FBITS - 1u) / F::FBITS);
     if (ctl[BC_BAD] || (u64)nflags + P + U > cap) return;        // (declined, or no room: benc_result says so)
@@ -421,9 +401,7 @@ __global__ __launch_bounds__(256) void benc_flags(BencArgs a, const u32* __restr
         const u32 ti = gi * F::FBITS + k;
         if (ti < T && tokbit[ti]) acc |= 1u << (F::MSB ? F::FBITS - 1u - k : k);
     }
-    u8* o = dst + gofs[gi];
-    if (F::FB == 1u) o[0] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc);
-    else { o[0] = (u8)(acc >> 24); o[1] = (u8)(acc >> 16); o[2] = (u8)(acc >> 8); o[3] = (u8)acc; }
+    (void)put_flag_word<FMT>(dst, gofs[gi], acc, cap);            // (room: checked above)
 }
 
 static size_t benc_al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -532,7 +510,7 @@ __global__ __launch_bounds__(64) void benc_seq(BencArgs a, const u8* __restrict_
                                                const u32* __restrict__ off_base, u32* __restrict__ tile_out, u8* __restrict__ dst, u32 cap) {
     typedef SeqFmt<FMT> F;
     constexpr bool LZ4 = FMT == ALZ_FMT_LZ4_BLOCK;
-    const u32 tile = blockIdx.x, lane = benc_lane();
+    const u32 tile = blockIdx.x, lane = (u32)lane_id();
     if (PASS == 2 && (ctl[BC_BAD] || benc_seq_total<FMT>(a, ctl) > cap)) return;
     u32 cover = PASS >= 1 ? cover_base[tile] : 0u;
     u32 obase = PASS == 2 ? off_base[tile] + (LZ4 ? 0u : benc_snappy_varint(a.N)) : 0u;
@@ -649,7 +627,7 @@ template <bool BIG, int PASS>
 __global__ __launch_bounds__(64) void benc_prs(BencArgs a, const u8* __restrict__ mark, const u8* __restrict__ sr, const u32* __restrict__ ml, const u32* __restrict__ md,
                                                const u32* __restrict__ ctl, const u32* __restrict__ base_b, const u32* __restrict__ base_p, u32* __restrict__ tile_b,
                                                u32* __restrict__ tile_p, u8* __restrict__ dst, u32 cap, u8* __restrict__ bitv, u32* __restrict__ gofs) {
-    const u32 tile = blockIdx.x, lane = benc_lane(), tail = ctl[BC_TAIL];
+    const u32 tile = blockIdx.x, lane = (u32)lane_id(), tail = ctl[BC_TAIL];
     if (PASS == 1) { const u64 total = (u64)((ctl[BC_BITS] + 7u) >> 3) + ctl[BC_PAY]; if (ctl[BC_BAD] || total > cap) return; }
     u32 bb = PASS == 1 ? base_b[tile] : 0u, pb = PASS == 1 ? base_p[tile] : 0u;
     for (u32 r = 0; r < BENC_TILE / 64u; r++) {
@@ -730,7 +708,7 @@ __device__ __forceinline__ void benc_wave_copy16(u8* d, const u8* s, u32 len, u3
 }
 __global__ __launch_bounds__(64) void benc_lzo_head(BencArgs a, const u8* __restrict__ mark, const u8* __restrict__ sr, const u32* __restrict__ ml_, const u32* __restrict__ md_,
                                                     u32* __restrict__ ctl, u8* __restrict__ dst, u32 cap) {
-    const u32 lane = benc_lane(), n = a.N;
+    const u32 lane = (u32)lane_id(), n = a.N;
     if (ctl[BC_BAD]) return;
     auto is_start = [&](u32 q) { return benc_token(a, q, 0xFFFFFFFFu, mark, sr, ml_, md_).kind == 2u; };
     auto next_start = [&](u32 from) -> u32 {                       // the next start at or behind `from` (n: none)
@@ -796,7 +774,7 @@ template <int PASS>
 __global__ __launch_bounds__(64) void benc_lzo(BencArgs a, const u8* __restrict__ mark, const u8* __restrict__ sr, const u32* __restrict__ ml, const u32* __restrict__ md,
                                                const u32* __restrict__ ctl, const u32* __restrict__ cover_base, const u32* __restrict__ off_base, u32* __restrict__ tile_out,
                                                u8* __restrict__ dst, u32 cap) {
-    const u32 tile = blockIdx.x, lane = benc_lane(), n = a.N;
+    const u32 tile = blockIdx.x, lane = (u32)lane_id(), n = a.N;
     const u32 mo = ctl[BC_LZ_MO], sp0 = ctl[BC_LZ_SP0];
     if (ctl[BC_BAD] || ctl[BC_LZ_DONE]) { if (PASS < 2 && lane == 0) tile_out[tile] = 0u; return; }
     if (PASS == 2) { u32 r_, l_, o_; if (ctl[BC_LZ_FAIL] || benc_lzo_total(a, ctl, r_, l_, o_) > cap) return; }

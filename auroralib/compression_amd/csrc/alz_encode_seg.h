@@ -44,10 +44,7 @@ __global__ __launch_bounds__(64) void enc_seg_kernel(const u8* __restrict__ src_
                                                      const u32* __restrict__ index_list, const mentry* __restrict__ match, const u64* __restrict__ pos_off,
                                                      const u64* __restrict__ startmask, SegRec* __restrict__ seg, const u32* __restrict__ stot,
                                                      u32 kpitch, u32 seglen, EncGeom g) {
-    constexpr bool THREE = (FMT == ALZ_FMT_YAY0 || FMT == ALZ_FMT_MIO0);
-    constexpr bool LIT_BIT = (FMT == ALZ_FMT_LZSS || FMT == ALZ_FMT_YAZ0 || FMT == ALZ_FMT_LZHUDSON || THREE);
-    constexpr bool MSB = (FMT != ALZ_FMT_LZSS && FMT != ALZ_FMT_CLZ0);
-    constexpr u32 FBITS = FMT == ALZ_FMT_LZHUDSON ? 32u : 8u, FB = FBITS / 8u;
+    typedef FlagFmt<FMT> F;
     __shared__ u32 flagacc[16];
     __shared__ u32 gofs[16];
     const u32 k = blockIdx.x, bid = blockIdx.y;
@@ -85,10 +82,10 @@ __global__ __launch_bounds__(64) void enc_seg_kernel(const u8* __restrict__ src_
     u32 tok_base = 0, pay_base = 0, unc_base = 0, nflags = 0, pay_total = 0;
     if (EMIT) {
         tok_base = rec->tok; pay_base = rec->pay; unc_base = rec->unc;
-        if (THREE) { nflags = FB * ((stot[4 * (size_t)bid] + FBITS - 1u) / FBITS); pay_total = stot[4 * (size_t)bid + 1]; }
+        if (F::THREE) { nflags = F::FB * ((stot[4 * (size_t)bid] + F::FBITS - 1u) / F::FBITS); pay_total = stot[4 * (size_t)bid + 1]; }
     }
-    const u32 g0 = tok_base / FBITS;
-    const bool straddle = (tok_base % FBITS) != 0u;          // the first tokens complete a group that began in the segment before
+    const u32 g0 = tok_base / F::FBITS;
+    const bool straddle = (tok_base % F::FBITS) != 0u;          // the first tokens complete a group that began in the segment before
     bool fail = false;
     auto ldm = [&](u32 q) { return (int)q <= limit ? m_unpack(m[q]) : make_uint2(0, 0); };
     // (mask word, match entries and source bytes of a window are loaded while the window before it is worked on)
@@ -99,71 +96,42 @@ __global__ __launch_bounds__(64) void enc_seg_kernel(const u8* __restrict__ src_
         const u32 p = P + (u32)lane;
         const u64 sm = sm_n; const uint2 a = a_n; const u32 sb = sb_n;
         if (P + 64 < E) { sm_n = mask[(P + 64) >> 6]; a_n = ldm(p + 64u); sb_n = p + 64u < n ? src[p + 64u] : 0u; }
-        // ---- as enc_parse_emit_kernel: prefix sums over the start mask give every token its flag group and byte offset
+        // ---- the tokens of this window, as enc_parse_emit_kernel
         const bool start = ((sm >> lane) & 1ull) && p < n;
         uint2 mt = make_uint2(0, 0);
         if (start) mt = a;
         if (FMT == ALZ_FMT_LZ11 || FMT == ALZ_FMT_LZ40) { if (start && mt.y == ALZ_M_LONG) mt.y = m[p + 1]; }     // (a taken match of 2 046 bytes or more: the walk left its length in the next entry)
-        const u32 mend = start ? p + mt.y : 0u;
-        const u32 pmax = scan_max(mend);
-        u32 before = (u32)__builtin_amdgcn_update_dpp(0, (int)pmax, 0x138, 0xF, 0xF, false);   // wave_shr:1 -> max over lanes below
-        if (before < cover) before = cover;
-        const bool lit = !start && p < n && p >= before;
-        const bool tok = start || lit;
-        const u64 tm = __ballot(tok);
-        const u32 ti = tok_base + __builtin_amdgcn_mbcnt_hi((u32)(tm >> 32), __builtin_amdgcn_mbcnt_lo((u32)tm, 0u));
-        u32 b0 = 0, b1 = 0, b2 = 0, b3 = 0, psize = 0, usize = 0;
-        if (lit) { b0 = sb; psize = 1; }
-        else if (start) flag_payload<FMT>(g, p, mt, b0, b1, b2, b3, psize);
-        if (THREE) {
-            if (lit) { usize = 1; psize = 0; }
-            else if (start && FMT == ALZ_FMT_YAY0 && psize == 3) { usize = 1; psize = 2; }
-        }
-        const u32 pincl = scan_add(psize);
-        const u32 poff = pay_base + pincl - psize;
-        const u32 uincl = THREE ? scan_add(usize) : 0u;
-        const u32 uoff = unc_base + uincl - usize;
+        const FlagToks w = flag_window<FMT>(g, p, n, start, mt, sb, cover, tok_base, pay_base, unc_base);
         if (EMIT) {
-            const u32 group = ti / FBITS, bitpos = ti % FBITS;
-            const u32 flag_off = THREE ? group : poff + FB * group;
-            if (tok && bitpos == 0) { gofs[group & 15u] = flag_off; flagacc[group & 15u] = 0; }
+            const u32 group = w.ti / F::FBITS, bitpos = w.ti % F::FBITS;
+            const u32 flag_off = F::THREE ? group : w.poff + F::FB * group;
+            if (w.tok && bitpos == 0) { gofs[group & 15u] = flag_off; flagacc[group & 15u] = 0; }
             __syncthreads();
-            if (tok) {
-                const u32 bitv = (lit ? LIT_BIT : !LIT_BIT) ? 1u : 0u;
-                if (bitv) atomicOr(&flagacc[group & 15u], 1u << (MSB ? FBITS - 1u - bitpos : bitpos));
-            }
+            if (w.tok) { const u32 bitv = F::bit(w.lit, bitpos); if (bitv) atomicOr(&flagacc[group & 15u], bitv); }
             __syncthreads();
-            if (tok) {
-                if (bitpos == FBITS - 1u) {
+            if (w.tok) {
+                if (bitpos == F::FBITS - 1u) {
                     const u32 acc = flagacc[group & 15u];
                     if (straddle && group == g0) rec->head = acc;             // (its flag byte lies in the segment before: enc_seg_flags_kernel)
-                    else {
-                        const u32 fo = gofs[group & 15u];
-                        if (fo + FB <= cap) { if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc); else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; } }
-                        else fail = true;
-                    }
+                    else if (!put_flag_word<FMT>(dst, gofs[group & 15u], acc, cap)) fail = true;
                 }
-                if (!THREE) {
-                    const u32 o = poff + FB * (group + 1u);
-                    if (o + psize <= cap) { dst[o] = (u8)b0; if (psize > 1) dst[o + 1] = (u8)b1; if (psize > 2) dst[o + 2] = (u8)b2; if (psize > 3) dst[o + 3] = (u8)b3; }
+                if (!F::THREE) {
+                    const u32 o = w.poff + F::FB * (group + 1u);
+                    if (o + w.psize <= cap) { dst[o] = (u8)w.b0; if (w.psize > 1) dst[o + 1] = (u8)w.b1; if (w.psize > 2) dst[o + 2] = (u8)w.b2; if (w.psize > 3) dst[o + 3] = (u8)w.b3; }
                     else fail = true;
                 } else {
                     // (the sections straight into place: their offsets are known)
-                    const u32 oc = nflags + poff, ou = nflags + pay_total + uoff;
-                    if (lit) { if (ou < cap) dst[ou] = (u8)b0; else fail = true; }
+                    const u32 oc = nflags + w.poff, ou = nflags + pay_total + w.uoff;
+                    if (w.lit) { if (ou < cap) dst[ou] = (u8)w.b0; else fail = true; }
                     else {
-                        if (oc + 2u <= cap) { dst[oc] = (u8)b0; dst[oc + 1] = (u8)b1; } else fail = true;
-                        if (usize) { if (ou < cap) dst[ou] = (u8)b2; else fail = true; }
+                        if (oc + 2u <= cap) { dst[oc] = (u8)w.b0; dst[oc + 1] = (u8)w.b1; } else fail = true;
+                        if (w.usize) { if (ou < cap) dst[ou] = (u8)w.b2; else fail = true; }
                     }
                 }
             }
             __syncthreads();
         }
-        tok_base += (u32)__popcll(tm);
-        pay_base += (u32)__builtin_amdgcn_readlane((int)pincl, 63);
-        if (THREE) unc_base += (u32)__builtin_amdgcn_readlane((int)uincl, 63);
-        const u32 wmax = (u32)__builtin_amdgcn_readlane((int)pmax, 63);
-        if (wmax > cover) cover = wmax;
+        w.advance(tok_base, pay_base, unc_base, cover);
     }
     if (!EMIT) {
         if (lane == 0) { SegRec r; r.tok = tok_base; r.pay = pay_base; r.unc = unc_base; r.head = 0; r.tailbits = 0; r.tailofs = 0; r.fail = 0; r.pad = 0; *rec = r; }
@@ -171,9 +139,9 @@ __global__ __launch_bounds__(64) void enc_seg_kernel(const u8* __restrict__ src_
     }
     const bool anyfail = __ballot(fail) != 0ull;
     if (lane == 0) {
-        const u32 gt = tok_base / FBITS;                                       // (tok_base: one behind the segment's last token)
+        const u32 gt = tok_base / F::FBITS;                                       // (tok_base: one behind the segment's last token)
         if (straddle && gt == g0) rec->head = flagacc[g0 & 15u];               // still inside the group it began in
-        else if ((tok_base % FBITS) != 0u) { rec->tailbits = flagacc[gt & 15u]; rec->tailofs = gofs[gt & 15u]; }
+        else if ((tok_base % F::FBITS) != 0u) { rec->tailbits = flagacc[gt & 15u]; rec->tailofs = gofs[gt & 15u]; }
         rec->fail = anyfail ? 1u : 0u;
     }
 }
@@ -203,8 +171,7 @@ template <int FMT>
 __global__ __launch_bounds__(64) void enc_seg_flags_kernel(u8* __restrict__ dst_base, const alz_stream* __restrict__ streams, const u32* __restrict__ index_list,
                                                            const SegRec* __restrict__ seg, const u32* __restrict__ stot, u32 kpitch, u32 seglen,
                                                            alz_result* __restrict__ results, alz_encode_aux* __restrict__ aux) {
-    constexpr bool THREE = (FMT == ALZ_FMT_YAY0 || FMT == ALZ_FMT_MIO0);
-    constexpr u32 FBITS = FMT == ALZ_FMT_LZHUDSON ? 32u : 8u, FB = FBITS / 8u;
+    typedef FlagFmt<FMT> F;
     const u32 bid = blockIdx.x;
     const int lane = (int)threadIdx.x;
     const u32 sid = index_list[bid];
@@ -217,24 +184,23 @@ __global__ __launch_bounds__(64) void enc_seg_flags_kernel(u8* __restrict__ dst_
     bool fail = false;
     for (u32 k = (u32)lane; k < K; k += 64) {
         const u32 tb = rec[k].tok, te = k + 1u < K ? rec[k + 1u].tok : tok_total;
-        const u32 g0 = tb / FBITS, gt = te / FBITS;
-        const bool straddle = (tb % FBITS) != 0u;
+        const u32 g0 = tb / F::FBITS, gt = te / F::FBITS;
+        const bool straddle = (tb % F::FBITS) != 0u;
         if (rec[k].fail) fail = true;
-        if ((te % FBITS) != 0u && !(straddle && gt == g0)) {                    // a group begins in this segment and does not end in it
+        if ((te % F::FBITS) != 0u && !(straddle && gt == g0)) {                    // a group begins in this segment and does not end in it
             u32 acc = rec[k].tailbits;
             const u32 fo = rec[k].tailofs;
-            for (u32 j = k + 1u; j < K && rec[j].tok / FBITS == gt; j++) acc |= rec[j].head;
-            if (fo + FB <= cap) { if (FB == 1u) dst[fo] = (u8)(FMT == ALZ_FMT_LZ40 ? 0u - acc : acc); else { dst[fo] = (u8)(acc >> 24); dst[fo + 1] = (u8)(acc >> 16); dst[fo + 2] = (u8)(acc >> 8); dst[fo + 3] = (u8)acc; } }
-            else fail = true;
+            for (u32 j = k + 1u; j < K && rec[j].tok / F::FBITS == gt; j++) acc |= rec[j].head;
+            if (!put_flag_word<FMT>(dst, fo, acc, cap)) fail = true;
         }
     }
-    const u32 nflags = FB * ((tok_total + FBITS - 1u) / FBITS);
-    const u32 total = nflags + pay_total + (THREE ? unc_total : 0u);
+    const u32 nflags = F::FB * ((tok_total + F::FBITS - 1u) / F::FBITS);
+    const u32 total = nflags + pay_total + (F::THREE ? unc_total : 0u);
     const bool anyfail = __ballot(fail) != 0ull || total > cap;
     if (lane == 0) {
         alz_result r; r.dst_len = anyfail ? 0u : total; r.src_used = n; r.status = anyfail ? ALZ_ST_OUTPUT_CAPACITY : ALZ_ST_OK; r.reserved = 0;
         results[sid] = r;
-        if (aux) { aux[sid].aux0 = THREE ? nflags : 0u; aux[sid].aux1 = THREE ? nflags + pay_total : 0u; }
+        if (aux) { aux[sid].aux0 = F::THREE ? nflags : 0u; aux[sid].aux1 = F::THREE ? nflags + pay_total : 0u; }
     }
 }
 

@@ -245,35 +245,19 @@ __device__ __forceinline__ int spec_walk(const u8* data, int ns, int limit, cons
         const uint2 a = ldm(p), b = ldm(p + 1);
         // (capped by kernel B, or searched exactly by some walk that found 2 046 bytes or more -- the entry holds the code, not the length: searched again)
         const bool capped = a.y >= ALZ_M_LONG || b.y >= ALZ_M_LONG;
-        int jump = 1, startrel = 0;   // startrel: 0 no token here, 1 match starts here, 2 literal here + match at p + 1
-        if (!capped && p <= limit && (int)a.y >= g.min_len) {
-            const int l0 = (int)a.y, l1 = (int)b.y;
-            const bool lazyc = l0 <= g.lazy && p + 1 <= limit;
-            if (lazyc && l1 > l0) { startrel = 2; const int e = p + 1 + l1; const int stop2 = e < limit + 1 ? e : limit + 1; jump = (p + 2 > stop2 ? p + 2 : stop2) - p; }
-            else { startrel = 1; const int skip = lazyc ? 1 : 0; const int e = p + l0; const int stop2 = e < limit + 1 ? e : limit + 1; jump = (p + 1 + skip > stop2 ? p + 1 + skip : stop2) - p; }
-        }
+        int jump = 1, startrel = 0;   // startrel: the rule's kind -- 0 no token here, 1 match starts here, 2 literal here + match at p + 1
+        if (!capped && p <= limit) jump = parse_rule(g, limit, p, (int)a.y, (int)b.y, startrel);
         const u64 stopw = !stop ? 0ull : (has0 && P == S) ? stop0 : stop[(u32)(P - S) >> 6];
         u64 sb = 0, cb = 0; bool nextbit = false;
         int rel = cur - P;
         if (__ballot(capped) == 0ull) {
-            // no capped entry in the window: the hops as five scalar instructions each, the visited lanes collected as a bit mask and the token starts read off two
-            // ballots (enc_roles_kernel's loop -- written in C++ a hop is ~40 instructions of the CU's one scalar unit, which seven wavefronts per SIMD share: the walk
-            // kernel of 256 x 64 KiB at quality 0 took 0.23 ms of the call's 0.64)
-            u64 M = 0; u32 r = (u32)rel, j;
+            // no capped entry in the window: the hops by hand (hop_walk_lim -- written in C++ a hop is ~40 instructions of the CU's one scalar unit, which seven
+            // wavefronts per SIMD share: the walk kernel of 256 x 64 KiB at quality 0 took 0.23 ms of the call's 0.64), the token starts read off two ballots
+            u32 r = (u32)rel;
             u32 lim = (u32)(limit + 1 - P) < 64u ? (u32)(limit + 1 - P) : 64u;     // (r < lim on entry: cur <= limit and cur < End)
             if ((u32)(End - P) < lim) lim = (u32)(End - P);
             lim = (u32)__builtin_amdgcn_readfirstlane((int)lim); r = (u32)__builtin_amdgcn_readfirstlane((int)r);      // (wave-uniform by construction: into scalar registers)
-            asm volatile(
-                "s_nop 3\n"
-                "1:\n\t"
-                "s_bitset1_b64 %[M], %[r]\n\t"
-                "v_readlane_b32 %[j], %[jump], %[r]\n\t"
-                "s_add_u32 %[r], %[r], %[j]\n\t"
-                "s_cmp_lt_u32 %[r], %[lim]\n\t"
-                "s_cbranch_scc1 1b\n\t"
-                : [M] "+s"(M), [r] "+s"(r), [j] "=&s"(j)
-                : [jump] "v"(jump), [lim] "s"(lim)
-                : "scc");
+            u64 M = hop_walk_lim(jump, r, lim);
             if (M & stopw) {                                                       // the first cursor the speculative walk stood on as well: the walks are one from here
                 const u32 b0 = (u32)__builtin_ctzll(M & stopw);
                 met = true; M &= (1ull << b0) - 1ull; r = b0;
@@ -291,13 +275,7 @@ __device__ __forceinline__ int spec_walk(const u8* data, int ns, int limit, cons
                 int d0, l0, d1 = 0, l1 = 0; bool s0, s1;
                 const uint2 e0 = make_uint2((u32)__builtin_amdgcn_readlane((int)a.x, rel), (u32)__builtin_amdgcn_readlane((int)a.y, rel));
                 const uint2 e1 = make_uint2((u32)__builtin_amdgcn_readlane((int)b.x, rel), (u32)__builtin_amdgcn_readlane((int)b.y, rel));
-                benc_capped_cursor<MINT>(data, ns, g, p4, pm, q, limit, e0, e0.y >= ALZ_M_LONG, e1, e1.y >= ALZ_M_LONG, d0, l0, d1, l1, s0, s1);
-                j = 1; sr = 0;
-                if (l0 >= g.min_len) {
-                    const bool lazyc = l0 <= g.lazy && q + 1 <= limit;
-                    if (lazyc && l1 > l0) { sr = 2; const int e = q + 1 + l1; const int stop2 = e < limit + 1 ? e : limit + 1; j = (q + 2 > stop2 ? q + 2 : stop2) - q; }
-                    else { sr = 1; const int skip = lazyc ? 1 : 0; const int e = q + l0; const int stop2 = e < limit + 1 ? e : limit + 1; j = (q + 1 + skip > stop2 ? q + 1 + skip : stop2) - q; }
-                }
+                j = parse_capped_cursor(data, ns, g, MINT, p4, pm, q, limit, e0, e0.y >= ALZ_M_LONG, e1, e1.y >= ALZ_M_LONG, d0, l0, d1, l1, s0, s1, sr);
                 // the exact matches go into the array -- what MatchSearch returns for q and q + 1, whoever asks -- a length of 2 046 or more as its code only
                 if (lane == 0) {
                     if (s0) m[q] = m_pack((u32)d0, l0 < (int)ALZ_M_LONG ? (u32)l0 : ALZ_M_LONG);

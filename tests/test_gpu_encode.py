@@ -76,11 +76,15 @@ def _token_soup(rng, size):
     return bytes(out[:size])
 
 
-@pytest.mark.parametrize("fmt", [A.FMT_LZ4_BLOCK, A.FMT_SNAPPY_RAW, A.FMT_PRS_BE, A.FMT_PRS_LE, A.FMT_LZO, A.FMT_LZ11, A.FMT_LZ40])
-@pytest.mark.parametrize("quality", [0, 3, 8])
+@pytest.mark.parametrize("fmt", [A.FMT_LZ4_BLOCK, A.FMT_SNAPPY_RAW, A.FMT_PRS_BE, A.FMT_PRS_LE, A.FMT_LZO, A.FMT_LZ11, A.FMT_LZ40,
+                                 A.FMT_LZSS, A.FMT_LZ10, A.FMT_YAZ0, A.FMT_YAY0, A.FMT_MIO0, A.FMT_CLZ0, A.FMT_BLZ, A.FMT_LZHUDSON,
+                                 A.FMT_LZ02, A.FMT_HIG])
+@pytest.mark.parametrize("quality", [0, 3, 8, 12])
 def test_encode_window_edges(fmt, quality):
     """The kernels that walk and emit 64 positions at a time (WinParse; at quality 0 with the search inside): buffers of every length around
-    one, two and three windows, and token soup that puts starts, carried starts and match ends on every lane."""
+    one, two and three windows, and token soup that puts starts, carried starts and match ends on every lane.  Every form of the window walk
+    is here: the sequence formats (WinParse), the flag-bit family with window skipping (LZ11, LZ40) and without (the rest), and two formats whose
+    serial emitter reads the roles kernel's walk (LZ02, HIG); at quality 12 the min-length table is on and a capped cursor goes through it."""
     rng = np.random.default_rng(1000 * fmt + quality)
     sizes = list(range(1, 24)) + list(range(56, 72)) + list(range(120, 136)) + list(range(184, 200)) + [255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097]
     raws = [_token_soup(rng, n) for n in sizes] + [_token_soup(rng, int(rng.integers(300, 20000))) for _ in range(40)]
