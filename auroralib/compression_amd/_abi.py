@@ -133,6 +133,18 @@ BITLZ_PROTOTYPES = {
     "alz_allz_is_match": _BITLZ_IS_MATCH, "alz_allz_decompressed_size": _BITLZ_SIZE, "alz_allz_decompress": _BITLZ_DECOMPRESS,
 }
 
+# CRILAYLA / ALLZ written (CompressHeaderless of the two classes): batches of raw buffers (streams[i].format a BITLZ_* value, an ALLZ stream's aux0 = allz_aux0(...))
+# and the two classes' files; settings is an alz_settings* (NULL: quality 8)
+_BITENC_ENCODE = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+BITENC_PROTOTYPES = {
+    "alz_bitenc_bound": [C.c_uint32, C.c_size_t],                                  # returns size_t (BITENC_RESTYPES)
+    "alz_bitenc_encode_batch": _BITENC_ENCODE, "alz_bitenc_encode_batch_device": _BITENC_ENCODE,
+    "alz_bitenc_file_bound": [C.c_uint32, C.c_size_t],                             # returns size_t
+    "alz_bitenc_file_compress": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "alz_bitenc_file_compress_batch": _BITENC_ENCODE,
+}
+BITENC_RESTYPES = {"alz_bitenc_bound": C.c_size_t, "alz_bitenc_file_bound": C.c_size_t}
+
 # the DEFLATE entry points (decode only): batches of raw streams, their sizes without decoding, and the ZLib / GZip classes on a file in host memory
 INFLATE_WINDOW = 0x8000
 _INFLATE_DECODE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

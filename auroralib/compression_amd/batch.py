@@ -198,6 +198,29 @@ class Context:
         """alz_bitlz_decode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
         return self._device(self.lib.alz_bitlz_decode_batch_device, (), streams, d_src, src_bytes, d_dst, dst_bytes)
 
+    # ---- CRILAYLA / ALLZ written: raw buffers in (src_*), headerless bodies out (dst_*); streams[i].format is an A.BITLZ_* value
+    def bitenc_encode_batch(self, streams, src, dst_bytes, quality=8, strategy=0, dst=None):
+        """alz_bitenc_encode_batch on host buffers -> (dst, results): CompressHeaderless of the two classes, the managed bytes for the same settings.
+        A body occupies [dst_off, dst_off + dst_len); an ALLZ stream takes aux0 = A.allz_aux0(copy, dist, len).  ALLZ at quality 1 raises AlzError
+        E_UNSUPPORTED.  A lone large buffer goes through the same batch pipeline as many small ones."""
+        st = A.Settings(quality, 0, strategy, 0)
+        return self._host_decode(self.lib.alz_bitenc_encode_batch, (C.byref(st),), streams, src, dst_bytes, dst)
+
+    def bitenc_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes, quality=8, strategy=0):
+        """alz_bitenc_encode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
+        st = A.Settings(quality, 0, strategy, 0)
+        return self._device(self.lib.alz_bitenc_encode_batch_device, (C.byref(st),), streams, d_src, src_bytes, d_dst, dst_bytes)
+
+    def bitenc_file_compress_batch(self, files, src, dst_bytes, quality=8, strategy=0, dst=None):
+        """alz_bitenc_file_compress_batch on host buffers -> (dst, results): per file (Stream.format an A.BITLZ_* value, aux0 ALLZ's start bits) what
+        alz_bitenc_file_compress writes and returns for it alone; all bodies are one encode batch."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        st = A.Settings(quality, 0, strategy, 0)
+        check(self.lib.alz_bitenc_file_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
     # ---- DEFLATE (decode only): raw streams as zlib's inflate reads them; format, decom_len, aux0 and aux1 of a stream are ignored
     def inflate_decode_batch(self, streams, src, dst_bytes, dst=None):
         """alz_inflate_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""

@@ -135,7 +135,7 @@ struct alz_ctx {
     void* d_plan = nullptr; size_t d_plan_cap = 0;   // plan arrays of the host-buffer entry points (no hipMalloc / hipFree per call)
     // encoder scratch (prev links, narrowed links, matches, masks ...: ~45 GB for 10 000 x 256 KiB at quality 8), one grow-only slot
     // per purpose: allocating and freeing it per call cost 1-2 s, four times the kernels.  alz_ctx_release_scratch() returns it.
-    enum { ENC_STREAMS, ENC_RESULTS, ENC_AUX, ENC_INDEX, ENC_POS, ENC_PREV4, ENC_PREVM, ENC_MATCH, ENC_SIDE, ENC_MASK, ENC_TAIL, ENC_BIG, ENC_SEL, ENC_NARROW, ENC_SEG, ENC_DEFLATE, ENC_SLOTS };
+    enum { ENC_STREAMS, ENC_RESULTS, ENC_AUX, ENC_INDEX, ENC_POS, ENC_PREV4, ENC_PREVM, ENC_MATCH, ENC_SIDE, ENC_MASK, ENC_TAIL, ENC_BIG, ENC_SEL, ENC_NARROW, ENC_SEG, ENC_DEFLATE, ENC_REV, ENC_SLOTS };
     void* enc_buf[ENC_SLOTS] = {nullptr}; size_t enc_cap[ENC_SLOTS] = {0};
     copy_pool* pool = nullptr;                 // created with the pinned buffers
     std::vector<copy_job> jobs;                // (scratch of the staging loops)
@@ -219,7 +219,7 @@ static int validate_streams(const char* what, uint32_t kinds, uint32_t n, const 
 
 // The streams of a batch grouped per kind: `index` lists the stream numbers kind after kind, a kind's streams in input order; off[k] / cnt[k] is
 // where kind k's list starts and how many it holds.  With a cost(i) the costliest streams of a kind come first (equal costs in input order).
-static const uint32_t kMaxKinds = ALZ_FMT_COUNT;
+static const uint32_t kMaxKinds = ALZ_ENCFMT_COUNT;   // (the encoder's slots: the public formats, FastLZ level 2, the two internal ones of alz_bitlz.h)
 static_assert(ALZ_RLH_COUNT <= kMaxKinds && ALZ_BITLZ_COUNT <= kMaxKinds, "the per-kind counters of group_streams");
 template <class KindOf>
 static void group_streams(uint32_t n, uint32_t kinds, KindOf kind_of, std::vector<uint32_t>& index, uint32_t* off, uint32_t* cnt) {
@@ -1453,7 +1453,8 @@ static inline bool fastlz_level2(const alz_settings& st, uint32_t src_len) { ret
 // only -- point at the copy; offsets are differences of device addresses).
 // encode_core runs the stages below in turn; what one stage works out for the next travels in these three structs.
 namespace {
-// One format slot of a batch: ALZ_FMT_COUNT slots for the formats and a last one for FastLZ level 2, which has a geometry and a launch of its own
+// One format slot of a batch: ALZ_FMT_COUNT slots for the public formats, one for FastLZ level 2, which has a geometry and a launch of its own, and behind it
+// the internal formats of alz_bitlz.h (CRILAYLA, ALLZ), which only alz_bitenc_encode_batch* can name: ALZ_ENCFMT_COUNT in all
 struct enc_slot {
     unsigned char* geom = nullptr;                 // alz_encode_geometry's bytes (all zero while the batch has no stream of the slot)
     uint32_t seg_len = 0, seg_kmax = 0;            // the segmented parse + emit (alz_encode_seg.h) takes the slot's launch: segment length and segments per buffer
@@ -1461,10 +1462,10 @@ struct enc_slot {
 };
 struct enc_batch {
     alz_settings st; alz_lz_properties lz;
-    uint32_t cnt[ALZ_FMT_COUNT], off[ALZ_FMT_COUNT];   // per format; a FastLZ list holds the level-1 streams first, then the n_fastlz2 level-2 ones
+    uint32_t cnt[ALZ_ENCFMT_COUNT], off[ALZ_ENCFMT_COUNT];   // per format (slot ALZ_FMT_COUNT stays empty here); a FastLZ list holds the level-1 streams first, then the n_fastlz2 level-2 ones
     std::vector<uint32_t> index; std::vector<uint64_t> pos_off;   // pos_off: where a stream's positions start in the per-position scratch arrays, `total` positions in all
     uint64_t total = 0; uint32_t max_len = 0, n_fastlz2 = 0;
-    std::vector<unsigned char> geom_bytes; enc_slot slot[ALZ_FMT_COUNT + 1]; size_t seg_bytes = 0;
+    std::vector<unsigned char> geom_bytes; enc_slot slot[ALZ_ENCFMT_COUNT]; size_t seg_bytes = 0;
     bool any(bool enc_slot::*need) const { for (const enc_slot& s : slot) if (s.*need) return true; return false; }
 };
 // The device side of one call, shared by its two paths: the buffers `upload` hands over (once), and the streams relocated out of a caller's tail
@@ -1476,19 +1477,20 @@ struct enc_io {
 };
 }
 // Stage 1: the settings, then the streams
-static int enc_validate(const alz_settings* settings, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes, alz_settings* out) {
+// (`kinds`: ALZ_FMT_COUNT for the public entry points -- an internal format is an unknown one there --, ALZ_ENCFMT_COUNT for alz_bitenc_encode_batch*' translated table)
+static int enc_validate(const alz_settings* settings, uint32_t kinds, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes, alz_settings* out) {
     alz_settings st; if (settings) st = *settings; else { st.quality = 8; st.max_window_bits = 0; st.strategy = 0; st.min_distance = 0; }
     if (st.quality < 0 || st.quality > 15) return fail(ALZ_E_INVALID, "quality %d outside 0..15 (CompressionSettings.cs:38-50)", st.quality);
     if (st.max_window_bits < 0 || st.max_window_bits > 24) return fail(ALZ_E_INVALID, "max_window_bits %d outside 0..24", st.max_window_bits);
     *out = st;
-    return validate_streams("", ALZ_FMT_COUNT, n, streams, &src_bytes, &dst_bytes, [](uint32_t i, const alz_stream& s) -> int {
+    return validate_streams("", kinds, n, streams, &src_bytes, &dst_bytes, [](uint32_t i, const alz_stream& s) -> int {
         return s.src_len > 0x7FFFFF00u ? fail(ALZ_E_UNSUPPORTED, "stream %u: inputs above 2 GiB are not supported", i) : ALZ_OK;
     });
 }
 // Stage 2: the streams grouped per format, their places in the per-position arrays, and the geometry of every format slot present
 static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams, enc_batch* b) {
     const alz_settings& st = b->st;
-    group_streams(n, ALZ_FMT_COUNT, [&](uint32_t i) { return streams[i].format; }, b->index, b->off, b->cnt);
+    group_streams(n, ALZ_ENCFMT_COUNT, [&](uint32_t i) { return streams[i].format; }, b->index, b->off, b->cnt);
     const uint32_t* cnt = b->cnt;
     b->pos_off.resize(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -1501,12 +1503,16 @@ static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams,
                               [&](uint32_t i) { return !fastlz_level2(st, streams[i].src_len); });
     const uint32_t n_fastlz2 = b->n_fastlz2, max_len = b->max_len;
     if (cnt[ALZ_FMT_LZSS] && (!lzss_on_gpu(b->lz) || b->lz.max_distance != (1u << b->lz.window_bits))) return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path");
-    b->geom_bytes.resize((ALZ_FMT_COUNT + 1) * alz_encode_geom_size());   // (zeros) last slot: FastLZ level 2
-    for (int f = 0; f <= ALZ_FMT_COUNT; f++) {
+    b->geom_bytes.resize(ALZ_ENCFMT_COUNT * alz_encode_geom_size());   // (zeros) slot ALZ_FMT_COUNT: FastLZ level 2
+    for (int f = 0; f < ALZ_ENCFMT_COUNT; f++) {
         enc_slot& s = b->slot[f];
         void* g = s.geom = b->geom_bytes.data() + f * alz_encode_geom_size();
         const bool lvl2 = f == ALZ_FMT_COUNT;
         if (lvl2 ? !n_fastlz2 : !(cnt[f] - (f == ALZ_FMT_FASTLZ ? n_fastlz2 : 0u))) continue;
+        // ALLZ at quality 1: maxChain is 2 and the managed chain table has 1 << min(17 + 1, 19) slots for a window of 1 << 19, so a slot is reused INSIDE
+        // maxDistance and GetNext is no longer prev() (LzChainMatchFinder.cs:94-96; alz_encode_geometry's check): what the kernels compute is not what it finds
+        if (f == ALZ_ENCFMT_ALLZ && st.quality == 1)
+            return fail(ALZ_E_UNSUPPORTED, "ALLZ at quality 1: the managed chain table (2^18 slots) is smaller than the 2^19 window, its links are not prev(): not reproduced on the GPU (every other quality 0..15 is)");
         alz_settings sf = st;
         if (st.max_window_bits != 0 && f != ALZ_FMT_FASTLZ && !lvl2) {
             // CompressionSettings.MaxWindowBits can only WIDEN the finder (windowsBits = max(.., maxWindowBits), maxDistance = max(.., 1 <<
@@ -1520,7 +1526,7 @@ static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams,
                 return fail(ALZ_E_UNSUPPORTED, "format %d: CompressionSettings.MaxWindowBits %d is beyond the format's window (%d bits, distances up to %d): "
                             "the managed finder would return distances the format cannot store", f, st.max_window_bits, wb0, alz_encode_geom_max_dist(g));
         }
-        if (!alz_encode_geometry(lvl2 ? ALZ_FMT_FASTLZ : f, &b->lz, &sf, g, nullptr, lvl2 ? 1 : 0))
+        if (!alz_encode_geometry(lvl2 ? ALZ_FMT_FASTLZ : f, &b->lz, &sf, g, nullptr, (lvl2 || (f > ALZ_FMT_COUNT && c->exact)) ? 1 : 0))   // (CRILAYLA, ALLZ: 1 = their lone-lane emitters)
             return fail(ALZ_E_UNSUPPORTED, "format %d: geometry not supported by the GPU encoder", lvl2 ? ALZ_FMT_FASTLZ : f);
         s.min_table = alz_encode_geom_min_table(g);
         s.narrows = alz_encode_geom_narrows(g);
@@ -1585,7 +1591,8 @@ static bool enc_takes_big_path(const alz_ctx* c, const enc_batch& b, uint32_t n,
 static hipError_t enc_relocate_tails(alz_ctx* c, enc_io& io, uint32_t n, const alz_stream* streams) {
     if (io.src_has_slack || io.tails_done) return hipSuccess;
     io.tails_done = true;
-    auto in_tail = [&](const alz_stream& s) { return s.src_off + s.src_len + 64 > io.src_bytes; };
+    // (a CRILAYLA stream is never searched where it lies: the batch path reverses it into scratch of its own, with room behind it)
+    auto in_tail = [&](const alz_stream& s) { return s.format != ALZ_ENCFMT_CRILAYLA && s.src_off + s.src_len + 64 > io.src_bytes; };
     auto room = [](const alz_stream& s) { return ((size_t)s.src_len + 64 + 63) & ~(size_t)63; };
     size_t bytes = 0; for (uint32_t i = 0; i < n; i++) if (in_tail(streams[i])) bytes += room(streams[i]);
     if (!bytes) return hipSuccess;
@@ -1658,6 +1665,13 @@ static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n
     uint32_t* d_sel = (uint32_t*)sc.get(alz_ctx::ENC_SEL, ((size_t)4 * n + 128) * sizeof(uint32_t), any_match);     // which kernel B per stream (enc_probe_kernel); behind it the two lists of enc_scan_select_kernel
     int* d_narrow = (int*)sc.get(alz_ctx::ENC_NARROW, (size_t)total * sizeof(int) + 256, any_narrow);   // the links of the finder's own hash width, narrowed from 15-bit ones (enc_narrow_kernel)
     void* d_seg = sc.get(alz_ctx::ENC_SEG, b.seg_bytes, b.seg_bytes != 0);                              // segment records of alz_encode_seg.h
+    // CRILAYLA: every stream's reversed copy, 64 readable bytes behind each, in front of them the streams' own source offsets (what enc_bits_reverse_kernel reads from)
+    auto rev_room = [](const alz_stream& s) { return ((size_t)s.src_len + 64 + 63) & ~(size_t)63; };
+    const size_t rev_head = ((size_t)n * sizeof(uint64_t) + 255) & ~(size_t)255;
+    size_t rev_bytes = rev_head; std::vector<uint64_t> orig_off;
+    if (cnt[ALZ_ENCFMT_CRILAYLA]) for (uint32_t i = 0; i < n; i++) if (streams[i].format == ALZ_ENCFMT_CRILAYLA) rev_bytes += rev_room(streams[i]);
+    uint8_t* d_rev = (uint8_t*)sc.get(alz_ctx::ENC_REV, rev_bytes, cnt[ALZ_ENCFMT_CRILAYLA] != 0);
+    const uint64_t* d_orig = (const uint64_t*)d_rev;
     if (sc.err != hipSuccess) return fail(ALZ_E_NOMEM, "encoder scratch allocation failed: %s", hipGetErrorString(sc.err));
     io.tm.mark("validate + allocate");
     int rc = io.stage();
@@ -1667,6 +1681,18 @@ static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n
     rc = launch_bracket(c, "alz_encode_batch",
         [&] {   // (the tables are read out of `io.moved`, `b` and the caller's table: the bracket waits for the copies)
             hipError_t e = enc_relocate_tails(c, io, n, streams);
+            if (e == hipSuccess && d_rev) {     // (the device copy of the descriptors points at the reversed bytes, as it does at a relocated tail)
+                if (io.moved.empty()) io.moved.assign(streams, streams + n);
+                orig_off.resize(n);
+                uint8_t* to = d_rev + rev_head;
+                for (uint32_t i = 0; i < n; i++) {
+                    orig_off[i] = io.moved[i].src_off;
+                    if (streams[i].format != ALZ_ENCFMT_CRILAYLA) continue;
+                    io.moved[i].src_off = (uint64_t)(uintptr_t)to - (uint64_t)(uintptr_t)io.d_src;
+                    to += rev_room(streams[i]);
+                }
+                e = hipMemcpyAsync(d_rev, orig_off.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+            }
             if (e == hipSuccess) e = hipMemcpyAsync(d_streams, io.moved.empty() ? streams : io.moved.data(), (size_t)n * sizeof(alz_stream), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(d_index, b.index.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(d_pos, b.pos_off.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
@@ -1676,7 +1702,7 @@ static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n
             return e;
         },
         [&] {   // table resets + the encode kernels
-            for (int f = 0; f <= ALZ_FMT_COUNT; f++) {
+            for (int f = 0; f < ALZ_ENCFMT_COUNT; f++) {
                 const bool lvl2 = f == ALZ_FMT_COUNT;
                 const int fmt = lvl2 ? ALZ_FMT_FASTLZ : f;
                 const uint32_t first = b.off[fmt] + (lvl2 ? cnt[fmt] - b.n_fastlz2 : 0u);
@@ -1684,6 +1710,8 @@ static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n
                 const enc_slot& s = b.slot[f];
                 for (uint32_t done = 0; done < count; done += CH) {
                     const uint32_t k = count - done < CH ? count - done : CH;
+                    if (f == ALZ_ENCFMT_CRILAYLA)                                  // the finder runs over the reversed source  CRILAYLA.cs:204-206
+                        if (const hipError_t er = alz_launch_encode_reverse(c->stream, io.d_src, d_rev, d_streams, d_orig, d_index + first + done, k, b.max_len)) return er;
                     // (positional on purpose: the prototype lives in alz_internal.h, which the decode counters are hashed over -- a struct in its place belongs to the change that next re-profiles the decoder)
                     const hipError_t e = alz_launch_encode(fmt, c->stream, io.d_src, io.d_dst, d_streams, d_index + first + done, k, b.max_len, d_prev4, d_prevm, d_narrow,
                                           d_match, d_pos, d_side, d_mask, d_results, d_aux, s.geom, d_sel, n, s.seg_len ? d_seg : nullptr, s.seg_len, s.seg_kmax, (c->exact || c->variant != 0) ? 2 : c->scan_mode, c->d_big_accepted ? c->d_big_accepted + 1 : nullptr, &side_q);
@@ -1701,9 +1729,10 @@ static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n
     return ALZ_OK;
 }
 static int encode_core(alz_ctx* c, const alz_lz_properties* props, const alz_settings* settings, uint32_t n, size_t src_bytes, const alz_stream* streams,
-                       size_t dst_bytes, alz_result* results, alz_encode_aux* aux, const std::function<int(const void*&, void*&)>& upload, bool src_has_slack = true) {
+                       size_t dst_bytes, alz_result* results, alz_encode_aux* aux, const std::function<int(const void*&, void*&)>& upload, bool src_has_slack = true,
+                       uint32_t kinds = ALZ_FMT_COUNT) {
     enc_batch b; int rc;
-    if ((rc = enc_validate(settings, n, src_bytes, streams, dst_bytes, &b.st))) return rc;
+    if ((rc = enc_validate(settings, kinds, n, src_bytes, streams, dst_bytes, &b.st))) return rc;
     b.lz = effective_lz(props);
     enc_io io{upload, src_bytes, src_has_slack, phase_timer("alz_encode_batch")};
     if ((rc = enc_geometry(c, n, streams, &b))) return rc;
@@ -1734,6 +1763,57 @@ int alz_encode_batch_device(alz_ctx* c, const alz_lz_properties* props, const al
     if (n == 0) return ALZ_OK;
     return encode_core(c, props, settings, n, src_bytes, streams, dst_bytes, results, aux,
                        [&](const void*& ds, void*& dd) { ds = d_src_base; dd = d_dst_base; return (int)ALZ_OK; }, false);
+}
+
+// ---------------------------------------------------------------- CRILAYLA / ALLZ bodies written (alz_encode.hip): CompressHeaderless of the two classes
+// streams[i].format is an alz_bitlz_kind; the table the encoder sees names the internal formats behind the public enum.  A lone large buffer goes
+// through the batch pipeline like any other (no whole-GPU path, no segments: the two formats have rows without them in ALZ_ENC_PATHS).
+size_t alz_bitenc_bound(uint32_t kind, size_t src_len) {
+    // CRILAYLA: nine bits per literal; a match (16 bits for three bytes, 14 + 10 + 8 per 255 further ones) is never more than its bytes as literals.
+    if (kind == ALZ_BITLZ_CRILAYLA) return (src_len * 9 + 7) / 8;
+    // ALLZ: at most src_len / 3 + 1 units of [run?][match].  WriteALFlag(start, v) writes 2 * bits - start + 1 bits with bits <= max(start, bitlen(v) + 1):
+    // at most 39 for a distance or a length (v < 2^19, start <= 24), at most 28 + 2 * bitlen(run) for a run, and the bit lengths of all runs add up to
+    // no more than their bytes.  So 1 + 28 + 39 + 39 = 107 bits per unit, 2 * src_len bits for the runs' lengths, the runs themselves and the last byte.
+    if (kind == ALZ_BITLZ_ALLZ) return src_len + src_len / 4 + 14 * (src_len / 3 + 1) + 2;
+    return 0;
+}
+
+static int bitenc_batch(alz_ctx* c, bool device, const alz_settings* settings, uint32_t n, const void* src_base, size_t src_bytes, const alz_stream* streams,
+                        void* dst_base, size_t dst_bytes, alz_result* results) {
+    const char* what = device ? "alz_bitenc_encode_batch_device" : "alz_bitenc_encode_batch";
+    if (!c || (n && (!streams || !results || !dst_base || (device && !src_base)))) return fail(ALZ_E_INVALID, "%s: bad argument", what);
+    if (n == 0) return ALZ_OK;
+    // (the finder's settings: what enc_validate lets through, less the two that would make the managed finder return what neither format can store)
+    if (settings && settings->max_window_bits != 0) return fail(ALZ_E_UNSUPPORTED, "%s: max_window_bits %d: CRILAYLA and ALLZ are written at their own windows only", what, settings->max_window_bits);
+    if (settings && settings->min_distance != 0) return fail(ALZ_E_UNSUPPORTED, "%s: min_distance %d: CRILAYLA and ALLZ are written at their own minimum distances only", what, settings->min_distance);
+    std::vector<alz_stream> table(streams, streams + n);
+    for (uint32_t i = 0; i < n; i++) {
+        alz_stream& s = table[i];
+        if (s.format >= ALZ_BITLZ_COUNT) return fail(ALZ_E_INVALID, "%s: stream %u: unknown format / kind %u", what, i, s.format);
+        if (s.format == ALZ_BITLZ_ALLZ) {
+            if ((s.aux0 & 0xFFu) > 24u || ((s.aux0 >> 8) & 0xFFu) > 24u || ((s.aux0 >> 16) & 0xFFu) > 24u || (s.aux0 >> 24))
+                return fail(ALZ_E_INVALID, "%s: stream %u: ALLZ start bits 0x%x outside 0..24 each", what, i, s.aux0);
+            if (s.src_len > 0x40000000u) return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: ALLZ sources above 0x40000000 bytes are not supported (WriteALFlag's int sums)", what, i);
+        }
+        s.format = s.format == ALZ_BITLZ_CRILAYLA ? (uint32_t)ALZ_ENCFMT_CRILAYLA : (uint32_t)ALZ_ENCFMT_ALLZ;
+    }
+    if (device)
+        return encode_core(c, nullptr, settings, n, src_bytes, table.data(), dst_bytes, results, nullptr,
+                           [&](const void*& ds, void*& dd) { ds = src_base; dd = dst_base; return (int)ALZ_OK; }, false, ALZ_ENCFMT_COUNT);
+    const int rc = encode_core(c, nullptr, settings, n, src_bytes, table.data(), dst_bytes, results, nullptr, [&](const void*& ds, void*& dd) {
+        const int r = stage_source(c, (const uint8_t*)src_base, src_bytes, true, dst_bytes);
+        ds = c->d_src; dd = c->d_dst;
+        return r;
+    }, true, ALZ_ENCFMT_COUNT);
+    return rc ? rc : download_outputs(c, n, streams, results, (uint8_t*)dst_base, true);
+}
+int alz_bitenc_encode_batch(alz_ctx* c, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                            uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return bitenc_batch(c, false, settings, n, src_base, src_bytes, streams, dst_base, dst_bytes, results);
+}
+int alz_bitenc_encode_batch_device(alz_ctx* c, const alz_settings* settings, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                   uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    return bitenc_batch(c, true, settings, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
 }
 
 // ---------------------------------------------------------------- multi-GPU: one batch over several contexts

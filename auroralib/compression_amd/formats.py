@@ -907,14 +907,57 @@ class RLHudson(_WrappedFile):
 WRAPPED_FORMATS = [AsuraZlb, ZLB, MDF0, RareZip, HWGZ, SSZL, ZLWF, RLHudson]
 
 BITLZ_NO_ENCODER = ("%s has no encoder here: CompressHeaderless runs the LzChainMatchFinder, the bar is bit-identity with the managed bytes checked against "
-                    "the CPU oracle, and there is no oracle body to hold bit-identity against (include/auroralz.h)")
+                    "the CPU oracle, and there is no oracle body to hold bit-identity against (include/auroralz.h).  Encode(data, settings) writes the file "
+                    "on the GPU: its bit-identity is held against a Python restatement of the finder that is pinned to the oracle through other formats")
 
 
 class _BitLzFile:
-    """A class of the .Extended assembly over its alz_<prefix>_* file entry points (alz_bitlz_decode_batch underneath); decode only.
-    No alz_container value backs it, so it stays outside ALL_FORMATS."""
+    """A class of the .Extended assembly over its alz_<prefix>_* file entry points (alz_bitlz_decode_batch underneath) and, for writing,
+    alz_bitenc_file_* (Encode / EncodeMany; Compress still refuses).  No alz_container value backs it, so it stays outside ALL_FORMATS."""
     provides_size = True
     prefix = None
+    kind = None
+
+    def _aux0(self):
+        return 0
+
+    def Encode(self, data, settings=None):
+        """The file Compress of the reference writes for these settings (alz_bitenc_file_compress): the finder and the bit emitter on the GPU.
+        A lone large input goes through the batch pipeline -- there is no whole-GPU path for these two formats.  Refused: MaxWindowBits other than 0,
+        ALLZ at quality 1 (E_UNSUPPORTED), a CRILAYLA source under 0x100 bytes (E_INVALID)."""
+        data = bytes(data)
+        settings = settings or CompressionSettings.Balanced
+        lib = load()
+        cap = lib.alz_bitenc_file_bound(self.kind, len(data))
+        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
+        dl = C.c_size_t()
+        st = A.Settings(settings.Quality, settings.MaxWindowBits, settings.Strategy, 0)
+        check(lib.alz_bitenc_file_compress(_context().h, self.kind, C.byref(st), self._aux0(), data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
+        return dst_arr[:dl.value].tobytes()
+
+    def EncodeMany(self, datas, settings=None):
+        """Encode for a whole set of inputs in ONE alz_bitenc_file_compress_batch (one encode batch).  Returns a list with, per input, the file's
+        bytes -- or the exception instance Encode would have raised for it."""
+        datas = [bytes(d) for d in datas]
+        settings = settings or CompressionSettings.Balanced
+        if settings.MaxWindowBits:
+            raise AlzError(A.E_UNSUPPORTED, "MaxWindowBits %d: CRILAYLA and ALLZ are written at their own windows only" % settings.MaxWindowBits)
+        lib = load()
+        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
+        table, so, do = (A.Stream * len(datas))(), 0, 0
+        for i, d in enumerate(datas):
+            cap = lib.alz_bitenc_file_bound(self.kind, len(d))
+            table[i] = A.Stream(so, do, len(d), cap, 0, self._aux0(), 0, self.kind)
+            so += len(d)
+            do += (cap + 15) & ~15
+        dst, res = _context().bitenc_file_compress_batch(table, src, do, settings.Quality, settings.Strategy)
+        out = []
+        for i, r in enumerate(res):
+            if r.rc:
+                out.append(AlzError(r.rc, "alz_bitenc_file_compress_batch: file %d" % i))
+            else:
+                out.append(dst[table[i].dst_off:table[i].dst_off + r.dst_len].tobytes())
+        return out
 
     def IsMatch(self, data):
         data = bytes(data)
@@ -948,12 +991,17 @@ class CRILAYLA(_BitLzFile):
     """src/AuroraLib.Compression-Extended/CRI/CRILAYLA.cs -- "CRILAYLA" + size + csize + body + 0x100 plain header bytes (alz_crilayla_*).
     Decompress returns size + 0x100 bytes: the header bytes first, the body -- decoded from its last byte down -- behind them."""
     prefix = "crilayla"
+    kind = A.BITLZ_CRILAYLA
 
 
 class ALLZ(_BitLzFile):
     """src/AuroraLib.Compression-Extended/Specialized/ALLZ.cs -- "ALLZ" + 4 flag bytes + size + body (alz_allz_*).  The three fields are
     what Compress would write into the header (ALLZ.cs:34-36); Decompress takes them from the file."""
     prefix = "allz"
+    kind = A.BITLZ_ALLZ
+
+    def _aux0(self):
+        return A.allz_aux0(self.LzCopyBits, self.LzDistanceBits, self.LzLengthBits)
 
     def __init__(self):
         self.LzCopyBits, self.LzDistanceBits, self.LzLengthBits = 0, 10, 1

@@ -471,8 +471,9 @@ int alz_aplib_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8
  *   a needed flag byte is missing, or the input holds fewer bytes than a run (after clipping) needs: INPUT_TRUNCATED, src_used = src_len;
  *                               the run bytes that exist are copied.
  *   decom_len 0                 OK, nothing read.       success: OK, dst_len == decom_len, src_used = the input position.
- * THERE IS NO ENCODER for either: the project's bar is bit-identity with the managed bytes checked against the CPU oracle, and the oracle
- *   has neither body.  alz_brute_force and alz_container_scan do not try them. */
+ * THE ENCODER is alz_bitenc_* below.  The CPU oracle has neither body, so its bit-identity with the managed bytes is held against a Python
+ *   restatement of LzChainMatchFinder and of the two CompressHeaderless bodies, and that restatement is pinned to the oracle through the formats
+ *   the oracle does have.  alz_brute_force and alz_container_scan do not try the two formats. */
 typedef enum alz_bitlz_kind { ALZ_BITLZ_CRILAYLA = 0, ALZ_BITLZ_ALLZ = 1, ALZ_BITLZ_COUNT = 2 } alz_bitlz_kind;
 #define ALZ_ALLZ_AUX0(copy_bits, dist_bits, len_bits)  ((copy_bits) | (dist_bits) << 8 | (len_bits) << 16)   /* flags[1], flags[2], flags[3] */
 int alz_bitlz_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
@@ -503,6 +504,51 @@ int alz_allz_is_match(const uint8_t* src, size_t src_len);
 int alz_allz_decompressed_size(const uint8_t* src, size_t src_len, uint32_t* size_out);
 int alz_allz_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_t* dst, size_t dst_cap,
                         size_t* dst_len, size_t* src_used, int32_t* status);
+
+/* ---------------------------------------- CRILAYLA and ALLZ written: CompressHeaderless of the two classes (CRILAYLA.cs:190-258, ALLZ.cs:129-174)
+ * Both bodies run LzChainMatchFinder, so the encoder's finder kernels serve them: the bytes are those of the managed code for the same
+ * CompressionSettings.  streams[i].format is an alz_bitlz_kind (anything else: ALZ_E_INVALID); a batch may mix both kinds.  src_* is the raw
+ * input, dst_* where the body goes: it occupies [dst_off, dst_off + dst_len) -- CRILAYLA's too, which the managed code writes from the end of
+ * its array downwards: the bytes are the same.  alz_result is { OK, dst_len, src_used = src_len }; a body that does not fit dst_cap is
+ * ALZ_ST_OUTPUT_CAPACITY with dst_len 0, and nothing outside [dst_off, dst_off + dst_cap) is ever written.  alz_bitenc_bound(kind, n) is the
+ * worst case of the body and always suffices: 9 n / 8 for CRILAYLA, which is tight.  For ALLZ it is LOOSE, about 5.9 n: it knows neither
+ * aux0 nor the data and charges every three source bytes a unit of maximal fields (a bound from aux0 and the 2^19 distance limit would be
+ * several times tighter: not built).  A caller short of memory may give a smaller dst_cap and handle ALZ_ST_OUTPUT_CAPACITY.  The file layer
+ * sizes its slots by the bound.
+ * settings: NULL = quality 8.  quality outside 0..15: ALZ_E_INVALID.  max_window_bits other than 0, and min_distance other than 0:
+ *   ALZ_E_UNSUPPORTED (the managed finder would return what neither format stores).  ALLZ AT QUALITY 1 IS ALZ_E_UNSUPPORTED: maxChain is 2
+ *   and the managed chain table has 2^18 slots for a 2^19 window, so its links are not what the kernels compute (LzChainMatchFinder.cs:94-96);
+ *   every other quality 0..15 is supported for both kinds.
+ * CRILAYLA: LzProperties(0x2000, 65535, 3, 0, 3); the finder runs over the REVERSED source (:204-206), reversed on the device.  aux0 ignored.
+ * ALLZ: five tiered LzProperties, a 512 KiB window, lengths to 0x40000.  aux0 = ALZ_ALLZ_AUX0(copy, dist, len), each 0..24, else
+ *   ALZ_E_INVALID.  src_len above 0x40000000: ALZ_E_UNSUPPORTED (within it WriteALFlag's int sums do not wrap).  Empty input: the byte 01.
+ * One wavefront writes one stream's bits, placed by prefix sums; alz_ctx_set_exact_kernels selects the form in which one lane writes them token
+ *   by token: the same bytes.  A lone large buffer goes through the same batch pipeline as many small ones: neither format has a whole-GPU
+ *   path or a segmented walk.  The device form needs no slack behind its source (streams at the buffer's end are
+ *   copied to scratch, as alz_encode_batch_device does).  alz_last_kernel_ms reports the device time of the call's launches.
+ * The file layer, host memory.  kind is an alz_bitlz_kind.
+ *   CRILAYLA (Compress, :102-121): a source under 0x100 bytes is ALZ_E_INVALID.  "CRILAYLA", u32 LE src_len - 0x100, u32 LE csize, the body of
+ *     source[0x100:], then source[:0x100].  The managed class rents src_len + 10 % for the body and fails where nine bits per literal (12.5 %)
+ *     run out of it; the library writes the file a large enough array would have given.  aux0 ignored.
+ *   ALLZ (Compress, :78-88): "ALLZ", { 0, copy, dist, len } from aux0, u32 LE src_len, the body.
+ *   alz_bitenc_file_compress: a dst_cap that is too small is ALZ_E_NOMEM (*dst_len 0); alz_bitenc_file_bound(kind, n) suffices.
+ *   alz_bitenc_file_compress_batch: files[i].format the kind, files[i].aux0 ALLZ's start bits; all bodies of the call are ONE
+ *     alz_bitenc_encode_batch.  results[i] is { ALZ_OK, ALZ_ST_OK, dst_len, src_len } and the bytes of the single-file call on file i alone,
+ *     or { that call's code, ALZ_ST_OK, 0, 0 }: one file's failure is that file's rc, nothing outside a file's slot is written.
+ * NOT BUILT: aPLib (distances of exactly 2^21, one more than a match entry holds;
+ *   lwm / lastOffset state in its emitter), device-resident file forms, shim classes. */
+size_t alz_bitenc_bound(uint32_t kind, size_t src_len);
+int alz_bitenc_encode_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                            const alz_stream* streams, uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_bitenc_encode_batch_device(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                                   const alz_stream* streams, uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+struct alz_file_result;                            /* (defined with alz_zfile_* below) */
+size_t alz_bitenc_file_bound(uint32_t kind, size_t src_len);
+int alz_bitenc_file_compress(alz_ctx* ctx, uint32_t kind, const alz_settings* settings, uint32_t aux0, const uint8_t* src, size_t src_len,
+                             uint8_t* dst, size_t dst_cap, size_t* dst_len);
+int alz_bitenc_file_compress_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                                   const alz_stream* files, uint8_t* dst_base, size_t dst_bytes, struct alz_file_result* results);
 
 /* ---------------------------------------- DEFLATE: raw streams, their sizes, ZLib and GZip files (decode only)
  * The reference hands the bodies of its ZLib and GZip classes (src/AuroraLib.Compression/Formats/Common/ZLib.cs:30-34, GZip.cs:29-34) and

@@ -157,6 +157,20 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib)] internal static extern int alz_allz_decompress(IntPtr ctx, byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap,
             UIntPtr* dstLen, UIntPtr* srcUsed, int* status);
 
+        // CRILAYLA and ALLZ written on the GPU (CompressHeaderless of the two classes, the managed bytes for the same settings): raw buffers in
+        // batches (AlzStream.format is an alz_bitlz_kind, an ALLZ stream's aux0 its three start bits; the body occupies [dstOff, dstOff + dstLen)),
+        // and the two classes' files, one or a batch.  ALLZ at quality 1 is refused (ALZ_E_UNSUPPORTED); CRILAYLA.Compress / ALLZ.Compress stay managed
+        [DllImport(Lib)] internal static extern UIntPtr alz_bitenc_bound(uint kind, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_bitenc_encode_batch(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_bitenc_encode_batch_device(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern UIntPtr alz_bitenc_file_bound(uint kind, UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_bitenc_file_compress(IntPtr ctx, uint kind, AlzSettings* settings, uint aux0,
+            byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap, UIntPtr* dstLen);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_bitenc_file_compress_batch(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
+
         // DEFLATE as zlib's inflate reads it (the body of ZLib / GZip, which the managed classes hand to the BCL), decode only: raw streams in
         // batches (format, decomLen, aux0, aux1 of a stream are ignored), their sizes without decoding, and the two classes on a whole file in
         // host memory (checksums verified on the host; *_measure takes them as correct)
