@@ -105,6 +105,9 @@ def test_encode_compatibility_mode(test_bmp):
 def test_encode_lzss_geometries(test_bmp):
     for bits in [(10, 6, 2), (12, 4, 2), (8, 4, 2)]:
         _encode_and_compare(A.FMT_LZSS, [test_bmp[:30000], bytes(1000)], 8, lz=A.LzProperties.from_bits(*bits))
+    # windows on both sides of the 16-bit links (max_dist <= 0xFFFF: (15, 6, 2) is under the line, (16, 8, 2) -- 65536 -- over it), on inputs longer than the window
+    for bits in [(14, 4, 2), (15, 6, 2), (16, 8, 2)]:
+        _encode_and_compare(A.FMT_LZSS, [test_bmp[100000:100000 + 70000], test_bmp[300000:300000 + 200000]], 8, lz=A.LzProperties.from_bits(*bits))
 
 
 def test_encode_synthetic_decoded_batch():
