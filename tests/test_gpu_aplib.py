@@ -420,3 +420,23 @@ def test_file_layer():
             select(0, 0)
     with pytest.raises(NotImplementedError):
         ap.Compress(data)
+
+
+def test_single_literals_at_the_ring_seam():
+    """aPLib is the one read-back configuration of the chunked copy phase with SINGLE literals: emit_steps stores them after the step's reads, into the ring and --
+    for the first 32 slots -- into the mirror behind it (csrc/alz_emit_chunk.h:266-271).  A literal at ring offset 4096 k + {0, 1, 31, 32}, then a match
+    whose source crosses that seam (near: it holds the literal) or the seam before it (read back), then matches of distance 4095 and 4096 with a literal directly
+    behind them: that literal's ring slot is the one the last / the byte behind the last source byte had 4096 bytes ago."""
+    items = []
+    for k in (1, 2, 5):
+        for off in (0, 1, 31, 32):
+            P = 4096 * k + off
+            for L in (8, 20):
+                near, far = off + 9, 4096 + off + 9                                       # the source starts 8 bytes in front of a seam
+                toks = prelude(P) + [("lit", 0xC3)] + copy_tokens(near, L + R.length_delta(near), False) + [("lit", 0xC4), ("match", far, L + R.length_delta(far)), ("lit", 0xC5)]
+                for d in (4095, 4096):
+                    toks += [("match", d, L + R.length_delta(d)), ("lit", 0xC6), ("lit", 0xC7)]
+                it = item(R.assemble(PRELUDE[0], toks + [("end",)]), name="literal at %d, copies of %d" % (P, L))
+                assert it["want"][1] == R.OK and it["want"][0][P] == 0xC3
+                items.append(it)
+    check(items, "literals at the seam", spread=True)
