@@ -333,6 +333,14 @@ uint64_t alz_debug_scan_streams(alz_ctx* c) {
     return v;
 }
 uint64_t alz_debug_seg_launches(const alz_ctx* c) { return c ? c->seg_enc_launches : 0; }
+/* not in the public header: which kernel B each stream of the LAST encode launch went to -- the first n words of the ENC_SEL scratch, enc_probe_kernel's word per stream
+   (bit 0: the one-position-per-lane kernel, bits 8 and up: hits per thousand sampled positions).  Meaningful behind a call of ONE format whose finder has the probe
+   (maxChain >= 3, 16-bit links, one property set); waits for the device.  Returns the words copied, -1 without that scratch. */
+int alz_debug_enc_probe_words(alz_ctx* c, uint32_t* out, uint32_t n) {
+    if (!c || !out || !c->enc_buf[alz_ctx::ENC_SEL] || c->enc_cap[alz_ctx::ENC_SEL] < (size_t)n * sizeof(uint32_t)) return -1;
+    if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, c->enc_buf[alz_ctx::ENC_SEL], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (int)n;
+}
 /* not in the public header: how often alz_plan_results has repeated a launch without the work queue on this context (expected: never) */
 uint64_t alz_debug_chunk_repeats(const alz_ctx* c) { return c ? c->chunk_repeats : 0; }
 /* not in the public header: output bytes per chunk of the work-queue kernels */
