@@ -145,6 +145,17 @@ BITENC_PROTOTYPES = {
 }
 BITENC_RESTYPES = {"alz_bitenc_bound": C.c_size_t, "alz_bitenc_file_bound": C.c_size_t}
 
+# aPLib written (aPLib.CompressHeaderless / Compress): batches of raw buffers (format, aux0, aux1 and decom_len of a stream are ignored) and "AP32" files;
+# settings is an alz_settings* (NULL: quality 8)
+APENC_PROTOTYPES = {
+    "alz_apenc_bound": [C.c_size_t],                                               # returns size_t (APENC_RESTYPES)
+    "alz_apenc_encode_batch": _BITENC_ENCODE, "alz_apenc_encode_batch_device": _BITENC_ENCODE,
+    "alz_apenc_file_bound": [C.c_size_t],                                          # returns size_t
+    "alz_apenc_file_compress": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "alz_apenc_file_compress_batch": _BITENC_ENCODE,
+}
+APENC_RESTYPES = {"alz_apenc_bound": C.c_size_t, "alz_apenc_file_bound": C.c_size_t}
+
 # the DEFLATE entry points (decode only): batches of raw streams, their sizes without decoding, and the ZLib / GZip classes on a file in host memory
 INFLATE_WINDOW = 0x8000
 _INFLATE_DECODE = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

@@ -83,9 +83,9 @@ def load():
     lib.alz_partition_batch.argtypes = [u32, vp, u32, vp, vp]
     lib.alz_measure_copy_bandwidth.argtypes = [vp, sz, C.c_int, C.POINTER(C.c_double)]
     lib.alz_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    for name, types in list(A.MEASURE_PROTOTYPES.items()) + list(A.RLH_PROTOTYPES.items()) + list(A.RLHUDSON_PROTOTYPES.items()) + list(A.WFILE_PROTOTYPES.items()) + list(A.APLIB_PROTOTYPES.items()) + list(A.BITLZ_PROTOTYPES.items()) + list(A.INFLATE_PROTOTYPES.items()) + list(A.CHECKSUM_PROTOTYPES.items()) + list(A.ZFILE_PROTOTYPES.items()) + list(A.XXH32_PROTOTYPES.items()) + list(A.FRAMED_PROTOTYPES.items()) + list(A.CRC32C_PROTOTYPES.items()) + list(A.FRAMING_COMPRESS_PROTOTYPES.items()) + list(A.DEFLATE_PROTOTYPES.items()) + list(A.BITENC_PROTOTYPES.items()):
+    for name, types in list(A.MEASURE_PROTOTYPES.items()) + list(A.RLH_PROTOTYPES.items()) + list(A.RLHUDSON_PROTOTYPES.items()) + list(A.WFILE_PROTOTYPES.items()) + list(A.APLIB_PROTOTYPES.items()) + list(A.BITLZ_PROTOTYPES.items()) + list(A.INFLATE_PROTOTYPES.items()) + list(A.CHECKSUM_PROTOTYPES.items()) + list(A.ZFILE_PROTOTYPES.items()) + list(A.XXH32_PROTOTYPES.items()) + list(A.FRAMED_PROTOTYPES.items()) + list(A.CRC32C_PROTOTYPES.items()) + list(A.FRAMING_COMPRESS_PROTOTYPES.items()) + list(A.DEFLATE_PROTOTYPES.items()) + list(A.BITENC_PROTOTYPES.items()) + list(A.APENC_PROTOTYPES.items()):
         getattr(lib, name).argtypes = types
-    for name, t in list(A.RLHUDSON_RESTYPES.items()) + list(A.WFILE_RESTYPES.items()) + list(A.CHECKSUM_RESTYPES.items()) + list(A.CRC32C_RESTYPES.items()) + list(A.DEFLATE_RESTYPES.items()) + list(A.BITENC_RESTYPES.items()):
+    for name, t in list(A.RLHUDSON_RESTYPES.items()) + list(A.WFILE_RESTYPES.items()) + list(A.CHECKSUM_RESTYPES.items()) + list(A.CRC32C_RESTYPES.items()) + list(A.DEFLATE_RESTYPES.items()) + list(A.BITENC_RESTYPES.items()) + list(A.APENC_RESTYPES.items()):
         getattr(lib, name).restype = t
     if lib.alz_abi_version() != A.ABI_VERSION:
         raise ImportError("libauroralz.so ABI %d != python mirror %d" % (lib.alz_abi_version(), A.ABI_VERSION))

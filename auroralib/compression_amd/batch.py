@@ -221,6 +221,29 @@ class Context:
         check(self.lib.alz_bitenc_file_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
         return dst, res
 
+    # ---- aPLib written: raw buffers in (src_*), headerless bodies out (dst_*); format, aux0, aux1 and decom_len of a stream are ignored
+    def apenc_encode_batch(self, streams, src, dst_bytes, quality=8, strategy=0, dst=None):
+        """alz_apenc_encode_batch on host buffers -> (dst, results): aPLib.CompressHeaderless, the managed bytes for the same settings.  A body
+        occupies [dst_off, dst_off + dst_len).  An empty stream raises AlzError E_INVALID; at qualities 1..7 a stream longer than the managed
+        chain table (2^18 / 2^19 / 2^20 bytes) raises E_UNSUPPORTED.  A lone large buffer goes through the same batch pipeline as many small ones."""
+        st = A.Settings(quality, 0, strategy, 0)
+        return self._host_decode(self.lib.alz_apenc_encode_batch, (C.byref(st),), streams, src, dst_bytes, dst)
+
+    def apenc_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes, quality=8, strategy=0):
+        """alz_apenc_encode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
+        st = A.Settings(quality, 0, strategy, 0)
+        return self._device(self.lib.alz_apenc_encode_batch_device, (C.byref(st),), streams, d_src, src_bytes, d_dst, dst_bytes)
+
+    def apenc_file_compress_batch(self, files, src, dst_bytes, quality=8, strategy=0, dst=None):
+        """alz_apenc_file_compress_batch on host buffers -> (dst, results): per file what alz_apenc_file_compress writes and returns for it
+        alone ("AP32", the 24-byte header, the body); all bodies are one encode batch."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        dst = _dst_array(dst, dst_bytes)
+        res = (A.FileResult * len(files))()
+        st = A.Settings(quality, 0, strategy, 0)
+        check(self.lib.alz_apenc_file_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
+        return dst, res
+
     # ---- DEFLATE (decode only): raw streams as zlib's inflate reads them; format, decom_len, aux0 and aux1 of a stream are ignored
     def inflate_decode_batch(self, streams, src, dst_bytes, dst=None):
         """alz_inflate_decode_batch on host buffers.  `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""

@@ -18,6 +18,8 @@ hipError_t alz_launch_bitlz_decode(int kind, hipStream_t stream, const void* d_s
 // batch are 0 .. ALZ_FMT_COUNT - 1 the public formats, ALZ_FMT_COUNT FastLZ level 2, then these.  alz_encode_batch* never lets a caller name one;
 // alz_bitenc_encode_batch* translates its alz_bitlz_kind into them.  (Here and not in alz_internal.h: the decoder's committed counters are hashed over that file.)
 enum { ALZ_ENCFMT_CRILAYLA = ALZ_FMT_COUNT + 1, ALZ_ENCFMT_ALLZ = ALZ_FMT_COUNT + 2, ALZ_ENCFMT_COUNT = ALZ_FMT_COUNT + 3 };
+// ... and aPLib's body (Formats/Common/aPLib.cs:183-286; include/auroralz.h: alz_apenc_*), the third one behind the enum.  ALZ_ENCFMT_END: what is sized by the number of slots
+enum { ALZ_ENCFMT_APLIB = ALZ_FMT_COUNT + 3, ALZ_ENCFMT_END = ALZ_FMT_COUNT + 4 };
 // d[i] = s[len - 1 - i] for the streams of d_index: s = d_src + d_orig_off[stream]; d is where d_streams[stream].src_off points (counted from
 // d_src, as every descriptor's), a place inside the scratch d_rev with 64 readable bytes behind each copy  CRILAYLA.cs:204-206,253-257
 hipError_t alz_launch_encode_reverse(hipStream_t stream, const void* d_src, void* d_rev, const alz_stream* d_streams, const uint64_t* d_orig_off,

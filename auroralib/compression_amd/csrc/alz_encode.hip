@@ -41,7 +41,7 @@
 
 #include "alz_device.h"
 #include "alz_internal.h"
-#include "alz_bitlz.h"   // ALZ_ENCFMT_*: the two internal formats of the encoder
+#include "alz_bitlz.h"   // ALZ_ENCFMT_*: the three internal formats of the encoder
 
 namespace {
 
@@ -51,9 +51,9 @@ struct EncGeom {           // per-format LzProperties + finder parameters (SURVE
     u32 min_mask;
     // LZSS
     u32 length_bits, lz_min_length, windows_start, lz_max_distance;
-    // the LzProperties[] form of the finder (RefPack, FastLZ level 2, ALLZ's five): ScoreMatch takes the first set that admits a candidate
-    int nprops, p_max_len[5], p_min_len[5], p_max_dist[5], p_min_dist[5];
-    int variant;           // FastLZ: 1 = level 2 (token format + the two property sets); CRILAYLA, ALLZ: 1 = the exact (lone-lane) emitter
+    // the LzProperties[] form of the finder (RefPack, FastLZ level 2, ALLZ's five, aPLib's seven): ScoreMatch takes the first set that admits a candidate
+    int nprops, p_max_len[7], p_min_len[7], p_max_dist[7], p_min_dist[7];
+    int variant;           // FastLZ: 1 = level 2 (token format + the two property sets); CRILAYLA, ALLZ, aPLib: bit 0 = the exact (lone-lane) emitter
     int link16;            // the 4-byte-hash links are 16-bit DISTANCES (0: none or out of reach): every finder whose maxDistance fits
     int b_cap;             // kernel B stops comparing a candidate here and marks the position (the parse searches it exactly if its cursor ever stands on it)
 };
@@ -520,6 +520,10 @@ typedef u32 mentry;
 #define ALZ_M_LONG 0x7FEu
 #define ALZ_M_CAP 0x7FFu
 __device__ __forceinline__ mentry m_pack(u32 d, u32 l) { return (l << ALZ_M_DBITS) | d; }
+// ... where aPLib's finder can come by (kernel B, the roles walk): its maxDistance is 1 << 21, ONE more than the field holds, and a match's distance is never 0 -- so the
+// distance is kept modulo 1 << 21, and aPLib's emitters read a 0 as 1 << 21 (m_dist21).  Every other geometry has max_dist <= ALZ_M_DMASK (alz_encode_geometry): the same entry.
+__device__ __forceinline__ mentry m_pack21(u32 d, u32 l) { return (l << ALZ_M_DBITS) | (d & ALZ_M_DMASK); }
+__device__ __forceinline__ u32 m_dist21(u32 d) { return d ? d : 1u << ALZ_M_DBITS; }
 __device__ __forceinline__ uint2 m_unpack(mentry e) { const u32 l = e >> ALZ_M_DBITS; return make_uint2(e & ALZ_M_DMASK, l == ALZ_M_CAP ? ALZ_CAPPED : l); }
 
 // The rule of FindNextBestMatch (LzChainMatchFinder.cs:157-212) for a cursor at p whose match has l0 bytes and whose neighbour's (p + 1) has l1: what the
@@ -1247,7 +1251,7 @@ __global__ __launch_bounds__(64) void enc_match_dense_kernel(const u8* __restric
                 }
             }
         }
-        __builtin_nontemporal_store(capped ? 0xFFFFFFFFu : m_pack((u32)best_d, (u32)best_l), m + pos);
+        __builtin_nontemporal_store(capped ? 0xFFFFFFFFu : m_pack21((u32)best_d, (u32)best_l), m + pos);
     }
   }
 }
@@ -1286,7 +1290,7 @@ __global__ __launch_bounds__(256) void enc_match_kernel(const u8* __restrict__ s
     for (int pos = first + (int)threadIdx.x; pos <= last; pos += 256) {
         int bd, bl;
         const bool okm = match_search_b<MINT, L16, PRUNE, true>(data, n, pos, p4, pm, g, g.b_cap, bd, bl);       // (256 threads, positions in thread order: a wavefront's are consecutive)
-        __builtin_nontemporal_store(okm ? m_pack((u32)bd, (u32)bl) : 0xFFFFFFFFu, m + pos);   // (written once, read by the next kernel: past the caches)
+        __builtin_nontemporal_store(okm ? m_pack21((u32)bd, (u32)bl) : 0xFFFFFFFFu, m + pos);   // (written once, read by the next kernel: past the caches)
     }
   }
 }
@@ -1391,7 +1395,7 @@ __global__ __launch_bounds__(256) void enc_match_dyn_kernel(const u8* __restrict
                     }
                 }
             }
-            __builtin_nontemporal_store(okm ? m_pack((u32)best_d, (u32)best_l) : 0xFFFFFFFFu, m + pos);
+            __builtin_nontemporal_store(okm ? m_pack21((u32)best_d, (u32)best_l) : 0xFFFFFFFFu, m + pos);
             pos = -1;
         }
     }
@@ -1812,6 +1816,215 @@ __device__ void allz_emit_lone(const u8* src, int n, Finder& mf, Out& out, u32 a
     fw.flush();
 }
 
+// ---------------------------------------------------------------------------------------------- aPLib written
+// aPLib.CompressHeaderless (Formats/Common/aPLib.cs:183-286), the third bit-stream body: LzChainMatchFinder over seven property sets (alz_encode_geometry), then
+// source[0] raw and a FlagWriter(Endian.Big) stream of literals (0 + byte), one-byte matches (111 + 4 bits), short blocks (110 + byte), repeats
+// (10, gamma 2, gamma L) and normal blocks (10, gamma high, low byte, gamma L - LengthDelta), an end marker (110 + byte 0).  A distance of exactly 1 << 21
+// arrives as 0 (m_pack21).  The branch `lengthDelta < 2 -> continue` (:256-259) is NOT here: every set's minimum length is at least LengthDelta + 2 over the
+// set's distances -- set 1 (D <= 0x80, L 2..3) is a short block up to 0x7F and has delta 0 at 0x80; sets 0, 2..6 admit L >= 3, 4, .. >= 2 + delta -- so no
+// (D, L) the finder returns reaches it (tests/test_apenc_cpu.py enumerates the edges).
+__device__ __forceinline__ u32 ap_length_delta(u32 d) { return (d < 0x80u || d >= 0x7D00u) ? 2u : d >= 0x500u ? 1u : 0u; }   // LengthDelta  :288-295
+
+// WriteGamma(v)  :309-319, bit by bit
+__device__ void ap_gamma_lone(FlagW& fw, u32 v) {
+    const int k = 32 - (int)__builtin_clz(v);
+    for (int i = k - 2; i >= 0; i--) { fw.bit((int)((v >> i) & 1u)); fw.bit(i > 0); }
+}
+
+// CompressHeaderless  :185-285 token by token.  A payload byte enters FlagW where the managed code puts it into Buffer: in front of the bit that follows it (a
+// literal, a short block, the end marker) or in front of FlushIfNecessary (a normal block's low byte).  With out.cap 0 nothing is stored and out.len counts: the sizing walk.
+__device__ void aplib_emit_lone(const u8* src, int n, const mentry* m, const u64* mask, Out& out) {
+    Finder mf; mf.m = m; mf.position = 0; mf.n = n; mf.limit = n - 4; mf.mask = mask;
+    FlagW fw; fw.init(&out, true);
+    int sp = 0; u32 last_offset = 0; bool lwm = false;
+    out.put(src[sp++]);                                                                    // the first literal: raw  :191
+    for (;;) {
+        const Match mt = mf.next();
+        int plain = mt.offset - sp;
+        while (plain != 0) {
+            plain--;
+            const u32 by = src[sp++];
+            lwm = false;
+            int offset = -1;                                                                // a single-byte match  :205-219
+            if (by == 0u) offset = 0;
+            else {
+                const int lookback = sp < 16 ? sp : 16;
+                for (int i = 1; i < lookback; i++) if (src[sp - 1 - i] == by) { offset = i; break; }
+            }
+            if (offset != -1) { fw.bit(1); fw.bit(1); fw.bit(1); for (int i = 3; i >= 0; i--) fw.bit((offset >> i) & 1); continue; }
+            fw.pay(by); fw.bit(0);                                                          // :231-232
+        }
+        if (mt.length == 0) break;
+        const u32 D = m_dist21((u32)mt.distance), L = (u32)mt.length;
+        if (!lwm && last_offset == D) {                                                     // repeat  :239-245
+            fw.bit(1); fw.bit(0); ap_gamma_lone(fw, 2u); ap_gamma_lone(fw, L);
+        } else if (L <= 3u && D <= 127u) {                                                  // short block  :246-252
+            fw.bit(1); fw.bit(1); fw.pay((D << 1) | (L - 2u)); fw.bit(0);
+        } else {                                                                            // normal block  :253-275 (lengthDelta >= 2: above)
+            fw.bit(1); fw.bit(0);
+            ap_gamma_lone(fw, (D >> 8) + 2u + (lwm ? 0u : 1u));
+            fw.pay(D & 0xFFu); fw.flush_if_necessary();
+            ap_gamma_lone(fw, L - ap_length_delta(D));
+        }
+        last_offset = D; lwm = true; sp += mt.length;
+    }
+    fw.bit(1); fw.bit(1); fw.pay(0); fw.bit(0);                                             // the end marker  :282-285
+    fw.flush();
+}
+
+// ---- aPLib by the whole wavefront: one lane per position of a 64-position window (position n is the end marker's).  A position is covered by a match (nothing),
+// a one-byte match (7 bits), a literal (1 bit, 1 payload byte), a match's start (a repeat, a short block or a normal block: up to 2 + 26 + 60 bits, 0 or 1 payload
+// byte) or the end (3 bits, 1 byte); which of the three a match is hangs on lwm and lastOffset, and those are local: lwm <=> the match before ended exactly here,
+// lastOffset = its distance -- read from the lane of the window's start bit below this one, or carried in from the windows before as (end of the last match, its
+// distance).  The 15-byte look-back is positional (source bytes, whatever covers them): two unaligned qwords, nearest equal byte first.
+// Placement: with B the bits written when a payload byte enters Buffer -- counted from the stream's first flag bit --, it lands behind F = ceil((B + 1) / 8)
+// flag bytes (a literal, a short block, the end: one more bit follows, and the flag byte that bit opens or completes goes in front) or F = ceil(B / 8) (a normal
+// block's low byte: FlushIfNecessary lets it out at once when no flag is open), behind source[0] and behind the payload bytes before it: byte 1 + F + j for payload
+// j.  Flag byte k stands at 1 + k + #{ j : F_j <= k } -- ALLZ's run placement with runs of one byte: F is monotone, so a binary search over the window's prefix maxima
+// of F counts them; the payload of earlier windows all has F <= the first NEW flag byte of this one, the byte carried in was placed by the window it began in.
+// The bits go through a bit string in LDS as in enc_bits_cri_kernel (most significant bit first).  A first walk over the same tokens adds up bits and payload:
+// nothing is written unless the body fits.
+// The bit string of a window: a match's start has at most 2 + 26 + 60 = 88 bits and is followed by a position it covers (a match has two bytes or more), a
+// one-byte match has 7, a literal 1, the end 3: at most 32 starts of 88 bits -- 2 816 --, and the 7 carried in: 2 823 bits, 89 dwords and one for a field's low part.
+#define ALZ_GAMMA_WIN_DWORDS 96
+// WriteGamma(v) as `width` = 2 (bitlen(v) - 1) bits, most significant first: below the leading one every value bit, each followed by "more" (1) or "last" (0)  :309-319
+__device__ __forceinline__ u64 ap_gamma(u32 v, u32& width) {
+    const u32 k = 32u - (u32)__builtin_clz(v);
+    width = 2u * (k - 1u);
+    u64 x = v & ((1u << (k - 1u)) - 1u);                                 // (k - 1 <= 30 bits, spread to the even places)
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return (x << 1) | (0x5555555555555554ull & ((1ull << width) - 1ull));
+}
+// hb bits of hv, then tb bits of tv; a payload byte `pay` (has: kb != 0) that enters Buffer kb bits into the token -- with one more bit to follow (a literal 1, a short
+// block or the end 3) or FlushIfNecessary (a normal block: kb = hb), which comes to the same place: behind ceil((B + kb) / 8) flag bytes
+struct ApTok { u32 width, hv, hb, tb, kb, pay; u64 tv; };
+
+__global__ __launch_bounds__(64) void enc_gamma_ap_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base, const alz_stream* __restrict__ streams,
+                                                          const u32* __restrict__ index_list, u32 count, const mentry* __restrict__ match,
+                                                          const u64* __restrict__ pos_off, alz_result* __restrict__ results, const u64* __restrict__ startmask) {
+    __shared__ u32 buf[ALZ_GAMMA_WIN_DWORDS];
+    __shared__ u32 key[64], rsum[64];                                   // per lane: the largest F (from the window's first flag byte on) of the payload so far, payload bytes so far
+    if (blockIdx.x >= count) return;
+    const int lane = (int)threadIdx.x;
+    const u32 sid = index_list[blockIdx.x];
+    const alz_stream st = streams[sid];
+    const u8* src = src_base + st.src_off;
+    u8* dst = dst_base + st.dst_off;
+    const u32 cap = st.dst_cap;
+    const int n = (int)st.src_len, limit = n - 4;
+    const mentry* m = match + pos_off[sid];
+    const u64* mask = startmask + (pos_off[sid] >> 6);
+    const int nwords = limit >= 0 ? (limit >> 6) + 1 : 0;              // (the mask words the roles walk may have written)
+    // the token of this lane's position in the window at P; `cover`, `last_d`: where the last match taken so far ends, and its distance (0: none yet)
+    auto token = [&](int P, u32& cover, u32& last_d) {
+        ApTok t = { 0u, 0u, 0u, 0u, 0u, 0u, 0ull };
+        const int p = P + lane;
+        const u64 mw = (P >> 6) < nwords ? mask[P >> 6] : 0ull;
+        const bool start = (mw >> lane) & 1ull;
+        u32 D = 0, L = 0;
+        if (start) { uint2 r = m_unpack(m[p]); if (r.y == ALZ_M_LONG) r.y = m[p + 1]; D = m_dist21(r.x); L = r.y; }
+        const u32 mend = start ? (u32)p + L : 0u;
+        const u32 incl = scan_max(mend);
+        u32 excl = (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x138, 0xF, 0xF, false);      // wave_shr:1 -> the ends of the matches that start in the lanes below
+        if (excl < cover) excl = cover;
+        // the match before this lane's: the start bit below it in this window, or what the windows before left
+        const u64 below = mw & ((1ull << lane) - 1ull);
+        const int from = below ? 63 - (int)__builtin_clzll(below) : lane;
+        u32 prev_end = (u32)__builtin_amdgcn_ds_bpermute(from << 2, (int)mend), prev_d = (u32)__builtin_amdgcn_ds_bpermute(from << 2, (int)D);
+        if (!below) { prev_end = cover; prev_d = last_d; }
+        if (start) {
+            const bool lwm = prev_end == (u32)p;
+            if (!lwm && prev_d == D) {                                  // repeat: 10, gamma(2) = 00, gamma(L)  :239-245
+                t.hv = 0x8u; t.hb = 4u; t.tv = ap_gamma(L, t.tb);
+            } else if (L <= 3u && D <= 127u) {                          // short block: 11, the byte, 0  :246-252
+                t.hv = 0x6u; t.hb = 3u; t.kb = 3u; t.pay = (D << 1) | (L - 2u);
+            } else {                                                    // normal block: 10, gamma(high), the low byte, gamma(L - LengthDelta)  :253-275
+                u32 gw; const u64 gh = ap_gamma((D >> 8) + 2u + (lwm ? 0u : 1u), gw);   // (high <= 0x2003: 26 bits)
+                t.hv = (0x2u << gw) | (u32)gh; t.hb = 2u + gw; t.kb = t.hb; t.pay = D & 0xFFu;
+                t.tv = ap_gamma(L - ap_length_delta(D), t.tb);
+            }
+        } else if (p == n) {                                            // the end marker: 11, byte 0, 0  :282-285
+            t.hv = 0x6u; t.hb = 3u; t.kb = 3u;
+        } else if (p >= 1 && p < n && (u32)p >= excl) {                 // a plain byte  :198-233 (position 0 went out raw)
+            const u32 by = src[p];
+            int off = -1;
+            if (by == 0u) off = 0;
+            else if (p >= 16) {                                         // the 15 bytes in front: p - 8 .. p - 1 and p - 16 .. p - 9, an exact zero-byte test on their XOR with the byte
+                const u64 rep = 0x0101010101010101ull * by, lo7 = 0x7F7F7F7F7F7F7F7Full;
+                const u64 za = load64(src + p - 8) ^ rep, zb = load64(src + p - 16) ^ rep;
+                const u64 ea = ~(((za & lo7) + lo7) | za | lo7), eb = ~(((zb & lo7) + lo7) | zb | lo7) & ~0xFFull;   // (offset 16 is outside the look-back)
+                if (ea) off = 1 + ((int)__builtin_clzll(ea) >> 3);
+                else if (eb) off = 9 + ((int)__builtin_clzll(eb) >> 3);
+            } else for (int i = 1; i <= p; i++) if (src[p - i] == by) { off = i; break; }     // min(16, srcPtr) at the stream's start  :210
+            if (off >= 0) { t.hv = 0x70u | (u32)off; t.hb = 7u; }       // 111 + 4 bits  :223-226
+            else { t.hb = 1u; t.kb = 1u; t.pay = by; }                  // the byte, then 0  :231-232
+        }
+        t.width = t.hb + t.tb;
+        const u32 last = (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        if (last > cover) cover = last;
+        if (mw) last_d = (u32)__builtin_amdgcn_readlane((int)D, 63 - (int)__builtin_clzll(mw));
+        return t;
+    };
+    // the sizing walk: source[0], the flag bytes, the payload
+    u64 bits = 0; u32 npay = 0, cover = 0, last_d = 0;
+    for (int P = 0; P <= n; P += 64) {
+        const ApTok t = token(P, cover, last_d);
+        bits += (u64)__builtin_amdgcn_readlane((int)scan_add(t.width), 63);
+        npay += (u32)__popcll(__ballot(t.kb != 0u));
+    }
+    const u64 total = 1ull + ((bits + 7ull) >> 3) + (u64)npay;
+    if (total > (u64)cap) {
+        if (lane == 0) { alz_result r; r.dst_len = 0u; r.src_used = st.src_len; r.status = ALZ_ST_OUTPUT_CAPACITY; r.reserved = 0; results[sid] = r; }
+        return;
+    }
+    if (lane == 0) dst[0] = src[0];                                     // :191
+    u64 G = 0; u32 rtot = 0, carry = 0, carry_pos = 0;                  // bits and payload bytes so far; the flag byte the bits end in (its top G % 8) and its place
+    cover = 0; last_d = 0;
+    auto put = [&](u32 at, u32 v, u32 nb) {                             // nb <= 32 bits of v at bit `at` of the window's string, most significant first
+        const u64 x = (u64)v << (64u - (at & 31u) - nb);
+        atomicOr(&buf[at >> 5], (u32)(x >> 32));
+        if ((u32)x) atomicOr(&buf[(at >> 5) + 1u], (u32)x);
+    };
+    auto byte_at = [&](u32 j) { return (buf[j >> 2] >> (24u - 8u * (j & 3u))) & 0xFFu; };
+    auto store = [&](u32 at, u32 b) { if (at < cap) dst[at] = (u8)b; };  // (the body fits: the test costs nothing and no index is trusted)
+    for (int P = 0; P <= n; P += 64) {
+        const ApTok t = token(P, cover, last_d);
+        for (int j = lane; j < ALZ_GAMMA_WIN_DWORDS; j += 64) buf[j] = j == 0 ? carry << 24 : 0u;
+        const u32 phase = (u32)G & 7u, incl = scan_add(t.width), t0 = phase + incl - t.width;
+        const bool has = t.kb != 0u;
+        const u32 rincl = scan_add(has ? 1u : 0u), frel = (t0 + t.kb + 7u) >> 3;       // frel: flag bytes, from the window's first on, in front of this lane's payload
+        key[lane] = scan_max(has ? frel : 0u); rsum[lane] = rincl;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        if (t.hb) put(t0, t.hv, t.hb);
+        if (t.tb > 32u) { put(t0 + t.hb, (u32)(t.tv >> 32), t.tb - 32u); put(t0 + t.hb + t.tb - 32u, (u32)t.tv, 32u); }
+        else if (t.tb) put(t0 + t.hb, (u32)t.tv, t.tb);
+        const u32 byte0 = (u32)(G >> 3);                                                // the flag byte the window's string starts with
+        if (has) store(1u + byte0 + frel + rtot + rincl - 1u, t.pay);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        // flag byte j of the window stands behind the payload with F <= j: that of the lanes whose key is at most j
+        auto place = [&](u32 j) {
+            u32 lo = 0, hi = 64;                                                        // lanes [0, lo) have key <= j
+            while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (key[mid] <= j) lo = mid + 1u; else hi = mid; }
+            return 1u + byte0 + j + rtot + (lo ? rsum[lo - 1u] : 0u);
+        };
+        const u32 end = phase + (u32)__builtin_amdgcn_readlane((int)incl, 63), nfull = end >> 3;
+        for (u32 j = (u32)lane; j < nfull; j += 64u) store((j == 0u && phase) ? carry_pos : place(j), byte_at(j));
+        if (end & 7u) { const u32 cp = (nfull == 0u && phase) ? carry_pos : place(nfull); carry = byte_at(nfull); carry_pos = cp; }
+        else carry = 0u;
+        G += (u64)(end - phase);
+        rtot += (u32)__builtin_amdgcn_readlane((int)rincl, 63);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    }
+    if (lane == 0) {
+        if ((u32)G & 7u) store(carry_pos, carry);                       // Dispose: the open flag byte  FlagWriter.cs:111-127
+        alz_result r; r.dst_len = (u32)total; r.src_used = st.src_len; r.status = ALZ_ST_OK; r.reserved = 0; results[sid] = r;
+    }
+}
+
 template <int FMT>
 __global__ __launch_bounds__(64) void enc_emit_kernel(const u8* __restrict__ src_base, u8* __restrict__ dst_base,
                                                       const alz_stream* __restrict__ streams, const u32* __restrict__ index_list,
@@ -2127,6 +2340,10 @@ __global__ __launch_bounds__(64) void enc_emit_kernel(const u8* __restrict__ src
         if (cri_emit_lone(src, n, mf.m, mf.mask, out.p, out.cap, total)) out.len = total; else out.fail = true;
     } else if constexpr (FMT == ALZ_ENCFMT_ALLZ) {                          // ALLZ.cs:129-174
         allz_emit_lone(src, n, mf, out, st.aux0);
+    } else if constexpr (FMT == ALZ_ENCFMT_APLIB) {                         // aPLib.cs:183-286: sized first, written if it fits
+        Out size = { out.p, 0u, 0u, false };
+        aplib_emit_lone(src, n, mf.m, mf.mask, size);
+        if (size.len > out.cap) out.fail = true; else aplib_emit_lone(src, n, mf.m, mf.mask, out);
     } else if constexpr (FMT == ALZ_FMT_LZ02) {                             // LZ02.cs:117-151
         FlagW fw; fw.init(&out, true);
         for (;;) {
@@ -2372,12 +2589,12 @@ __global__ __launch_bounds__(64) void enc_roles_kernel(const u8* __restrict__ sr
                 // (only what was searched here: an entry that was exact stays -- and the neighbour is searched only behind a match of the lazy threshold or less, never a long one)
                 if (lane == 0) {
                     if (s0) {
-                        if (sr == 1 && l0 >= (int)ALZ_M_LONG) { m[q] = m_pack((u32)d0, ALZ_M_LONG); m[q + 1] = (u32)l0; }
-                        else m[q] = m_pack((u32)d0, l0 < (int)ALZ_M_LONG ? (u32)l0 : ALZ_M_LONG - 1u);
+                        if (sr == 1 && l0 >= (int)ALZ_M_LONG) { m[q] = m_pack21((u32)d0, ALZ_M_LONG); m[q + 1] = (u32)l0; }
+                        else m[q] = m_pack21((u32)d0, l0 < (int)ALZ_M_LONG ? (u32)l0 : ALZ_M_LONG - 1u);
                     }
                     if (s1) {
-                        if (l1 < (int)ALZ_M_LONG) { m[q + 1] = m_pack((u32)d1, (u32)l1); tile[q + 1 - tbase] = m_pack((u32)d1, (u32)l1); }
-                        else if (sr == 2) { m[q + 1] = m_pack((u32)d1, ALZ_M_LONG); m[q + 2] = (u32)l1; }
+                        if (l1 < (int)ALZ_M_LONG) { m[q + 1] = m_pack21((u32)d1, (u32)l1); tile[q + 1 - tbase] = m_pack21((u32)d1, (u32)l1); }
+                        else if (sr == 2) { m[q + 1] = m_pack21((u32)d1, ALZ_M_LONG); m[q + 2] = (u32)l1; }
                     }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
@@ -2992,7 +3209,8 @@ struct EncPath { bool known; EncFamily family; bool scan; EncSegWalk seg; int ta
     X(ALZ_FMT_CNS,        ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
     X(ALZ_FMT_CNX2,       ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
     X(ALZ_ENCFMT_CRILAYLA, ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
-    X(ALZ_ENCFMT_ALLZ,    ENC_SERIAL, false, ENC_SEG_NONE, 0, false)
+    X(ALZ_ENCFMT_ALLZ,    ENC_SERIAL, false, ENC_SEG_NONE, 0, false) \
+    X(ALZ_ENCFMT_APLIB,   ENC_SERIAL, false, ENC_SEG_NONE, 0, false)
 constexpr EncPath enc_path(int fmt) {
     switch (fmt) {
 #define ALZ_ENC_ROW(F, FAMILY, SCAN, SEG, TAIL, LONG) case F: return EncPath{ true, FAMILY, SCAN, SEG, TAIL, LONG };
@@ -3072,6 +3290,12 @@ bool alz_encode_geometry(int fmt, const alz_lz_properties* lz, const alz_setting
         for (int k = 0; k < 5; k++) { g.p_max_dist[k] = tier_dist[k]; g.p_min_len[k] = tier_min[k]; g.p_max_len[k] = 0x40000; g.p_min_dist[k] = 1; }
         break;
     }
+    case ALZ_ENCFMT_APLIB: {                                                                                // aPLib.cs:27-36: seven sets IN THIS ORDER (ScoreMatch takes the first that admits)
+        static const int set_dist[7] = { 0x1000, 0x80, 0x4000, 0x10000, 0x40000, 0x100000, 0x200000 }, set_min[7] = { 3, 2, 4, 5, 6, 7, 8 };
+        wb = 21; g.min_len = 2; g.max_len = 0x7FFFFFFF; g.max_dist = 0x200000; g.nprops = 7; g.variant = variant & 1;   // variant bit 0: the lone-lane emitter
+        for (int k = 0; k < 7; k++) { g.p_max_dist[k] = set_dist[k]; g.p_min_len[k] = set_min[k]; g.p_max_len[k] = k == 1 ? 3 : 0x7FFFFFFF; g.p_min_dist[k] = 1; }
+        break;
+    }
     default: return false;
     }
     if (st->max_window_bits != 0) {                                  // LzChainMatchFinder.cs:70-74 (the host only lets FastLZ through)
@@ -3090,13 +3314,16 @@ bool alz_encode_geometry(int fmt, const alz_lz_properties* lz, const alz_setting
     // the chain table of the reference has 1 << min(17 + floor(sqrt(2q)), windowsBits) slots; the prev() identity needs
     // it to cover maxDistance, which holds for every format geometry of the reference
     const int chain_bits = (17 + isqrt_floor(2 * q)) < wb ? (17 + isqrt_floor(2 * q)) : wb;
-    if (g.max_chain != 1 && (1 << chain_bits) < g.max_dist) return false;
+    // (aPLib, variant bit 1: the caller has seen that no stream of the call is longer than the chain table -- alz_apenc_chain_slots --, so no slot is reused and the
+    // links are still prev(): qualities 1..7, whose table is smaller than the 1 << 21 window)
+    if (g.max_chain != 1 && (1 << chain_bits) < g.max_dist && !(fmt == ALZ_ENCFMT_APLIB && (variant & 2))) return false;
     // (16-bit links: 67 -> 57 GB of HBM traffic per 10 000 x 256 KiB at quality 0, 217 -> 143 at quality 8, times within 1 %; at quality 15 --
     // chains of up to 1 024 links -- they cost kernel B 5 % while the conversion sat right behind the load, and gain 1 % (104.9 -> 103.6 ms)
     // since the dense kernel converts a link at the top of the NEXT trip)
     g.link16 = g.max_dist <= 0xFFFF ? 1 : 0;
     g.b_cap = ALZ_LEN_CAP;
-    if (g.max_dist > (int)ALZ_M_DMASK) return false;                  // a distance has 21 bits in the match array (FastLZ with MaxWindowBits above 20: the caller's own encoder)
+    // a distance has 21 bits in the match array (FastLZ with MaxWindowBits above 20: the caller's own encoder); aPLib's 1 << 21 is kept as 0 (m_pack21)
+    if (g.max_dist > (int)ALZ_M_DMASK && !(fmt == ALZ_ENCFMT_APLIB && g.max_dist == (int)ALZ_M_DMASK + 1)) return false;
     memcpy(out_geom, &g, sizeof(g));
     if (window_bits) *window_bits = wb;
     return true;
@@ -3884,6 +4111,8 @@ static void launch_emit(const EncLaunch& L) {
     if (L.mask) hipLaunchKernelGGL((enc_roles_kernel<false>), grid, wave, 0, L.s, L.src, L.streams, L.index, L.count, L.match, L.pos_off, L.prev4, L.prevm, L.mask, L.g, L.tail, nullptr, 0u);
     if constexpr (FMT == ALZ_ENCFMT_ALLZ)                                  // its bits by the whole wavefront (above); g.variant 1: the context asks for the exact kernels
         if (!L.g.variant) { hipLaunchKernelGGL(enc_bits_allz_kernel, grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.results, L.mask); return; }
+    if constexpr (FMT == ALZ_ENCFMT_APLIB)
+        if (!L.g.variant) { hipLaunchKernelGGL(enc_gamma_ap_kernel, grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.results, L.mask); return; }
     if constexpr (FMT == ALZ_ENCFMT_CRILAYLA)
         if (!L.g.variant) { hipLaunchKernelGGL(enc_bits_cri_kernel, grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.results, L.mask); return; }
     hipLaunchKernelGGL((enc_emit_kernel<FMT>), grid, wave, 0, L.s, L.src, L.dst, L.streams, L.index, L.count, L.match, L.pos_off, L.side, L.results, L.aux, L.g, 1u, L.mask);

@@ -219,7 +219,7 @@ static int validate_streams(const char* what, uint32_t kinds, uint32_t n, const 
 
 // The streams of a batch grouped per kind: `index` lists the stream numbers kind after kind, a kind's streams in input order; off[k] / cnt[k] is
 // where kind k's list starts and how many it holds.  With a cost(i) the costliest streams of a kind come first (equal costs in input order).
-static const uint32_t kMaxKinds = ALZ_ENCFMT_COUNT;   // (the encoder's slots: the public formats, FastLZ level 2, the two internal ones of alz_bitlz.h)
+static const uint32_t kMaxKinds = ALZ_ENCFMT_END;   // (the encoder's slots: the public formats, FastLZ level 2, the two internal ones of alz_bitlz.h)
 static_assert(ALZ_RLH_COUNT <= kMaxKinds && ALZ_BITLZ_COUNT <= kMaxKinds, "the per-kind counters of group_streams");
 template <class KindOf>
 static void group_streams(uint32_t n, uint32_t kinds, KindOf kind_of, std::vector<uint32_t>& index, uint32_t* off, uint32_t* cnt) {
@@ -1462,7 +1462,7 @@ static inline bool fastlz_level2(const alz_settings& st, uint32_t src_len) { ret
 // encode_core runs the stages below in turn; what one stage works out for the next travels in these three structs.
 namespace {
 // One format slot of a batch: ALZ_FMT_COUNT slots for the public formats, one for FastLZ level 2, which has a geometry and a launch of its own, and behind it
-// the internal formats of alz_bitlz.h (CRILAYLA, ALLZ), which only alz_bitenc_encode_batch* can name: ALZ_ENCFMT_COUNT in all
+// the internal formats of alz_bitlz.h (CRILAYLA, ALLZ), which only alz_bitenc_encode_batch* can name: ALZ_ENCFMT_END in all
 struct enc_slot {
     unsigned char* geom = nullptr;                 // alz_encode_geometry's bytes (all zero while the batch has no stream of the slot)
     uint32_t seg_len = 0, seg_kmax = 0;            // the segmented parse + emit (alz_encode_seg.h) takes the slot's launch: segment length and segments per buffer
@@ -1470,10 +1470,10 @@ struct enc_slot {
 };
 struct enc_batch {
     alz_settings st; alz_lz_properties lz;
-    uint32_t cnt[ALZ_ENCFMT_COUNT], off[ALZ_ENCFMT_COUNT];   // per format (slot ALZ_FMT_COUNT stays empty here); a FastLZ list holds the level-1 streams first, then the n_fastlz2 level-2 ones
+    uint32_t cnt[ALZ_ENCFMT_END], off[ALZ_ENCFMT_END];   // per format (slot ALZ_FMT_COUNT stays empty here); a FastLZ list holds the level-1 streams first, then the n_fastlz2 level-2 ones
     std::vector<uint32_t> index; std::vector<uint64_t> pos_off;   // pos_off: where a stream's positions start in the per-position scratch arrays, `total` positions in all
     uint64_t total = 0; uint32_t max_len = 0, n_fastlz2 = 0;
-    std::vector<unsigned char> geom_bytes; enc_slot slot[ALZ_ENCFMT_COUNT]; size_t seg_bytes = 0;
+    std::vector<unsigned char> geom_bytes; enc_slot slot[ALZ_ENCFMT_END]; size_t seg_bytes = 0;
     bool any(bool enc_slot::*need) const { for (const enc_slot& s : slot) if (s.*need) return true; return false; }
 };
 // The device side of one call, shared by its two paths: the buffers `upload` hands over (once), and the streams relocated out of a caller's tail
@@ -1485,7 +1485,7 @@ struct enc_io {
 };
 }
 // Stage 1: the settings, then the streams
-// (`kinds`: ALZ_FMT_COUNT for the public entry points -- an internal format is an unknown one there --, ALZ_ENCFMT_COUNT for alz_bitenc_encode_batch*' translated table)
+// (`kinds`: ALZ_FMT_COUNT for the public entry points -- an internal format is an unknown one there --, ALZ_ENCFMT_END for alz_bitenc_encode_batch*' translated table)
 static int enc_validate(const alz_settings* settings, uint32_t kinds, uint32_t n, size_t src_bytes, const alz_stream* streams, size_t dst_bytes, alz_settings* out) {
     alz_settings st; if (settings) st = *settings; else { st.quality = 8; st.max_window_bits = 0; st.strategy = 0; st.min_distance = 0; }
     if (st.quality < 0 || st.quality > 15) return fail(ALZ_E_INVALID, "quality %d outside 0..15 (CompressionSettings.cs:38-50)", st.quality);
@@ -1498,7 +1498,7 @@ static int enc_validate(const alz_settings* settings, uint32_t kinds, uint32_t n
 // Stage 2: the streams grouped per format, their places in the per-position arrays, and the geometry of every format slot present
 static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams, enc_batch* b) {
     const alz_settings& st = b->st;
-    group_streams(n, ALZ_ENCFMT_COUNT, [&](uint32_t i) { return streams[i].format; }, b->index, b->off, b->cnt);
+    group_streams(n, ALZ_ENCFMT_END, [&](uint32_t i) { return streams[i].format; }, b->index, b->off, b->cnt);
     const uint32_t* cnt = b->cnt;
     b->pos_off.resize(n);
     for (uint32_t i = 0; i < n; i++) {
@@ -1511,8 +1511,8 @@ static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams,
                               [&](uint32_t i) { return !fastlz_level2(st, streams[i].src_len); });
     const uint32_t n_fastlz2 = b->n_fastlz2, max_len = b->max_len;
     if (cnt[ALZ_FMT_LZSS] && (!lzss_on_gpu(b->lz) || b->lz.max_distance != (1u << b->lz.window_bits))) return fail(ALZ_E_UNSUPPORTED, "LZSS geometry outside the GPU path");
-    b->geom_bytes.resize(ALZ_ENCFMT_COUNT * alz_encode_geom_size());   // (zeros) slot ALZ_FMT_COUNT: FastLZ level 2
-    for (int f = 0; f < ALZ_ENCFMT_COUNT; f++) {
+    b->geom_bytes.resize(ALZ_ENCFMT_END * alz_encode_geom_size());   // (zeros) slot ALZ_FMT_COUNT: FastLZ level 2
+    for (int f = 0; f < ALZ_ENCFMT_END; f++) {
         enc_slot& s = b->slot[f];
         void* g = s.geom = b->geom_bytes.data() + f * alz_encode_geom_size();
         const bool lvl2 = f == ALZ_FMT_COUNT;
@@ -1521,6 +1521,18 @@ static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams,
         // maxDistance and GetNext is no longer prev() (LzChainMatchFinder.cs:94-96; alz_encode_geometry's check): what the kernels compute is not what it finds
         if (f == ALZ_ENCFMT_ALLZ && st.quality == 1)
             return fail(ALZ_E_UNSUPPORTED, "ALLZ at quality 1: the managed chain table (2^18 slots) is smaller than the 2^19 window, its links are not prev(): not reproduced on the GPU (every other quality 0..15 is)");
+        // aPLib at qualities 1..7: the same table -- 1 << min(17 + floor(sqrt(2 q)), 21) slots -- under a window of 1 << 21.  While no stream of the call is longer
+        // than the table no slot is ever reused and the links ARE prev(): the rule is applied per call (variant bit 1 tells alz_encode_geometry that it was)
+        int ap_chain_ok = 0;
+        if (f == ALZ_ENCFMT_APLIB && st.quality >= 1 && st.quality <= 7) {
+            int r = 0; while ((r + 1) * (r + 1) <= 2 * st.quality) r++;
+            const uint32_t slots = 1u << (17 + r);
+            for (uint32_t i = 0; i < n; i++)
+                if (streams[i].format == ALZ_ENCFMT_APLIB && streams[i].src_len > slots)
+                    return fail(ALZ_E_UNSUPPORTED, "aPLib at quality %d: stream %u has %u bytes, more than the managed chain table's %u slots (the window is 2^21): its links are not prev() "
+                                "beyond that, not reproduced on the GPU (qualities 0 and 8..15 take any length)", st.quality, i, streams[i].src_len, slots);
+            ap_chain_ok = 2;
+        }
         alz_settings sf = st;
         if (st.max_window_bits != 0 && f != ALZ_FMT_FASTLZ && !lvl2) {
             // CompressionSettings.MaxWindowBits can only WIDEN the finder (windowsBits = max(.., maxWindowBits), maxDistance = max(.., 1 <<
@@ -1534,7 +1546,7 @@ static int enc_geometry(const alz_ctx* c, uint32_t n, const alz_stream* streams,
                 return fail(ALZ_E_UNSUPPORTED, "format %d: CompressionSettings.MaxWindowBits %d is beyond the format's window (%d bits, distances up to %d): "
                             "the managed finder would return distances the format cannot store", f, st.max_window_bits, wb0, alz_encode_geom_max_dist(g));
         }
-        if (!alz_encode_geometry(lvl2 ? ALZ_FMT_FASTLZ : f, &b->lz, &sf, g, nullptr, (lvl2 || (f > ALZ_FMT_COUNT && c->exact)) ? 1 : 0))   // (CRILAYLA, ALLZ: 1 = their lone-lane emitters)
+        if (!alz_encode_geometry(lvl2 ? ALZ_FMT_FASTLZ : f, &b->lz, &sf, g, nullptr, ((lvl2 || (f > ALZ_FMT_COUNT && c->exact)) ? 1 : 0) | ap_chain_ok))   // (CRILAYLA, ALLZ, aPLib: 1 = their lone-lane emitters)
             return fail(ALZ_E_UNSUPPORTED, "format %d: geometry not supported by the GPU encoder", lvl2 ? ALZ_FMT_FASTLZ : f);
         s.min_table = alz_encode_geom_min_table(g);
         s.narrows = alz_encode_geom_narrows(g);
@@ -1710,7 +1722,7 @@ static int enc_batch_path(alz_ctx* c, const enc_batch& b, enc_io& io, uint32_t n
             return e;
         },
         [&] {   // table resets + the encode kernels
-            for (int f = 0; f < ALZ_ENCFMT_COUNT; f++) {
+            for (int f = 0; f < ALZ_ENCFMT_END; f++) {
                 const bool lvl2 = f == ALZ_FMT_COUNT;
                 const int fmt = lvl2 ? ALZ_FMT_FASTLZ : f;
                 const uint32_t first = b.off[fmt] + (lvl2 ? cnt[fmt] - b.n_fastlz2 : 0u);
@@ -1807,12 +1819,12 @@ static int bitenc_batch(alz_ctx* c, bool device, const alz_settings* settings, u
     }
     if (device)
         return encode_core(c, nullptr, settings, n, src_bytes, table.data(), dst_bytes, results, nullptr,
-                           [&](const void*& ds, void*& dd) { ds = src_base; dd = dst_base; return (int)ALZ_OK; }, false, ALZ_ENCFMT_COUNT);
+                           [&](const void*& ds, void*& dd) { ds = src_base; dd = dst_base; return (int)ALZ_OK; }, false, ALZ_ENCFMT_END);
     const int rc = encode_core(c, nullptr, settings, n, src_bytes, table.data(), dst_bytes, results, nullptr, [&](const void*& ds, void*& dd) {
         const int r = stage_source(c, (const uint8_t*)src_base, src_bytes, true, dst_bytes);
         ds = c->d_src; dd = c->d_dst;
         return r;
-    }, true, ALZ_ENCFMT_COUNT);
+    }, true, ALZ_ENCFMT_END);
     return rc ? rc : download_outputs(c, n, streams, results, (uint8_t*)dst_base, true);
 }
 int alz_bitenc_encode_batch(alz_ctx* c, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
@@ -1822,6 +1834,53 @@ int alz_bitenc_encode_batch(alz_ctx* c, const alz_settings* settings, uint32_t n
 int alz_bitenc_encode_batch_device(alz_ctx* c, const alz_settings* settings, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
                                    uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
     return bitenc_batch(c, true, settings, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
+}
+
+// ---------------------------------------------------------------- aPLib's body written (alz_encode.hip): aPLib.CompressHeaderless  Formats/Common/aPLib.cs:183-286
+// Every stream is an aPLib body to be: format, aux0, aux1 and decom_len are ignored, the table the encoder sees names the third internal format.  A lone large
+// buffer goes through the batch pipeline like any other (its row in ALZ_ENC_PATHS has no whole-GPU path and no segments).
+size_t alz_apenc_bound(size_t src_len) {
+    // Literals only is the worst case: source[0], then a bit and a byte per further byte, the end marker's three bits and its byte -- src_len + 1 bytes and
+    // src_len + 2 bits.  No other token costs more than 9 bits per byte it covers: a one-byte match 7; a short block 11 for two; a repeat 4 + 2 (bitlen(L) - 1) for
+    // L >= 2; a normal block 2 + gamma(high) + 8 + gamma(L - delta) against the minimum length of the set its distance falls in: 14 bits for two bytes at 0x80,
+    // at most 20 for three up to 0xFFF, 24 for four up to 0x3FFF, 28 for five, 34 for six, 38 for seven, 40 for eight at the far end; a longer match adds two bits
+    // each time L - delta doubles.
+    return src_len ? src_len + 1 + (src_len + 2 + 7) / 8 : 0;
+}
+
+static int apenc_batch(alz_ctx* c, bool device, const alz_settings* settings, uint32_t n, const void* src_base, size_t src_bytes, const alz_stream* streams,
+                       void* dst_base, size_t dst_bytes, alz_result* results) {
+    const char* what = device ? "alz_apenc_encode_batch_device" : "alz_apenc_encode_batch";
+    if (!c || (n && (!streams || !results || !dst_base || (device && !src_base)))) return fail(ALZ_E_INVALID, "%s: bad argument", what);
+    if (n == 0) return ALZ_OK;
+    if (settings && (settings->quality < 0 || settings->quality > 15)) return fail(ALZ_E_INVALID, "%s: quality %d outside 0..15 (CompressionSettings.cs:38-50)", what, settings->quality);
+    // (the finder's settings: what enc_validate lets through, less the two that would make the managed finder return what the format cannot store)
+    if (settings && settings->max_window_bits != 0) return fail(ALZ_E_UNSUPPORTED, "%s: max_window_bits %d: aPLib is written at its own window only", what, settings->max_window_bits);
+    if (settings && settings->min_distance != 0) return fail(ALZ_E_UNSUPPORTED, "%s: min_distance %d: aPLib is written at its own minimum distance only", what, settings->min_distance);
+    std::vector<alz_stream> table(streams, streams + n);
+    for (uint32_t i = 0; i < n; i++) {
+        alz_stream& s = table[i];
+        if (s.src_len == 0) return fail(ALZ_E_INVALID, "%s: stream %u: an empty source (the managed code throws on source[0]  aPLib.cs:191)", what, i);
+        if (s.src_len > 0x40000000u) return fail(ALZ_E_UNSUPPORTED, "%s: stream %u: sources above 0x40000000 bytes are not supported", what, i);
+        s.format = (uint32_t)ALZ_ENCFMT_APLIB; s.aux0 = s.aux1 = 0; s.decom_len = 0;
+    }
+    if (device)
+        return encode_core(c, nullptr, settings, n, src_bytes, table.data(), dst_bytes, results, nullptr,
+                           [&](const void*& ds, void*& dd) { ds = src_base; dd = dst_base; return (int)ALZ_OK; }, false, ALZ_ENCFMT_END);
+    const int rc = encode_core(c, nullptr, settings, n, src_bytes, table.data(), dst_bytes, results, nullptr, [&](const void*& ds, void*& dd) {
+        const int r = stage_source(c, (const uint8_t*)src_base, src_bytes, true, dst_bytes);
+        ds = c->d_src; dd = c->d_dst;
+        return r;
+    }, true, ALZ_ENCFMT_END);
+    return rc ? rc : download_outputs(c, n, streams, results, (uint8_t*)dst_base, true);
+}
+int alz_apenc_encode_batch(alz_ctx* c, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
+                           uint8_t* dst_base, size_t dst_bytes, alz_result* results) {
+    return apenc_batch(c, false, settings, n, src_base, src_bytes, streams, dst_base, dst_bytes, results);
+}
+int alz_apenc_encode_batch_device(alz_ctx* c, const alz_settings* settings, uint32_t n, const uint8_t* d_src_base, size_t src_bytes, const alz_stream* streams,
+                                  uint8_t* d_dst_base, size_t dst_bytes, alz_result* results) {
+    return apenc_batch(c, true, settings, n, d_src_base, src_bytes, streams, d_dst_base, dst_bytes, results);
 }
 
 // ---------------------------------------------------------------- multi-GPU: one batch over several contexts

@@ -16,7 +16,7 @@ PY
 )"
 FLAGS="-O3 -fPIC --offload-arch=gfx950 -std=c++17 -I$ROOT/include -I$HERE -Wall -Wno-unused-function -Wno-inline-asm"
 mkdir -p "$HERE/_obj"
-for f in alz_kernels.hip alz_encode.hip alz_big.hip alz_measure.hip alz_rlh.hip alz_aplib.hip alz_bitlz.hip alz_inflate.hip alz_checksum.hip alz_xxh32.hip alz_host.cpp alz_aplib_file.cpp alz_bitlz_file.cpp alz_bitenc_file.cpp alz_inflate_file.cpp alz_zfile.cpp alz_wfile.cpp alz_deflate_file.cpp alz_framed_batch.cpp alz_framing_compress.cpp alz_container.cpp alz_container_measure.cpp; do
+for f in alz_kernels.hip alz_encode.hip alz_big.hip alz_measure.hip alz_rlh.hip alz_aplib.hip alz_bitlz.hip alz_inflate.hip alz_checksum.hip alz_xxh32.hip alz_host.cpp alz_aplib_file.cpp alz_bitlz_file.cpp alz_bitenc_file.cpp alz_apenc_file.cpp alz_inflate_file.cpp alz_zfile.cpp alz_wfile.cpp alz_deflate_file.cpp alz_framed_batch.cpp alz_framing_compress.cpp alz_container.cpp alz_container_measure.cpp; do
   [ -f "$HERE/$f" ] || continue
   o="$HERE/_obj/${f%.*}.o"
   if [ ! -f "$o" ] || [ "$HERE/$f" -nt "$o" ] || [ -n "$(find "$HERE" "$ROOT/include" -maxdepth 1 -name '*.h' -newer "$o" 2>/dev/null)" ]; then

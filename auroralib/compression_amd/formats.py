@@ -602,13 +602,53 @@ __all__ = [c.__name__ for c in ALL_FORMATS] + ["CompressionSettings", "Decompres
 
 
 APLIB_NO_ENCODER = ("aPLib has no encoder here: CompressHeaderless runs the tiered LzChainMatchFinder with a 2 MiB window and unbounded lengths, the bar is "
-                    "bit-identity with the managed bytes checked against the CPU oracle, and the oracle has no aPLib (include/auroralz.h)")
+                    "bit-identity with the managed bytes checked against the CPU oracle, and the oracle has no aPLib (include/auroralz.h).  "
+                    "Encode(data, settings) writes the file on the GPU: its bit-identity is held against a Python restatement of the finder that is "
+                    "pinned to the oracle through other formats")
 
 
 class APLib:
-    """src/AuroraLib.Compression/Formats/Common/aPLib.cs -- "AP32" + 24-byte header + body, or a headerless body (alz_aplib_*); decode only.
-    No alz_container value backs it, so it stays outside ALL_FORMATS."""
+    """src/AuroraLib.Compression/Formats/Common/aPLib.cs -- "AP32" + 24-byte header + body, or a headerless body (alz_aplib_*) and, for writing,
+    alz_apenc_file_* (Encode / EncodeMany; Compress still refuses).  No alz_container value backs it, so it stays outside ALL_FORMATS."""
     provides_size = True
+
+    def Encode(self, data, settings=None):
+        """The file Compress of the reference writes for these settings (alz_apenc_file_compress): the finder and the bit emitter on the GPU.
+        Refused: an empty input (E_INVALID), MaxWindowBits other than 0, and at qualities 1..7 an input longer than the managed chain table
+        (2^18 bytes at quality 1, 2^19 at 2..4, 2^20 at 5..7: E_UNSUPPORTED)."""
+        data = bytes(data)
+        settings = settings or CompressionSettings.Balanced
+        lib = load()
+        cap = lib.alz_apenc_file_bound(len(data))
+        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
+        dl = C.c_size_t()
+        st = A.Settings(settings.Quality, settings.MaxWindowBits, settings.Strategy, 0)
+        check(lib.alz_apenc_file_compress(_context().h, C.byref(st), data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
+        return dst_arr[:dl.value].tobytes()
+
+    def EncodeMany(self, datas, settings=None):
+        """Encode for a whole set of inputs in ONE alz_apenc_file_compress_batch (one encode batch).  Returns a list with, per input, the file's
+        bytes -- or the exception instance Encode would have raised for it."""
+        datas = [bytes(d) for d in datas]
+        settings = settings or CompressionSettings.Balanced
+        if settings.MaxWindowBits:
+            raise AlzError(A.E_UNSUPPORTED, "MaxWindowBits %d: aPLib is written at its own window only" % settings.MaxWindowBits)
+        lib = load()
+        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
+        table, so, do = (A.Stream * len(datas))(), 0, 0
+        for i, d in enumerate(datas):
+            cap = max(lib.alz_apenc_file_bound(len(d)), 1)
+            table[i] = A.Stream(so, do, len(d), cap, 0, 0, 0, 0)
+            so += len(d)
+            do += (cap + 15) & ~15
+        dst, res = _context().apenc_file_compress_batch(table, src, do, settings.Quality, settings.Strategy)
+        out = []
+        for i, r in enumerate(res):
+            if r.rc:
+                out.append(AlzError(r.rc, "alz_apenc_file_compress_batch: file %d" % i))
+            else:
+                out.append(dst[table[i].dst_off:table[i].dst_off + r.dst_len].tobytes())
+        return out
 
     def IsMatch(self, data):
         data = bytes(data)

@@ -405,9 +405,10 @@ size_t alz_rlhudson_encode_bound(size_t src_len);   /* 2 * src_len: no token has
  * alz_aplib_measure_batch*: results[i] is what alz_aplib_decode_batch would return for streams[i] -- status, dst_len, and src_used wherever
  *   it is defined (every status but OUTPUT_CAPACITY); dst_off is ignored, dst_cap only bounds the count (0xFFFFFF00 for "the size"),
  *   nothing is written on the device but the results.
- * THERE IS NO ENCODER.  aPLib.CompressHeaderless runs the tiered LzChainMatchFinder over seven LzProperties with a 2 MiB window and
- *   unbounded lengths; the project's bar is bit-identity with the managed bytes, checked against the CPU oracle, and the oracle has no
- *   aPLib.  alz_brute_force and alz_container_scan keep their 19 decoders / alz_container values and do not try aPLib. */
+ * THERE IS NO ENCODER in this family: the writer is alz_apenc_* below.  aPLib.CompressHeaderless runs the tiered LzChainMatchFinder over
+ *   seven LzProperties with a 2 MiB window and unbounded lengths; the CPU oracle has no aPLib, so bit-identity with the managed bytes is held
+ *   against a Python restatement.  alz_brute_force and alz_container_scan keep their 19 decoders / alz_container values and do not try aPLib
+ *   (INTEGRATION.md). */
 int alz_aplib_decode_batch(alz_ctx* ctx, uint32_t n, const uint8_t* src_base, size_t src_bytes, const alz_stream* streams,
                            uint8_t* dst_base, size_t dst_bytes, alz_result* results);
 /* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
@@ -535,8 +536,7 @@ int alz_allz_decompress(alz_ctx* ctx, const uint8_t* src, size_t src_len, uint8_
  *   alz_bitenc_file_compress_batch: files[i].format the kind, files[i].aux0 ALLZ's start bits; all bodies of the call are ONE
  *     alz_bitenc_encode_batch.  results[i] is { ALZ_OK, ALZ_ST_OK, dst_len, src_len } and the bytes of the single-file call on file i alone,
  *     or { that call's code, ALZ_ST_OK, 0, 0 }: one file's failure is that file's rc, nothing outside a file's slot is written.
- * NOT BUILT: aPLib (distances of exactly 2^21, one more than a match entry holds;
- *   lwm / lastOffset state in its emitter), device-resident file forms, shim classes. */
+ * NOT BUILT: device-resident file forms, shim classes.  (aPLib, the third bit-stream body, is written by alz_apenc_* below.) */
 size_t alz_bitenc_bound(uint32_t kind, size_t src_len);
 int alz_bitenc_encode_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
                             const alz_stream* streams, uint8_t* dst_base, size_t dst_bytes, alz_result* results);
@@ -549,6 +549,53 @@ int alz_bitenc_file_compress(alz_ctx* ctx, uint32_t kind, const alz_settings* se
                              uint8_t* dst, size_t dst_cap, size_t* dst_len);
 int alz_bitenc_file_compress_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
                                    const alz_stream* files, uint8_t* dst_base, size_t dst_bytes, struct alz_file_result* results);
+
+/* ---------------------------------------- aPLib written: aPLib.CompressHeaderless and Compress (Formats/Common/aPLib.cs:183-286, :87-103)
+ * The body alz_aplib_* reads, written with the managed code's bytes for the same CompressionSettings.  Every stream of a call is one body:
+ * format, aux0, aux1 and decom_len of a stream are IGNORED.  src_* is the raw input, dst_* where the body goes; alz_result is
+ * { OK, dst_len, src_used = src_len }; a body that does not fit dst_cap is ALZ_ST_OUTPUT_CAPACITY with dst_len 0 -- the body is sized before
+ * it is written -- and nothing outside [dst_off, dst_off + dst_cap) is ever written.  alz_apenc_bound(n) = n + 1 + ceil((n + 2) / 8) for
+ * n >= 1 (0 for 0) is the worst case, literals only, and is tight: no other token costs more than nine bits per byte it covers.
+ * The finder: seven LzProperties in the class's order -- (0x1000, max, 3), (0x80, 3, 2), (0x4000, max, 4), (0x10000, max, 5), (0x40000, max, 6),
+ *   (0x100000, max, 7), (0x200000, max, 8): ScoreMatch takes the first that admits a candidate --, minimum length 2, a 2 MiB window; a match at
+ *   distance exactly 0x200000 is found and written.
+ * The body: source[0] raw, then FlagWriter(Endian.Big) -- 8-bit flag bytes, most significant bit first, payload bytes behind the flag byte
+ *   that was open when they were handed over.  A byte outside a match is `111` + 4 bits (the byte is 0: offset 0; it equals one of the
+ *   min(16, position + 1) - 1 bytes in front of it: the nearest such offset 1..15) or `0` + the byte.  A match is a repeat (`10`, gamma 2,
+ *   gamma L: no match ended right here and the distance is the last one), a short block (`11` + byte D << 1 | L - 2: L <= 3, D <= 127) or a
+ *   normal block (`10`, gamma (D >> 8) + 2, + 1 unless a match ended right here, byte D & 0xFF, gamma L - LengthDelta(D)).  The end: `11`, byte 0, `0`.
+ * settings: NULL = quality 8.  quality outside 0..15: ALZ_E_INVALID.  max_window_bits other than 0, and min_distance other than 0:
+ *   ALZ_E_UNSUPPORTED.  strategy 0 and 1 (noSelfOverlap) are both supported.  QUALITIES 1..7 NEED SHORT STREAMS: the managed chain table has
+ *   1 << min(17 + floor(sqrt(2 q)), 21) slots -- 2^18 at quality 1, 2^19 at 2..4, 2^20 at 5..7 -- for a 2^21 window, and once a slot is reused its
+ *   links are not what the kernels compute (LzChainMatchFinder.cs:94-96).  A call at one of these qualities in which any stream is longer than
+ *   that many bytes is ALZ_E_UNSUPPORTED, decided before anything is uploaded (alz_last_error says which stream); qualities 0 and 8..15 have
+ *   no such condition.
+ * A stream with src_len 0 makes the call ALZ_E_INVALID, before anything is uploaded: the managed code throws on source[0].  src_len above
+ *   0x40000000: ALZ_E_UNSUPPORTED.  n == 0: ALZ_OK.
+ * One wavefront writes one stream's bits, a lane per position, placed by prefix sums; alz_ctx_set_exact_kernels selects the form in which one
+ *   lane writes them token by token: the same bytes.  A lone large buffer goes through the same batch pipeline as many small ones (no
+ *   whole-GPU path, no segmented walk).  The device form needs no slack behind its source.  alz_last_kernel_ms reports the device time of the
+ *   call's launches.
+ * The file layer, host memory (Compress, :87-103): "AP32", then u32 LE 24, the body's size, 0, src_len, 0 (both CRC fields are written as 0),
+ *   then the body.  alz_apenc_file_bound(n) = 24 + alz_apenc_bound(n) suffices.
+ *   alz_apenc_file_compress: a dst_cap that is too small is ALZ_E_NOMEM (*dst_len 0); an empty source is ALZ_E_INVALID.
+ *   alz_apenc_file_compress_batch: all bodies of the call are ONE alz_apenc_encode_batch.  results[i] is { ALZ_OK, ALZ_ST_OK, dst_len, src_len }
+ *     and the bytes of the single-file call on file i alone, or { that call's code, ALZ_ST_OK, 0, 0 }: one file's failure (an empty file, a
+ *     slot too small) is that file's rc, nothing outside a file's slot is written.  A condition on the whole call (the quality, the chain
+ *     table's size at qualities 1..7) is the call's return value.
+ * NOT BUILT: a whole-GPU or segmented path for one large buffer, device-resident file forms, a shim class, rows in alz_brute_force /
+ *   alz_container_scan. */
+size_t alz_apenc_bound(size_t src_len);
+int alz_apenc_encode_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                           const alz_stream* streams, uint8_t* dst_base, size_t dst_bytes, alz_result* results);
+/* d_src_base / d_dst_base are DEVICE pointers; results come back to the host */
+int alz_apenc_encode_batch_device(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* d_src_base, size_t src_bytes,
+                                  const alz_stream* streams, uint8_t* d_dst_base, size_t dst_bytes, alz_result* results);
+size_t alz_apenc_file_bound(size_t src_len);
+int alz_apenc_file_compress(alz_ctx* ctx, const alz_settings* settings, const uint8_t* src, size_t src_len,
+                            uint8_t* dst, size_t dst_cap, size_t* dst_len);
+int alz_apenc_file_compress_batch(alz_ctx* ctx, const alz_settings* settings, uint32_t n, const uint8_t* src_base, size_t src_bytes,
+                                  const alz_stream* files, uint8_t* dst_base, size_t dst_bytes, struct alz_file_result* results);
 
 /* ---------------------------------------- DEFLATE: raw streams, their sizes, ZLib and GZip files (decode only)
  * The reference hands the bodies of its ZLib and GZip classes (src/AuroraLib.Compression/Formats/Common/ZLib.cs:30-34, GZip.cs:29-34) and

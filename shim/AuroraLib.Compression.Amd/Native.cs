@@ -171,6 +171,20 @@ namespace AuroraLib.Compression.Amd
         [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_bitenc_file_compress_batch(IntPtr ctx, AlzSettings* settings, uint n,
             byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
 
+        // aPLib written on the GPU (aPLib.CompressHeaderless, the managed bytes for the same settings): raw buffers in batches (format, decomLen, aux0,
+        // aux1 of a stream are ignored; the body occupies [dstOff, dstOff + dstLen)) and "AP32" files, one or a batch.  An empty source is
+        // ALZ_E_INVALID; at qualities 1..7 a source longer than the managed chain table is ALZ_E_UNSUPPORTED; aPLib.Compress stays managed
+        [DllImport(Lib)] internal static extern UIntPtr alz_apenc_bound(UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_apenc_encode_batch(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* streams, byte* dstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern int alz_apenc_encode_batch_device(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* dSrcBase, UIntPtr srcBytes, AlzStream* streams, byte* dDstBase, UIntPtr dstBytes, AlzResult* results);
+        [DllImport(Lib)] internal static extern UIntPtr alz_apenc_file_bound(UIntPtr srcLen);
+        [DllImport(Lib)] internal static extern int alz_apenc_file_compress(IntPtr ctx, AlzSettings* settings,
+            byte* src, UIntPtr srcLen, byte* dst, UIntPtr dstCap, UIntPtr* dstLen);
+        [DllImport(Lib, ExactSpelling = true)] internal static extern int alz_apenc_file_compress_batch(IntPtr ctx, AlzSettings* settings, uint n,
+            byte* srcBase, UIntPtr srcBytes, AlzStream* files, byte* dstBase, UIntPtr dstBytes, AlzFileResult* results);
+
         // DEFLATE as zlib's inflate reads it (the body of ZLib / GZip, which the managed classes hand to the BCL), decode only: raw streams in
         // batches (format, decomLen, aux0, aux1 of a stream are ignored), their sizes without decoding, and the two classes on a whole file in
         // host memory (checksums verified on the host; *_measure takes them as correct)
