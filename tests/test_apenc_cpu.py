@@ -250,16 +250,17 @@ def test_bounds_without_a_device():
 
 
 def test_kernel_hash_family_and_build_list():
-    """the new kernels stand in alz_encode.hip, a file of the family "encode": no csrc header or kernel file is new, the families are the ones tools/kernel_hash.py
-    lists, and the committed counters belong to these sources"""
+    """the kernels stand in alz_encode_bits.h, a header alz_encode.hip includes and a file of the family "encode": every csrc header and kernel file is listed in a
+    family, the families are the ones tools/kernel_hash.py lists, and the committed counters belong to these sources"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_hash as KH
     csrc = os.path.join(ROOT, "auroralib", "compression_amd", "csrc")
     listed = set(sum(KH.FAMILIES.values(), []))
     assert not [f for f in os.listdir(csrc) if f.endswith((".h", ".hip")) and f not in listed]
     assert sorted(KH.FAMILIES) == ["aplib", "bitlz", "checksum", "decode", "encode", "filebatch", "framing", "inflate", "measure", "rlh", "xxh32", "zfile"]
-    hip = open(os.path.join(csrc, "alz_encode.hip")).read()
-    assert "enc_gamma_ap_kernel" in hip and "aplib_emit_lone" in hip and "ALZ_ENCFMT_APLIB" in hip
+    hip, bits = open(os.path.join(csrc, "alz_encode.hip")).read(), open(os.path.join(csrc, "alz_encode_bits.h")).read()
+    assert "alz_encode_bits.h" in KH.FAMILIES["encode"] and '#include "alz_encode_bits.h"' in hip
+    assert "enc_gamma_ap_kernel" in bits and "aplib_emit_lone" in bits and "ALZ_ENCFMT_APLIB" in hip
     for name in KH.FILES:
         assert KH.recorded(name).get("encode") == KH.kernel_hash("encode") and KH.recorded(name).get("decode") == KH.kernel_hash("decode"), name
     assert "alz_apenc_file.cpp" in open(os.path.join(csrc, "build.sh")).read()

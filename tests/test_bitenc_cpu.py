@@ -248,14 +248,15 @@ def test_bounds_and_host_side_refusals_without_a_device():
 
 
 def test_kernel_hash_family():
-    """the new kernels stand in alz_encode.hip, a file of the family "encode": no csrc header or kernel file is new, so none falls into both hashes, and the
-    committed counters belong to these sources"""
+    """the kernels stand in alz_encode_bits.h, a header alz_encode.hip includes and a file of the family "encode": every csrc header and kernel file is listed in
+    a family, so none falls into both hashes, and the committed counters belong to these sources"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_hash as KH
     csrc = os.path.join(ROOT, "auroralib", "compression_amd", "csrc")
     listed = set(sum(KH.FAMILIES.values(), []))
     assert not [f for f in os.listdir(csrc) if f.endswith((".h", ".hip")) and f not in listed]
-    hip = open(os.path.join(csrc, "alz_encode.hip")).read()
+    assert "alz_encode_bits.h" in KH.FAMILIES["encode"] and '#include "alz_encode_bits.h"' in open(os.path.join(csrc, "alz_encode.hip")).read()
+    hip = open(os.path.join(csrc, "alz_encode_bits.h")).read()
     assert all(k in hip for k in ("enc_bits_cri_kernel", "enc_bits_allz_kernel", "enc_bits_reverse_kernel"))
     for name in KH.FILES:
         assert KH.recorded(name).get("encode") == KH.kernel_hash("encode") and KH.recorded(name).get("decode") == KH.kernel_hash("decode"), name

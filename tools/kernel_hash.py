@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "auroralib", "compression_amd", "csrc")
 FAMILIES = {
     "decode": ["alz_kernels.hip", "alz_big.hip", "alz_decode_fast.h", "alz_decode_serial.h", "alz_device.h", "alz_emit_byte.h", "alz_emit_chunk.h", "alz_prs_table.h", "alz_internal.h"],
-    "encode": ["alz_encode.hip", "alz_encode_big.h", "alz_encode_seg.h", "alz_encode_seg_seq.h", "alz_device.h", "alz_internal.h"],
+    "encode": ["alz_encode.hip", "alz_encode_big.h", "alz_encode_bits.h", "alz_encode_seg.h", "alz_encode_seg_seq.h", "alz_device.h", "alz_internal.h"],
     "measure": ["alz_measure.hip", "alz_measure.h"],   # decoded sizes without decoding: no committed counters
     "rlh": ["alz_rlh.hip", "alz_rlh.h"],               # RLE30 / HUF20, the non-LZ bodies of the GBA / DS family: no committed counters
     "aplib": ["alz_aplib.hip", "alz_aplib.h"],         # aPLib, the 2 MiB-window LzWindows user (decode + measure): no committed counters
