@@ -80,6 +80,56 @@ class ContainerOptions(C.Structure):
                 ("key", C.c_uint32), ("name", C.c_uint8 * 32)]
 
 
+_VP, _U32, _SZ, _VPP = C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(C.c_void_p)
+_U32P, _SZP, _I32P = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)
+
+# Every function of include/auroralz.h has its argument types in one <FAMILY>_PROTOTYPES table below, and its return type in <FAMILY>_RESTYPES where
+# that is not int; PROTOTYPES / RESTYPES at the end of the file join the tables, and _lib.load() applies them.
+
+# the core: library and context, LZ batches on host and device buffers, plans, device memory
+CORE_PROTOTYPES = {
+    "alz_abi_version": [], "alz_device_count": [], "alz_last_error": [],
+    "alz_create": [C.c_int, _VPP], "alz_destroy": [_VP],
+    "alz_device_info": [_VP, C.c_char_p, _SZ, C.POINTER(C.c_int), C.POINTER(C.c_uint64)],
+    "alz_ctx_set_exact_kernels": [_VP, C.c_int], "alz_ctx_set_kernel_variant": [_VP, C.c_int],
+    "alz_ctx_big_stream": [_VP, _U32, C.POINTER(C.c_uint64)], "alz_ctx_release_scratch": [_VP],
+    "alz_decode_batch": [_VP, _VP, _U32, _VP, _SZ, _VP, _VP, _SZ, _VP],
+    "alz_decode_batch_multi": [_VPP, _U32, _VP, _U32, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP],
+    "alz_partition_batch": [_U32, _VP, _U32, _VP, _VP],
+    "alz_decode": [_VP, _U32, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _U32, _VP],
+    "alz_plan_create": [_VP, _VP, _U32, _VP, _VPP], "alz_plan_execute": [_VP, _VP, _VP, _VP, _VP],
+    "alz_plan_execute_timed": [_VP, _VP, _VP, _VP, C.c_int, C.POINTER(C.c_float)],
+    "alz_plan_results": [_VP, _VP, _VP], "alz_plan_destroy": [_VP, _VP],
+    "alz_plan_create_multi": [_VP, _U32, _VP, _U32, _VP, _VP, _VPP, _VP], "alz_plan_execute_multi": [_VP, _VP, _VP],
+    "alz_plan_results_multi": [_VP, _VP], "alz_plan_destroy_multi": [_VP],
+    "alz_encode_batch": [_VP, _VP, _VP, _U32, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP],
+    "alz_encode_batch_device": [_VP, _VP, _VP, _U32, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP],
+    "alz_encode_batch_multi": [_VPP, _U32, _VP, _VP, _U32, _VP, _SZ, _VP, _VP, _SZ, _VP, _VP, _VP],
+    "alz_device_malloc": [_VP, _SZ, _VPP], "alz_device_free": [_VP, _VP],
+    "alz_memcpy_h2d": [_VP, _VP, _VP, _SZ], "alz_memcpy_d2h": [_VP, _VP, _VP, _SZ], "alz_memset_d": [_VP, _VP, C.c_int, _SZ],
+    "alz_synchronize": [_VP],
+    "alz_measure_copy_bandwidth": [_VP, _SZ, C.c_int, C.POINTER(C.c_double)], "alz_last_kernel_ms": [_VP, C.POINTER(C.c_float)],
+}
+CORE_RESTYPES = {"alz_last_error": C.c_char_p, "alz_destroy": None, "alz_plan_destroy": None, "alz_plan_destroy_multi": None}
+
+# the container layer: a whole file of one alz_container in host memory (alz_container_measure is with the measure entry points)
+CONTAINER_PROTOTYPES = {
+    "alz_container_is_match": [_U32, _VP, _SZ],
+    "alz_container_decompressed_size": [_U32, _VP, _VP, _SZ, _U32P],
+    "alz_container_decompress": [_VP, _U32, _VP, _VP, _SZ, _VP, _SZ, _SZP, _SZP, _I32P],
+    "alz_container_compress": [_VP, _U32, _VP, _VP, _VP, _SZ, _VP, _SZ, _SZP],
+    "alz_container_compress_bound": [_U32, _SZ],                                   # returns size_t (CONTAINER_RESTYPES)
+}
+CONTAINER_RESTYPES = {"alz_container_compress_bound": C.c_size_t}
+
+# the batch producers of the reference's CLI (scan.py)
+SCAN_PROTOTYPES = {
+    "alz_container_scan": [_VP, _VP, _U32, _VP, _VP, _SZ, _VP, _SZ, _VP, _U32, _U32P, _SZP],
+    "alz_brute_decoder_name": [_U32],                                              # returns const char*
+    "alz_brute_force": [_VP, _VP, _SZ, _U32, _VP, _SZ, _VP],
+}
+SCAN_RESTYPES = {"alz_brute_decoder_name": C.c_char_p}
+
 # the measure entry points (include/auroralz.h): decoded sizes without decoding
 MEASURE_NO_BOUND = 0xFFFFFF00          # the largest dst_cap: "count everything"
 MEASURE_PROTOTYPES = {
@@ -233,7 +283,6 @@ class WfilePart(C.Structure):
     _fields_ = [("src_off", C.c_uint32), ("src_len", C.c_uint32), ("body", C.c_uint32), ("dst_len", C.c_uint32)]
 
 
-_U32P, _SZP = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)
 WFILE_PROTOTYPES = {
     "alz_wfile_is_match": [C.c_uint32, C.c_void_p, C.c_size_t],
     "alz_wfile_decompressed_size": [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, _U32P],
@@ -257,5 +306,9 @@ DEFLATE_PROTOTYPES = {
     "alz_deflate_file_compress_batch": _DEFLATE_ENCODE,
 }
 DEFLATE_RESTYPES = {"alz_deflate_bound": C.c_size_t, "alz_deflate_file_bound": C.c_size_t}
+
+# all of them: what _lib.load() sets on the loaded library
+PROTOTYPES = {name: types for table, rows in list(globals().items()) if table.endswith("_PROTOTYPES") for name, types in rows.items()}
+RESTYPES = {name: t for table, rows in list(globals().items()) if table.endswith("_RESTYPES") for name, t in rows.items()}
 
 assert C.sizeof(Stream) == 40 and C.sizeof(Result) == 16 and C.sizeof(LzProperties) == 16 and C.sizeof(FileResult) == 16

@@ -20,6 +20,16 @@ def _ref(lz):
     return C.byref(lz) if lz is not None else None
 
 
+def _settings(quality, strategy=0, min_distance=0, max_window_bits=0):
+    """the alz_settings* of a call"""
+    return C.byref(A.Settings(quality, max_window_bits, strategy, min_distance))
+
+
+def _encode_aux(streams):
+    """one alz_encode_aux per stream: the trailing array of the alz_encode_batch* calls"""
+    return (A.EncodeAux * len(streams))()
+
+
 def _dst_array(dst, dst_bytes):
     """the destination of a host-buffer call: a new zeroed array, or the caller's own after a check of its shape"""
     if dst is None:
@@ -94,25 +104,35 @@ class Context:
         check(self.lib.alz_last_kernel_ms(self.h, C.byref(v)))
         return v.value
 
-    # ---- the three shapes of a batch call; `lead`: what the C function takes between the context and n (alz_lz_properties or nothing)
-    def _host_decode(self, fn, lead, streams, src, dst_bytes, dst=None):
-        """fn(ctx, *lead, n, src, src_bytes, streams, dst, dst_bytes, results) on host buffers -> (dst, results)"""
+    # ---- the shapes of a batch call.  `lead`: what the C function takes between the context and n (alz_lz_properties, alz_settings, a level, nothing);
+    # files: the table is one of whole files, answered by one alz_file_result per file; aux: arrays the C function takes behind the results
+    def _host_decode(self, fn, lead, streams, src, dst_bytes, dst=None, files=False, aux=()):
+        """fn(ctx, *lead, n, src, src_bytes, streams, dst, dst_bytes, results, *aux) on host buffers -> (dst, results)"""
         src = np.ascontiguousarray(src, dtype=np.uint8)
         dst = _dst_array(dst, dst_bytes)
-        res = (A.Result * len(streams))()
-        check(fn(self.h, *lead, len(streams), _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res))
-        return dst, res
+        return dst, self._device(fn, lead, streams, _vp(src), src.nbytes, _vp(dst), dst_bytes, files=files, aux=aux)
 
-    def _host_measure(self, fn, lead, streams, src):
+    def _host_measure(self, fn, lead, streams, src, files=False):
         """fn(ctx, *lead, n, src, src_bytes, streams, results) on a host buffer -> results"""
         src = np.ascontiguousarray(src, dtype=np.uint8)
-        return self._device(fn, lead, streams, _vp(src), src.nbytes)
+        return self._device(fn, lead, streams, _vp(src), src.nbytes, files=files)
 
-    def _device(self, fn, lead, streams, d_src, src_bytes, *dst):
-        """fn(ctx, *lead, n, d_src, src_bytes, streams, [d_dst, dst_bytes,] results) -> results"""
-        res = (A.Result * len(streams))()
-        check(fn(self.h, *lead, len(streams), d_src, src_bytes, streams, *dst, res))
+    def _device(self, fn, lead, streams, d_src, src_bytes, *dst, files=False, aux=()):
+        """fn(ctx, *lead, n, d_src, src_bytes, streams, [d_dst, dst_bytes,] results, *aux) -> results"""
+        res = (A.FileResult * len(streams))() if files else (A.Result * len(streams))()
+        check(fn(self.h, *lead, len(streams), d_src, src_bytes, streams, *dst, res, *aux))
         return res
+
+    def _host_ranges(self, fn, lead, ranges, src):
+        """fn(ctx, *lead, n, src, src_bytes, ranges, uint32[]) on a host buffer -> one uint32 per range"""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        return self._ranges(fn, lead, ranges, _vp(src), src.nbytes)
+
+    def _ranges(self, fn, lead, ranges, d_src, src_bytes):
+        """fn(ctx, *lead, n, d_src, src_bytes, ranges, uint32[]) -> one uint32 per range"""
+        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
+        check(fn(self.h, *lead, len(ranges), d_src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:len(ranges)]
 
     # ---- host-buffer decode (upload, decode on GPU, download)
     def decode_batch(self, streams, src, dst_bytes, lz=None, dst=None):
@@ -203,46 +223,32 @@ class Context:
         """alz_bitenc_encode_batch on host buffers -> (dst, results): CompressHeaderless of the two classes, the managed bytes for the same settings.
         A body occupies [dst_off, dst_off + dst_len); an ALLZ stream takes aux0 = A.allz_aux0(copy, dist, len).  ALLZ at quality 1 raises AlzError
         E_UNSUPPORTED.  A lone large buffer goes through the same batch pipeline as many small ones."""
-        st = A.Settings(quality, 0, strategy, 0)
-        return self._host_decode(self.lib.alz_bitenc_encode_batch, (C.byref(st),), streams, src, dst_bytes, dst)
+        return self._host_decode(self.lib.alz_bitenc_encode_batch, (_settings(quality, strategy),), streams, src, dst_bytes, dst)
 
     def bitenc_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes, quality=8, strategy=0):
         """alz_bitenc_encode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
-        st = A.Settings(quality, 0, strategy, 0)
-        return self._device(self.lib.alz_bitenc_encode_batch_device, (C.byref(st),), streams, d_src, src_bytes, d_dst, dst_bytes)
+        return self._device(self.lib.alz_bitenc_encode_batch_device, (_settings(quality, strategy),), streams, d_src, src_bytes, d_dst, dst_bytes)
 
     def bitenc_file_compress_batch(self, files, src, dst_bytes, quality=8, strategy=0, dst=None):
         """alz_bitenc_file_compress_batch on host buffers -> (dst, results): per file (Stream.format an A.BITLZ_* value, aux0 ALLZ's start bits) what
         alz_bitenc_file_compress writes and returns for it alone; all bodies are one encode batch."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        st = A.Settings(quality, 0, strategy, 0)
-        check(self.lib.alz_bitenc_file_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_bitenc_file_compress_batch, (_settings(quality, strategy),), files, src, dst_bytes, dst, files=True)
 
     # ---- aPLib written: raw buffers in (src_*), headerless bodies out (dst_*); format, aux0, aux1 and decom_len of a stream are ignored
     def apenc_encode_batch(self, streams, src, dst_bytes, quality=8, strategy=0, dst=None):
         """alz_apenc_encode_batch on host buffers -> (dst, results): aPLib.CompressHeaderless, the managed bytes for the same settings.  A body
         occupies [dst_off, dst_off + dst_len).  An empty stream raises AlzError E_INVALID; at qualities 1..7 a stream longer than the managed
         chain table (2^18 / 2^19 / 2^20 bytes) raises E_UNSUPPORTED.  A lone large buffer goes through the same batch pipeline as many small ones."""
-        st = A.Settings(quality, 0, strategy, 0)
-        return self._host_decode(self.lib.alz_apenc_encode_batch, (C.byref(st),), streams, src, dst_bytes, dst)
+        return self._host_decode(self.lib.alz_apenc_encode_batch, (_settings(quality, strategy),), streams, src, dst_bytes, dst)
 
     def apenc_encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes, quality=8, strategy=0):
         """alz_apenc_encode_batch_device: both buffers in HBM; returns the results, last_kernel_ms() is the device time of the launches."""
-        st = A.Settings(quality, 0, strategy, 0)
-        return self._device(self.lib.alz_apenc_encode_batch_device, (C.byref(st),), streams, d_src, src_bytes, d_dst, dst_bytes)
+        return self._device(self.lib.alz_apenc_encode_batch_device, (_settings(quality, strategy),), streams, d_src, src_bytes, d_dst, dst_bytes)
 
     def apenc_file_compress_batch(self, files, src, dst_bytes, quality=8, strategy=0, dst=None):
         """alz_apenc_file_compress_batch on host buffers -> (dst, results): per file what alz_apenc_file_compress writes and returns for it
         alone ("AP32", the 24-byte header, the body); all bodies are one encode batch."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        st = A.Settings(quality, 0, strategy, 0)
-        check(self.lib.alz_apenc_file_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_apenc_file_compress_batch, (_settings(quality, strategy),), files, src, dst_bytes, dst, files=True)
 
     # ---- DEFLATE (decode only): raw streams as zlib's inflate reads them; format, decom_len, aux0 and aux1 of a stream are ignored
     def inflate_decode_batch(self, streams, src, dst_bytes, dst=None):
@@ -262,15 +268,13 @@ class Context:
         return self._device(self.lib.alz_inflate_measure_batch_device, (), streams, d_src, src_bytes)
 
     # ---- checksums of byte ranges: kind is A.CK_ADLER32 or A.CK_CRC32; a range is src_off / src_len of its Stream
-    def _checksum(self, fn, kind, ranges, src, src_bytes):
-        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
-        check(fn(self.h, kind, len(ranges), src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out[:len(ranges)]
+    def _checksum(self, fn, kind, ranges, d_src, src_bytes):
+        """either form of the call on a source that is already a pointer (tests/test_gpu_checksum.py holds the two forms against each other this way)"""
+        return self._ranges(fn, (kind,), ranges, d_src, src_bytes)
 
     def checksum_batch(self, kind, ranges, src):
         """alz_checksum_batch on a host buffer -> a uint32 array, one checksum per range."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        return self._checksum(self.lib.alz_checksum_batch, kind, ranges, _vp(src), src.nbytes)
+        return self._host_ranges(self.lib.alz_checksum_batch, (kind,), ranges, src)
 
     def checksum_batch_device(self, kind, ranges, d_src, src_bytes):
         """alz_checksum_batch_device: the same with the bytes already in HBM at d_src; last_kernel_ms() is the device time of the two launches."""
@@ -280,85 +284,51 @@ class Context:
     def zfile_decode_batch(self, files, src, dst_bytes, dst=None):
         """alz_zfile_decode_batch on host buffers -> (dst, results): per file what alz_zlib_decompress / alz_gzip_decompress return for it alone.
         `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        check(self.lib.alz_zfile_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_zfile_decode_batch, (), files, src, dst_bytes, dst, files=True)
 
     def wfile_decode_batch(self, files, src, dst_bytes, dst=None):
         """alz_wfile_decode_batch on host buffers -> (dst, results): files[i].format is an A.WF_* kind (a batch may mix them), aux0 bit 0 the byte
         order of an HWGZ / ZLWF file; per file what alz_wfile_decompress returns for it alone."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        check(self.lib.alz_wfile_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_wfile_decode_batch, (), files, src, dst_bytes, dst, files=True)
 
     def zfile_measure_batch(self, files, src):
         """alz_zfile_measure_batch on a host buffer -> results: per file what alz_zlib_measure / alz_gzip_measure return; dst_cap is the size limit."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        res = (A.FileResult * len(files))()
-        check(self.lib.alz_zfile_measure_batch(self.h, len(files), _vp(src), src.nbytes, files, res))
-        return res
+        return self._host_measure(self.lib.alz_zfile_measure_batch, (), files, src, files=True)
 
     # ---- XXH32 of byte ranges (the checksum of the LZ4 frame format); a range is src_off / src_len of its Stream
-    def _xxh32(self, fn, ranges, src, src_bytes, seed):
-        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
-        check(fn(self.h, seed, len(ranges), src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out[:len(ranges)]
-
     def xxh32_batch(self, ranges, src, seed=0):
         """alz_xxh32_batch on a host buffer -> a uint32 array, one XXH32 per range."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        return self._xxh32(self.lib.alz_xxh32_batch, ranges, _vp(src), src.nbytes, seed)
+        return self._host_ranges(self.lib.alz_xxh32_batch, (seed,), ranges, src)
 
     def xxh32_batch_device(self, ranges, d_src, src_bytes, seed=0):
         """alz_xxh32_batch_device: the same with the bytes already in HBM at d_src; last_kernel_ms() is the device time of the launch."""
-        return self._xxh32(self.lib.alz_xxh32_batch_device, ranges, d_src, src_bytes, seed)
+        return self._ranges(self.lib.alz_xxh32_batch_device, (seed,), ranges, d_src, src_bytes)
 
     # ---- LZ4 and Snappy files in batches: Stream.format is A.C_LZ4_FRAME, A.C_LZ4_LEGACY or A.C_SNAPPY, src_off / src_len the whole file
     def framed_decode_batch(self, files, src, dst_bytes, dst=None):
         """alz_framed_decode_batch on host buffers -> (dst, results): per file what alz_container_decompress returns for it alone.
         `dst`: a caller-owned uint8 array of >= dst_bytes to decode into (default: a new one)."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        check(self.lib.alz_framed_decode_batch(self.h, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_framed_decode_batch, (), files, src, dst_bytes, dst, files=True)
 
     def framed_measure_batch(self, files, src):
         """alz_framed_measure_batch on a host buffer -> results: per file what alz_container_measure returns; dst_cap is the size limit."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        res = (A.FileResult * len(files))()
-        check(self.lib.alz_framed_measure_batch(self.h, len(files), _vp(src), src.nbytes, files, res))
-        return res
+        return self._host_measure(self.lib.alz_framed_measure_batch, (), files, src, files=True)
 
     # ---- CRC-32C of byte ranges (the checksum of a framed Snappy chunk, before its mask); a range is src_off / src_len of its Stream
-    def _crc32c(self, fn, ranges, src, src_bytes):
-        out = np.zeros(max(len(ranges), 1), dtype=np.uint32)
-        check(fn(self.h, len(ranges), src, src_bytes, ranges, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out[:len(ranges)]
-
     def crc32c_batch(self, ranges, src):
         """alz_crc32c_batch on a host buffer -> a uint32 array, one CRC-32C per range."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        return self._crc32c(self.lib.alz_crc32c_batch, ranges, _vp(src), src.nbytes)
+        return self._host_ranges(self.lib.alz_crc32c_batch, (), ranges, src)
 
     def crc32c_batch_device(self, ranges, d_src, src_bytes):
         """alz_crc32c_batch_device: the same with the bytes already in HBM at d_src; last_kernel_ms() is the device time of the two launches."""
-        return self._crc32c(self.lib.alz_crc32c_batch_device, ranges, d_src, src_bytes)
+        return self._ranges(self.lib.alz_crc32c_batch_device, (), ranges, d_src, src_bytes)
 
     # ---- LZ4 and Snappy files written in batches: Stream.format is A.C_LZ4_FRAME, A.C_LZ4_LEGACY or A.C_SNAPPY, src_off / src_len the raw input
     def framing_compress_batch(self, files, src, dst_bytes, dst=None, quality=8, strategy=0, min_distance=0, max_window_bits=0):
         """alz_framing_compress_batch on host buffers -> (dst, results): per file what alz_container_compress writes and returns for it alone
         (aux0: the block size of an LZ4 frame).  `dst`: a caller-owned uint8 array of >= dst_bytes to write into (default: a new one)."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        st = A.Settings(quality, max_window_bits, strategy, min_distance)
-        check(self.lib.alz_framing_compress_batch(self.h, C.byref(st), len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        st = _settings(quality, strategy, min_distance, max_window_bits)
+        return self._host_decode(self.lib.alz_framing_compress_batch, (st,), files, src, dst_bytes, dst, files=True)
 
     # ---- DEFLATE written on the GPU: raw streams (src_* the raw input, dst_* where the stream goes); level 0..9, flags A.DEFLATE_FIXED
     def deflate_encode_batch(self, streams, src, dst_bytes, level=6, flags=0, dst=None):
@@ -372,35 +342,20 @@ class Context:
     def deflate_file_compress_batch(self, files, src, dst_bytes, level=6, flags=0, dst=None):
         """alz_deflate_file_compress_batch on host buffers -> (dst, results): per file (Stream.format: A.ZFILE_ZLIB or A.ZFILE_GZIP) what
         alz_deflate_file_compress writes and returns for it alone.  `dst`: a caller-owned uint8 array of >= dst_bytes (default: a new one)."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = _dst_array(dst, dst_bytes)
-        res = (A.FileResult * len(files))()
-        check(self.lib.alz_deflate_file_compress_batch(self.h, level, flags, len(files), _vp(src), src.nbytes, files, _vp(dst), dst_bytes, res))
-        return dst, res
+        return self._host_decode(self.lib.alz_deflate_file_compress_batch, (level, flags), files, src, dst_bytes, dst, files=True)
 
     # ---- host-buffer encode
     def encode_batch(self, streams, src, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch: streams describe RAW inputs (src_*) and compressed-output capacity (dst_*)."""
-        n = len(streams)
-        src = np.ascontiguousarray(src, dtype=np.uint8)
-        dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
-        res = (A.Result * n)()
-        aux = (A.EncodeAux * n)()
-        st = A.Settings(quality, max_window_bits, strategy, min_distance)
-        check(self.lib.alz_encode_batch(self.h, C.byref(lz) if lz is not None else None, C.byref(st), n, _vp(src), src.nbytes, streams,
-                                        _vp(dst), dst_bytes, res, aux))
+        st, aux = _settings(quality, strategy, min_distance, max_window_bits), _encode_aux(streams)
+        dst, res = self._host_decode(self.lib.alz_encode_batch, (_ref(lz), st), streams, src, dst_bytes, aux=(aux,))
         return dst, res, aux
 
     def encode_batch_device(self, streams, d_src, src_bytes, d_dst, dst_bytes, quality=8, lz=None, strategy=0, min_distance=0, max_window_bits=0):
         """alz_encode_batch_device: raw buffers already in HBM at d_src, compressed streams left in HBM at d_dst (offsets of
         `streams` are relative to the two device pointers).  Returns (results, aux); last_kernel_ms() is the device time."""
-        n = len(streams)
-        res = (A.Result * n)()
-        aux = (A.EncodeAux * n)()
-        st = A.Settings(quality, max_window_bits, strategy, min_distance)
-        check(self.lib.alz_encode_batch_device(self.h, C.byref(lz) if lz is not None else None, C.byref(st), n, d_src, src_bytes, streams,
-                                               d_dst, dst_bytes, res, aux))
-        return res, aux
+        st, aux = _settings(quality, strategy, min_distance, max_window_bits), _encode_aux(streams)
+        return self._device(self.lib.alz_encode_batch_device, (_ref(lz), st), streams, d_src, src_bytes, d_dst, dst_bytes, aux=(aux,)), aux
 
     # ---- device memory
     def malloc(self, nbytes):
@@ -433,7 +388,7 @@ class Plan:
     def __init__(self, ctx, streams, lz=None):
         self.ctx, self.n = ctx, len(streams)
         h = C.c_void_p()
-        check(ctx.lib.alz_plan_create(ctx.h, C.byref(lz) if lz is not None else None, self.n, streams, C.byref(h)))
+        check(ctx.lib.alz_plan_create(ctx.h, _ref(lz), self.n, streams, C.byref(h)))
         self.h = h
 
     def execute(self, d_src, d_dst, hip_stream=None):
@@ -468,8 +423,7 @@ class MultiPlan:
         if part_of is not None:
             given = np.ascontiguousarray(part_of, dtype=np.uint32)
         h = C.c_void_p()
-        check(self.lib.alz_plan_create_multi(arr, len(self.ctxs), C.byref(lz) if lz is not None else None, self.n, streams,
-                                             _vp(given) if given is not None else None, C.byref(h), _vp(part)))
+        check(self.lib.alz_plan_create_multi(arr, len(self.ctxs), _ref(lz), self.n, streams, _vp(given), C.byref(h), _vp(part)))
         self.h, self.part_of = h, part[:self.n]
 
     def execute(self, d_srcs, d_dsts):
@@ -519,8 +473,7 @@ def decode_batch_multi(ctxs, streams, src, dst_bytes, lz=None):
     res = (A.Result * n)()
     part = np.zeros(max(n, 1), dtype=np.uint32)
     hs = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
-    check(lib.alz_decode_batch_multi(hs, len(ctxs), C.byref(lz) if lz is not None else None, n, _vp(src), src.nbytes, streams,
-                                     _vp(dst), dst_bytes, res, _vp(part)))
+    check(lib.alz_decode_batch_multi(hs, len(ctxs), _ref(lz), n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res, _vp(part)))
     return dst, res, part[:n]
 
 
@@ -531,10 +484,9 @@ def encode_batch_multi(ctxs, streams, src, dst_bytes, quality=8, lz=None, strate
     src = np.ascontiguousarray(src, dtype=np.uint8)
     dst = np.zeros(max(dst_bytes, 1), dtype=np.uint8)
     res = (A.Result * n)()
-    aux = (A.EncodeAux * n)()
+    aux = _encode_aux(streams)
     part = np.zeros(max(n, 1), dtype=np.uint32)
-    st = A.Settings(quality, max_window_bits, strategy, min_distance)
+    st = _settings(quality, strategy, min_distance, max_window_bits)
     hs = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
-    check(lib.alz_encode_batch_multi(hs, len(ctxs), C.byref(lz) if lz is not None else None, C.byref(st), n, _vp(src), src.nbytes, streams,
-                                     _vp(dst), dst_bytes, res, aux, _vp(part)))
+    check(lib.alz_encode_batch_multi(hs, len(ctxs), _ref(lz), st, n, _vp(src), src.nbytes, streams, _vp(dst), dst_bytes, res, aux, _vp(part)))
     return dst, res, aux, part[:n]

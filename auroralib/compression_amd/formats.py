@@ -71,6 +71,85 @@ def _raise_for_outcome(rc, status, dst_len):
     check(rc)
 
 
+def _alz_settings(settings):
+    """the alz_settings* of a call from a CompressionSettings (None: Balanced)"""
+    s = settings or CompressionSettings.Balanced
+    return C.byref(A.Settings(s.Quality, s.MaxWindowBits, s.Strategy, 0))
+
+
+def _keeps_src_used(reader):
+    """the `used` of _single for a class that keeps the count as last_src_used"""
+    return lambda n: setattr(reader, "last_src_used", n)
+
+
+def _single(fn, head, data, cap, used=None, used_after=False):
+    """One file through fn(ctx, *head, src, src_len, dst, cap, &dst_len[, &src_used, &status]) -> the bytes it left.  The destination is untouched
+    memory (np.empty: create_string_buffer writes the whole capacity first -- 68 MB of zeros for a 67 MB frame).  used: the call is a read -- fn has
+    the last two arguments, its outcome is raised as the reference's exception, and used(src_used) runs before that (used_after: only once the outcome
+    has passed).  None: a write, a failure is an AlzError."""
+    dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
+    dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
+    rc = fn(_context().h, *head, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl), *(() if used is None else (C.byref(su), C.byref(st))))
+    if used is None:
+        check(rc)
+    elif used_after:
+        _raise_for_outcome(rc, st.value, dl.value)
+        used(su.value)
+    else:
+        used(su.value)
+        _raise_for_outcome(rc, st.value, dl.value)
+    return dst_arr[:dl.value].tobytes()
+
+
+def _file_error(r, i, entry):
+    """What the alz_file_result of file i stands for: None (its bytes are good) or an exception instance -- the instance is the result.  entry: the
+    batch wrote the files, a failure is the AlzError of that entry point; None: it read them, a failure is what Decompress raises."""
+    if entry is not None:
+        return AlzError(r.rc, "%s: file %d" % (entry, i)) if r.rc else None
+    try:
+        _raise_for_outcome(r.rc, r.status, r.dst_len)
+    except Exception as e:
+        return e
+    return None
+
+
+def _source(files):
+    """the sources of a batch back to back in one buffer, one byte of padding behind the last"""
+    return np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8)
+
+
+def _table(files, caps, kind=0, aux0=0, align=16):
+    """The stream table of one batch over `files` as _source lays them out: file i gets caps[i] bytes of destination (None: no row), every
+    destination starts where the one before ends, rounded up to `align` bytes (1: back to back; 0: a measure pass, dst_off stays 0).  `kind` is
+    what Stream.format of the batch family takes.  -> (table, dst_bytes)"""
+    rows, so, do = [], 0, 0
+    for f, cap in zip(files, caps):
+        if cap is not None:
+            rows.append(A.Stream(so, do, len(f), cap, 0, aux0, 0, kind))
+            do += (cap + align - 1) // align * align if align else 0
+        so += len(f)
+    return (A.Stream * len(rows))(*rows), do
+
+
+def _cut(table, dst, res, entry=None):
+    """per row of the table its bytes out of dst -- or the exception instance of _file_error"""
+    out = []
+    for i, (row, r) in enumerate(zip(table, res)):
+        e = _file_error(r, i, entry)
+        out.append(e if e is not None else dst[int(row.dst_off):int(row.dst_off) + r.dst_len].tobytes())
+    return out
+
+
+def _batch(files, caps, run, kind=0, aux0=0, align=16, extra=0, entry=None, call_empty=True):
+    """Whole files through ONE batch: run(table, src, dst_bytes) -> (dst, results) over _table / _source of them, the destination `extra` bytes longer
+    than the slots; call_empty: an empty list is a call with n = 0 (False: no call).  Returns a list with, per file, its bytes or its exception instance."""
+    if not files and not call_empty:
+        return []
+    table, dst_bytes = _table(files, caps, kind, aux0, align)
+    dst, res = run(table, _source(files), dst_bytes + extra)
+    return _cut(table, dst, res, entry)
+
+
 def _decompress_many(files, kind, limit, measure_batch, decode_batch, decode_decides=False):
     """The two GPU batches behind every DecompressMany: measure_batch(table, src) gives the sizes up to `limit`, the destination holds exactly
     the measured sizes, decode_batch(table, src, dst_bytes) fills it.  `kind` is what Stream.format of the batch family takes for the class.
@@ -78,30 +157,17 @@ def _decompress_many(files, kind, limit, measure_batch, decode_batch, decode_dec
     there, and the decode's outcome is the file's (Decompress decodes first: a wrong content checksum in front of a truncated frame, a
     Snappy chunk the decoder refuses).  Returns a list with, per file, its bytes -- or the exception instance Decompress would have raised."""
     files = [bytes(f) for f in files]
-    src = np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8)
-    table, so = (A.Stream * len(files))(), 0
-    for i, f in enumerate(files):
-        table[i] = A.Stream(so, 0, len(f), limit, 0, 0, 0, kind)
-        so += len(f)
-
-    def outcome(r):
-        try:
-            _raise_for_outcome(r.rc, r.status, r.dst_len)
-        except Exception as e:              # the instance is the result
-            return e
-        return None
+    src = _source(files)
+    table, _ = _table(files, [limit] * len(files), kind, align=0)
     measured = measure_batch(table, src) if files else []
-    out = [outcome(r) for r in measured]
-    good, do = [i for i, e in enumerate(out) if e is None or (decode_decides and measured[i].rc == A.E_STREAM and measured[i].status != A.ST_OUTPUT_CAPACITY)], 0
+    out = [_file_error(r, i, None) for i, r in enumerate(measured)]
+    caps = [r.dst_len if e is None or (decode_decides and r.rc == A.E_STREAM and r.status != A.ST_OUTPUT_CAPACITY) else None for r, e in zip(measured, out)]
+    good = [i for i, cap in enumerate(caps) if cap is not None]
     if good:
-        sub = (A.Stream * len(good))()
-        for k, i in enumerate(good):
-            sub[k] = A.Stream(table[i].src_off, do, table[i].src_len, measured[i].dst_len, 0, 0, 0, kind)
-            do += measured[i].dst_len
-        dst, res = decode_batch(sub, src, do)
-        for k, i in enumerate(good):
-            e = outcome(res[k])
-            out[i] = e if e is not None else dst[int(sub[k].dst_off):int(sub[k].dst_off) + res[k].dst_len].tobytes()
+        sub, dst_bytes = _table(files, caps, kind, align=1)
+        dst, res = decode_batch(sub, src, dst_bytes)
+        for i, result in zip(good, _cut(sub, dst, res)):
+            out[i] = result
     return out
 
 
@@ -184,15 +250,7 @@ class _Format:
         if capacity is None:
             capacity = self.GetDecompressedSize(data) + 273
         o = self._opt()
-        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)       # (untouched memory: create_string_buffer writes the whole capacity first -- 68 MB of zeros for a 67 MB frame)
-        dst = dst_arr.ctypes.data_as(C.c_void_p)
-        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
-        lib = load()
-        lib.alz_container_decompress.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-        rc = lib.alz_container_decompress(_context().h, self.container, C.byref(o), data, len(data), dst, capacity, C.byref(dl), C.byref(su), C.byref(st))
-        _raise_for_outcome(rc, st.value, dl.value)
-        self.last_src_used = su.value
-        return dst_arr[:dl.value].tobytes()
+        return _single(load().alz_container_decompress, (self.container, C.byref(o)), data, capacity, _keeps_src_used(self), used_after=True)
 
     def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
         """The decompressed size of a file of a format WITHOUT a size field (PRS, LZO, FastLZ, LZ4, LZ4Legacy, Snappy), measured on the GPU
@@ -209,19 +267,8 @@ class _Format:
 
     def Compress(self, data, settings=None):
         data = bytes(data)
-        s = settings or CompressionSettings.Balanced
-        st = A.Settings(s.Quality, s.MaxWindowBits, s.Strategy, 0)
-        o = self._opt()
-        lib = load()
-        lib.alz_container_compress_bound.restype = C.c_size_t
-        lib.alz_container_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
-        cap = lib.alz_container_compress_bound(self.container, len(data))
-        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
-        dst = dst_arr.ctypes.data_as(C.c_void_p)
-        dl = C.c_size_t()
-        lib.alz_container_compress.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        check(lib.alz_container_compress(_context().h, self.container, C.byref(o), C.byref(st), data, len(data), dst, cap, C.byref(dl)))
-        return dst_arr[:dl.value].tobytes()
+        o, lib = self._opt(), load()
+        return _single(lib.alz_container_compress, (self.container, C.byref(o), _alz_settings(settings)), data, lib.alz_container_compress_bound(self.container, len(data)))
 
 
 class LZSS(_Format):
@@ -402,25 +449,11 @@ class _FramedMany:
         datas = [bytes(d) for d in datas]
         s = settings or CompressionSettings.Balanced
         lib = load()
-        lib.alz_container_compress_bound.restype = C.c_size_t
-        lib.alz_container_compress_bound.argtypes = [C.c_uint32, C.c_size_t]
-        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
-        table, so, do = (A.Stream * len(datas))(), 0, 0
-        for i, d in enumerate(datas):
-            cap = lib.alz_container_compress_bound(self.container, len(d))
-            table[i] = A.Stream(so, do, len(d), cap, 0, self.ChunkSize, 0, self.container)
-            so += len(d)
-            do += cap
-        if not datas:
-            return []
-        dst, res = _context().framing_compress_batch(table, src, do, quality=s.Quality, strategy=s.Strategy, max_window_bits=s.MaxWindowBits)
-        out = []
-        for i, r in enumerate(res):
-            if r.rc != 0:
-                out.append(AlzError(r.rc, "alz_framing_compress_batch: file %d" % i))
-            else:
-                out.append(dst[int(table[i].dst_off):int(table[i].dst_off) + r.dst_len].tobytes())
-        return out
+
+        def run(table, src, dst_bytes):
+            return _context().framing_compress_batch(table, src, dst_bytes, quality=s.Quality, strategy=s.Strategy, max_window_bits=s.MaxWindowBits)
+        return _batch(datas, [lib.alz_container_compress_bound(self.container, len(d)) for d in datas], run, self.container, self.ChunkSize, align=1,
+                      entry="alz_framing_compress_batch", call_empty=False)
 
 
 class LZ4(_FramedMany, _Format):
@@ -607,61 +640,80 @@ APLIB_NO_ENCODER = ("aPLib has no encoder here: CompressHeaderless runs the tier
                     "pinned to the oracle through other formats")
 
 
-class APLib:
-    """src/AuroraLib.Compression/Formats/Common/aPLib.cs -- "AP32" + 24-byte header + body, or a headerless body (alz_aplib_*) and, for writing,
-    alz_apenc_file_* (Encode / EncodeMany; Compress still refuses).  No alz_container value backs it, so it stays outside ALL_FORMATS."""
-    provides_size = True
+class _PrefixFile:
+    """A class of the reference over its alz_<prefix>_* file entry points.  No alz_container value backs it, so it stays outside ALL_FORMATS."""
+    prefix = None
 
-    def Encode(self, data, settings=None):
-        """The file Compress of the reference writes for these settings (alz_apenc_file_compress): the finder and the bit emitter on the GPU.
-        Refused: an empty input (E_INVALID), MaxWindowBits other than 0, and at qualities 1..7 an input longer than the managed chain table
-        (2^18 bytes at quality 1, 2^19 at 2..4, 2^20 at 5..7: E_UNSUPPORTED)."""
-        data = bytes(data)
-        settings = settings or CompressionSettings.Balanced
-        lib = load()
-        cap = lib.alz_apenc_file_bound(len(data))
-        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
-        dl = C.c_size_t()
-        st = A.Settings(settings.Quality, settings.MaxWindowBits, settings.Strategy, 0)
-        check(lib.alz_apenc_file_compress(_context().h, C.byref(st), data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
-        return dst_arr[:dl.value].tobytes()
-
-    def EncodeMany(self, datas, settings=None):
-        """Encode for a whole set of inputs in ONE alz_apenc_file_compress_batch (one encode batch).  Returns a list with, per input, the file's
-        bytes -- or the exception instance Encode would have raised for it."""
-        datas = [bytes(d) for d in datas]
-        settings = settings or CompressionSettings.Balanced
-        if settings.MaxWindowBits:
-            raise AlzError(A.E_UNSUPPORTED, "MaxWindowBits %d: aPLib is written at its own window only" % settings.MaxWindowBits)
-        lib = load()
-        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
-        table, so, do = (A.Stream * len(datas))(), 0, 0
-        for i, d in enumerate(datas):
-            cap = max(lib.alz_apenc_file_bound(len(d)), 1)
-            table[i] = A.Stream(so, do, len(d), cap, 0, 0, 0, 0)
-            so += len(d)
-            do += (cap + 15) & ~15
-        dst, res = _context().apenc_file_compress_batch(table, src, do, settings.Quality, settings.Strategy)
-        out = []
-        for i, r in enumerate(res):
-            if r.rc:
-                out.append(AlzError(r.rc, "alz_apenc_file_compress_batch: file %d" % i))
-            else:
-                out.append(dst[table[i].dst_off:table[i].dst_off + r.dst_len].tobytes())
-        return out
+    def _entry(self, what):
+        return getattr(load(), "alz_%s_%s" % (self.prefix, what))
 
     def IsMatch(self, data):
         data = bytes(data)
-        return bool(load().alz_aplib_is_match(data, len(data)))
+        return bool(self._entry("is_match")(data, len(data)))
+
+
+class _HeaderFile(_PrefixFile):
+    """A header that states the size, around one body: alz_<prefix>_* reads the file, alz_<writer>_file_* writes it (Encode / EncodeMany; Compress
+    still refuses) -- with a `kind` argument where the writer's family has several (alz_bitenc_*), without where it has one (alz_apenc_*)."""
+    provides_size = True
+    writer = None
+    kind = None
+    slot_floor = 0                        # EncodeMany: the least bytes a file's slot of the destination gets
+    src_used_after = False                # Decompress: last_src_used is set only once the outcome has passed
+    own_window = None                     # EncodeMany: why MaxWindowBits is refused
+
+    def _aux0(self):
+        return 0
+
+    def _file_bound(self, n):
+        return getattr(load(), "alz_%s_file_bound" % self.writer)(*(() if self.kind is None else (self.kind,)), n)
+
+    def Encode(self, data, settings=None):
+        """The file Compress of the reference writes for these settings (alz_apenc_file_compress / alz_bitenc_file_compress): the finder and the bit
+        emitter on the GPU.  A lone large input goes through the batch pipeline -- there is no whole-GPU path for these formats.  Refused: MaxWindowBits
+        other than 0; aPLib: an empty input (E_INVALID), and at qualities 1..7 an input longer than the managed chain table (2^18 bytes at quality 1,
+        2^19 at 2..4, 2^20 at 5..7: E_UNSUPPORTED); ALLZ at quality 1 (E_UNSUPPORTED); a CRILAYLA source under 0x100 bytes (E_INVALID)."""
+        data = bytes(data)
+        st = _alz_settings(settings)
+        head = (st,) if self.kind is None else (self.kind, st, self._aux0())
+        return _single(getattr(load(), "alz_%s_file_compress" % self.writer), head, data, self._file_bound(len(data)))
+
+    def EncodeMany(self, datas, settings=None):
+        """Encode for a whole set of inputs in ONE alz_apenc_file_compress_batch / alz_bitenc_file_compress_batch (one encode batch).  Returns a list
+        with, per input, the file's bytes -- or the exception instance Encode would have raised for it."""
+        datas = [bytes(d) for d in datas]
+        s = settings or CompressionSettings.Balanced
+        if s.MaxWindowBits:
+            raise AlzError(A.E_UNSUPPORTED, "MaxWindowBits %d: %s" % (s.MaxWindowBits, self.own_window))
+
+        def run(table, src, dst_bytes):
+            return getattr(_context(), "%s_file_compress_batch" % self.writer)(table, src, dst_bytes, s.Quality, s.Strategy)
+        return _batch(datas, [max(self._file_bound(len(d)), self.slot_floor) for d in datas], run, self.kind or 0, self._aux0(),
+                      entry="alz_%s_file_compress_batch" % self.writer)
 
     def GetDecompressedSize(self, data):
         data = bytes(data)
         size = C.c_uint32()
-        rc = load().alz_aplib_decompressed_size(data, len(data), C.byref(size))
+        rc = self._entry("decompressed_size")(data, len(data), C.byref(size))
         if rc == A.E_FORMAT:
             raise InvalidIdentifierException()
         check(rc)
         return size.value
+
+    def Decompress(self, data, capacity=None):
+        data = bytes(data)
+        if capacity is None:
+            capacity = self.GetDecompressedSize(data)
+        return _single(self._entry("decompress"), (), data, capacity, _keeps_src_used(self), self.src_used_after)
+
+
+class APLib(_HeaderFile):
+    """src/AuroraLib.Compression/Formats/Common/aPLib.cs -- "AP32" + 24-byte header + body, or a headerless body (alz_aplib_*) and, for writing,
+    alz_apenc_file_* (Encode / EncodeMany; Compress still refuses).  No alz_container value backs it, so it stays outside ALL_FORMATS."""
+    prefix, writer = "aplib", "apenc"
+    slot_floor = 1
+    src_used_after = True
+    own_window = "aPLib is written at its own window only"
 
     def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
         """The decoded size of a HEADERLESS body, counted on the GPU without decoding (alz_aplib_measure_batch)."""
@@ -676,12 +728,7 @@ class APLib:
         data = bytes(data)
         if capacity is None:
             capacity = self.GetDecompressedSize(data) if data[:4] == b"AP32" and len(data) >= 24 else self.MeasureDecompressedSize(data)
-        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)
-        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
-        rc = load().alz_aplib_decompress(_context().h, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), capacity, C.byref(dl), C.byref(su), C.byref(st))
-        _raise_for_outcome(rc, st.value, dl.value)
-        self.last_src_used = su.value
-        return dst_arr[:dl.value].tobytes()
+        return super().Decompress(data, capacity)
 
     def Compress(self, data, settings=None):
         raise NotImplementedError(APLIB_NO_ENCODER)
@@ -692,21 +739,16 @@ INFLATE_NO_ENCODER = ("%s has no encoder here: the reference hands Compress to t
                       "the library's own DEFLATE encoder")
 
 
-class _InflateFile:
+class _InflateFile(_PrefixFile):
     """A class of the reference that hands its body to the BCL, over its alz_<prefix>_* file entry points (alz_inflate_decode_batch underneath);
     decode only.  No alz_container value backs it, so it stays outside ALL_FORMATS.  The format stores no size in front of the data."""
     provides_size = False
-    prefix = None
-
-    def IsMatch(self, data):
-        data = bytes(data)
-        return bool(getattr(load(), "alz_%s_is_match" % self.prefix)(data, len(data)))
 
     def MeasureDecompressedSize(self, data, limit=A.MEASURE_NO_BOUND):
         """The decoded size of the file, counted on the GPU without decoding (alz_<prefix>_measure); checksums are taken as correct."""
         data = bytes(data)
         n, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
-        rc = getattr(load(), "alz_%s_measure" % self.prefix)(_context().h, data, len(data), limit, C.byref(n), C.byref(su), C.byref(st))
+        rc = self._entry("measure")(_context().h, data, len(data), limit, C.byref(n), C.byref(su), C.byref(st))
         _raise_for_outcome(rc, st.value, n.value)
         return n.value
 
@@ -715,19 +757,14 @@ class _InflateFile:
         data = bytes(data)
         if cap is None:
             cap = self.MeasureDecompressedSize(data)
-        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
-        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
-        rc = getattr(load(), "alz_%s_decompress" % self.prefix)(_context().h, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl), C.byref(su), C.byref(st))
-        self.last_src_used = su.value
-        _raise_for_outcome(rc, st.value, dl.value)
-        return dst_arr[:dl.value].tobytes()
+        return _single(self._entry("decompress"), (), data, cap, _keeps_src_used(self))
 
     def DecompressMany(self, files, limit=A.MEASURE_NO_BOUND):
         """Decompress for a whole set of files in two GPU batches: one alz_zfile_measure_batch (sizes up to `limit`), a destination of exactly
         the measured sizes, one alz_zfile_decode_batch.  Returns a list with, per file, its bytes -- or the exception instance Decompress would
         have raised for it."""
         ctx = _context()
-        return _decompress_many(files, A.ZFILE_ZLIB if self.prefix == "zlib" else A.ZFILE_GZIP, limit, ctx.zfile_measure_batch, ctx.zfile_decode_batch)
+        return _decompress_many(files, self._kind(), limit, ctx.zfile_measure_batch, ctx.zfile_decode_batch)
 
     def Compress(self, data, settings=None):
         raise NotImplementedError(INFLATE_NO_ENCODER % type(self).__name__)
@@ -743,34 +780,18 @@ class _InflateFile:
     def Deflate(self, data, level=6, fixed=False):
         """The file of this class around a DEFLATE body of `level` 0..9 (alz_deflate_file_compress); fixed: fixed Huffman codes only."""
         data = bytes(data)
-        lib = load()
-        cap = lib.alz_deflate_file_bound(self._kind(), len(data))
-        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
-        dl = C.c_size_t()
-        check(lib.alz_deflate_file_compress(_context().h, self._kind(), level, A.DEFLATE_FIXED if fixed else 0, data, len(data),
-                                            dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
-        return dst_arr[:dl.value].tobytes()
+        lib, kind = load(), self._kind()
+        return _single(lib.alz_deflate_file_compress, (kind, level, A.DEFLATE_FIXED if fixed else 0), data, lib.alz_deflate_file_bound(kind, len(data)))
 
     def DeflateMany(self, datas, level=6, fixed=False):
         """Deflate for a whole set of inputs in ONE alz_deflate_file_compress_batch.  Returns a list with, per input, the file's bytes -- or the
         exception instance Deflate would have raised for it."""
         datas = [bytes(d) for d in datas]
-        lib = load()
-        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
-        table, so, do = (A.Stream * len(datas))(), 0, 0
-        for i, d in enumerate(datas):
-            cap = lib.alz_deflate_file_bound(self._kind(), len(d))
-            table[i] = A.Stream(so, do, len(d), cap, 0, 0, 0, self._kind())
-            so += len(d)
-            do += (cap + 15) & ~15
-        dst, res = _context().deflate_file_compress_batch(table, src, do, level, A.DEFLATE_FIXED if fixed else 0)
-        out = []
-        for i, r in enumerate(res):
-            if r.rc:
-                out.append(AlzError(r.rc, "alz_deflate_file_compress_batch: file %d" % i))
-            else:
-                out.append(dst[table[i].dst_off:table[i].dst_off + r.dst_len].tobytes())
-        return out
+        lib, kind = load(), self._kind()
+
+        def run(table, src, dst_bytes):
+            return _context().deflate_file_compress_batch(table, src, dst_bytes, level, A.DEFLATE_FIXED if fixed else 0)
+        return _batch(datas, [lib.alz_deflate_file_bound(kind, len(d)) for d in datas], run, kind, entry="alz_deflate_file_compress_batch")
 
 
 class ZLib(_InflateFile):
@@ -836,49 +857,31 @@ class _WrappedFile:
         data = bytes(data)
         if capacity is None:
             capacity = self.GetDecompressedSize(data) + 64
-        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)
-        dl, su, st, o = C.c_size_t(), C.c_size_t(), C.c_int32(), self._opt()
-        rc = load().alz_wfile_decompress(_context().h, self.kind, C.byref(o), data, len(data), dst_arr.ctypes.data_as(C.c_void_p), capacity,
-                                         C.byref(dl), C.byref(su), C.byref(st))
-        self.last_src_used = su.value
-        if self.kind == A.WF_SSZL and len(data) >= 16:
-            self.Options = int.from_bytes(data[12:16], "little")            # Decompress stores the file's Options  SSZL.cs:92
-        _raise_for_outcome(rc, st.value, dl.value)
-        return dst_arr[:dl.value].tobytes()
+        o = self._opt()
+
+        def used(n):
+            self.last_src_used = n
+            if self.kind == A.WF_SSZL and len(data) >= 16:
+                self.Options = int.from_bytes(data[12:16], "little")        # Decompress stores the file's Options  SSZL.cs:92
+        return _single(load().alz_wfile_decompress, (self.kind, C.byref(o)), data, capacity, used)
 
     def DecompressMany(self, files):
         """Decompress for a whole set of files of this class in ONE alz_wfile_decode_batch.  Returns a list with, per file, its bytes -- or the
         exception instance Decompress would have raised for it."""
         files = [bytes(f) for f in files]
         lib, o = load(), self._opt()
-        table, so, do = (A.Stream * len(files))(), 0, 0
-        for i, f in enumerate(files):
+
+        def slot(f):
             v = C.c_uint32()
-            cap = v.value + 64 if lib.alz_wfile_decompressed_size(self.kind, C.byref(o), f, len(f), C.byref(v)) == 0 else 0
-            table[i] = A.Stream(so, do, len(f), cap, 0, o.big_endian, 0, self.kind)
-            so += len(f)
-            do += (cap + 15) & ~15
-        dst, res = _context().wfile_decode_batch(table, np.frombuffer(b"".join(files) + bytes(1), dtype=np.uint8), do + 64)
-        out = []
-        for i, r in enumerate(res):
-            try:
-                _raise_for_outcome(r.rc, r.status, r.dst_len)
-                out.append(dst[int(table[i].dst_off):int(table[i].dst_off) + r.dst_len].tobytes())
-            except Exception as e:          # the instance is the result
-                out.append(e)
-        return out
+            return v.value + 64 if lib.alz_wfile_decompressed_size(self.kind, C.byref(o), f, len(f), C.byref(v)) == 0 else 0
+        return _batch(files, [slot(f) for f in files], lambda table, src, dst_bytes: _context().wfile_decode_batch(table, src, dst_bytes),
+                      self.kind, o.big_endian, extra=64)
 
     def _write(self, data, settings, level, flags):
         data = bytes(data)
         lib, o = load(), self._opt()
-        s = settings or CompressionSettings.Balanced
-        st = A.Settings(s.Quality, s.MaxWindowBits, s.Strategy, 0)
-        cap = lib.alz_wfile_compress_bound(self.kind, C.byref(o), len(data))
-        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
-        dl = C.c_size_t()
-        check(lib.alz_wfile_compress(_context().h, self.kind, C.byref(o), C.byref(st), level, flags, data, len(data),
-                                     dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
-        return dst_arr[:dl.value].tobytes()
+        return _single(lib.alz_wfile_compress, (self.kind, C.byref(o), _alz_settings(settings), level, flags), data,
+                       lib.alz_wfile_compress_bound(self.kind, C.byref(o), len(data)))
 
     def Compress(self, data, settings=None):
         if self.deflate:
@@ -951,77 +954,11 @@ BITLZ_NO_ENCODER = ("%s has no encoder here: CompressHeaderless runs the LzChain
                     "on the GPU: its bit-identity is held against a Python restatement of the finder that is pinned to the oracle through other formats")
 
 
-class _BitLzFile:
+class _BitLzFile(_HeaderFile):
     """A class of the .Extended assembly over its alz_<prefix>_* file entry points (alz_bitlz_decode_batch underneath) and, for writing,
     alz_bitenc_file_* (Encode / EncodeMany; Compress still refuses).  No alz_container value backs it, so it stays outside ALL_FORMATS."""
-    provides_size = True
-    prefix = None
-    kind = None
-
-    def _aux0(self):
-        return 0
-
-    def Encode(self, data, settings=None):
-        """The file Compress of the reference writes for these settings (alz_bitenc_file_compress): the finder and the bit emitter on the GPU.
-        A lone large input goes through the batch pipeline -- there is no whole-GPU path for these two formats.  Refused: MaxWindowBits other than 0,
-        ALLZ at quality 1 (E_UNSUPPORTED), a CRILAYLA source under 0x100 bytes (E_INVALID)."""
-        data = bytes(data)
-        settings = settings or CompressionSettings.Balanced
-        lib = load()
-        cap = lib.alz_bitenc_file_bound(self.kind, len(data))
-        dst_arr = np.empty(max(cap, 1), dtype=np.uint8)
-        dl = C.c_size_t()
-        st = A.Settings(settings.Quality, settings.MaxWindowBits, settings.Strategy, 0)
-        check(lib.alz_bitenc_file_compress(_context().h, self.kind, C.byref(st), self._aux0(), data, len(data), dst_arr.ctypes.data_as(C.c_void_p), cap, C.byref(dl)))
-        return dst_arr[:dl.value].tobytes()
-
-    def EncodeMany(self, datas, settings=None):
-        """Encode for a whole set of inputs in ONE alz_bitenc_file_compress_batch (one encode batch).  Returns a list with, per input, the file's
-        bytes -- or the exception instance Encode would have raised for it."""
-        datas = [bytes(d) for d in datas]
-        settings = settings or CompressionSettings.Balanced
-        if settings.MaxWindowBits:
-            raise AlzError(A.E_UNSUPPORTED, "MaxWindowBits %d: CRILAYLA and ALLZ are written at their own windows only" % settings.MaxWindowBits)
-        lib = load()
-        src = np.frombuffer(b"".join(datas) + bytes(1), dtype=np.uint8)
-        table, so, do = (A.Stream * len(datas))(), 0, 0
-        for i, d in enumerate(datas):
-            cap = lib.alz_bitenc_file_bound(self.kind, len(d))
-            table[i] = A.Stream(so, do, len(d), cap, 0, self._aux0(), 0, self.kind)
-            so += len(d)
-            do += (cap + 15) & ~15
-        dst, res = _context().bitenc_file_compress_batch(table, src, do, settings.Quality, settings.Strategy)
-        out = []
-        for i, r in enumerate(res):
-            if r.rc:
-                out.append(AlzError(r.rc, "alz_bitenc_file_compress_batch: file %d" % i))
-            else:
-                out.append(dst[table[i].dst_off:table[i].dst_off + r.dst_len].tobytes())
-        return out
-
-    def IsMatch(self, data):
-        data = bytes(data)
-        return bool(getattr(load(), "alz_%s_is_match" % self.prefix)(data, len(data)))
-
-    def GetDecompressedSize(self, data):
-        data = bytes(data)
-        size = C.c_uint32()
-        rc = getattr(load(), "alz_%s_decompressed_size" % self.prefix)(data, len(data), C.byref(size))
-        if rc == A.E_FORMAT:
-            raise InvalidIdentifierException()
-        check(rc)
-        return size.value
-
-    def Decompress(self, data, capacity=None):
-        data = bytes(data)
-        if capacity is None:
-            capacity = self.GetDecompressedSize(data)
-        dst_arr = np.empty(max(capacity, 1), dtype=np.uint8)
-        dl, su, st = C.c_size_t(), C.c_size_t(), C.c_int32()
-        rc = getattr(load(), "alz_%s_decompress" % self.prefix)(_context().h, data, len(data), dst_arr.ctypes.data_as(C.c_void_p), capacity, C.byref(dl), C.byref(su), C.byref(st))
-        self.last_src_used = su.value
-        _raise_for_outcome(rc, st.value, dl.value)
-        return dst_arr[:dl.value].tobytes()
+    writer = "bitenc"
+    own_window = "CRILAYLA and ALLZ are written at their own windows only"
 
     def Compress(self, data, settings=None):
         raise NotImplementedError(BITLZ_NO_ENCODER % type(self).__name__)

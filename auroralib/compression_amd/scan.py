@@ -27,8 +27,6 @@ def scan(data, formats, big_endian=True, lz=None, max_hits=1 << 16, dst_cap=None
         o.lz = lz
     cap = dst_cap if dst_cap is not None else max(len(data) * 16, 1 << 20)
     lib = load()
-    lib.alz_container_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     while True:
         dst_arr = np.empty(cap, dtype=np.uint8)              # (untouched memory; a ctypes buffer's .raw copies the WHOLE capacity on every access -- once per hit, below)
         dst = dst_arr.ctypes.data_as(C.c_void_p)
@@ -52,8 +50,6 @@ def brute_force(raw, expected_size):
     dst_arr = np.empty(slot * nd, dtype=np.uint8)
     dst = dst_arr.ctypes.data_as(C.c_void_p)
     res = (A.Result * nd)()
-    lib.alz_brute_force.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.alz_brute_decoder_name.restype = C.c_char_p
     check(lib.alz_brute_force(_context().h, raw, len(raw), expected_size, dst, slot, res))
     out = {}
     for i in range(nd):
